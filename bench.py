@@ -23,7 +23,9 @@ Modes: default = weak scaling (every rank warps its own K frames of C2); `--c5` 
 on the device from the clip's quaternion tracks, a 64-bit checksum per frame — taken by the warp kernel where the pixels
 leave (gfw_set_frame_checksums; `--sum-pass`: a gfw_checksum64 pass over each destination instead) — all-gathered at the end.
 
-Prints ONE JSON line (rank 0) with
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and reports the headline (`value` in Mpix/s,
+`ms_per_step`, the workload in `config`); `--dump-outputs DIR` also writes what the last timed step computed (dump_outputs).
+`--full` adds what takes time of its own beyond that:
   roofline     — algorithmic HBM bytes/launch (sum over planes of w*h*bpp read + written) over the
                  kernel's mean launch duration, measured with hipEvents on the launch stream (GFW_OPT_PROFILE) during
                  the timed region, against the 8 TB/s HBM3E peak;
@@ -51,7 +53,8 @@ N_RESIDENT = 64                  # distinct source frames + per-row matrix table
                                  # (SURVEY.md 8d "64 distinct resident source frames cycled": 2.1 GB, far beyond L2 + MALL)
 CLIP_FRAMES = 16                 # most frames gfw_undistort_clip puts into one launch (GFW_CLIP_FRAMES_MAX)
 N_DST = 8                        # destination frame sets written round-robin (the frames of one clip launch are in flight together: one set each)
-N_CHECK = 3                      # frames of the timed region compared with the oracle afterwards
+N_CHECK = 3                      # frames of the timed region compared with the oracle afterwards (--full)
+DUMP_BUDGET_BYTES = 48 << 20     # --dump-outputs writes at most this much in all (C2's three planes as float32 are 66 MB: sampled)
 TRAFFIC_FILE = os.path.join("profiles", "r06_c2_traffic.json")       # rocprofv3 PMC passes of the C2 workload; names the kernel source it was taken on (abi.kernel_source_id)
 
 
@@ -69,6 +72,12 @@ def parse_args(argv):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the roofline (hipEvent brackets in the timed region, --profile-every), the oracle's parity verdict on "
+                         "the timed frames, the reference kernel's fixture through the timed call path, and the CPU baseline; a plain run does none of these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step computed (every destination plane of its frame, as float32) to DIR/<name>.npy; "
+                         "planes beyond the size budget are replaced by a fixed, seeded sample of their pixels")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N >= 2 (nccl = RCCL; gloo for the 1-GPU test of the N-rank path)")
     ap.add_argument("--same-device", action="store_true", help="every rank uses cuda:0 (testing the N-rank path on a 1-GPU box; with --backend gloo)")
@@ -109,9 +118,9 @@ def parse_args(argv):
     ap.add_argument("--host-buffers", action="store_true",
                     help="PCIe-inclusive run: source and destination planes live in host memory (BufferSource::Cpu), every "
                          "call stages H2D, warps, copies D2H and synchronises — never the headline value")
-    ap.add_argument("--profile-every", type=int, default=8,
+    ap.add_argument("--profile-every", type=int, default=None,
                     help="bracket every N-th launch of the timed region with hipEvents for the roofline's kernel duration "
-                         "(0 = none); the event pairs themselves cost GPU time between back-to-back kernels")
+                         "(0 = none; default 8 with --full, else 0); the event pairs themselves cost GPU time between back-to-back kernels")
     ap.add_argument("--digital", default="", help="digital lens on top of the physical one (gopro_superview, gopro_hyperview, ...)")
     ap.add_argument("--lens-model", default="", help="physical lens model instead of opencv_fisheye (opencv_standard, poly3, poly5, ptlens, insta360, "
                                                      "sony, generic_polynomial, gopro): the fused kernel's generic-model body")
@@ -136,7 +145,10 @@ def parse_args(argv):
     ap.add_argument("--upload-matrices", action="store_true",
                     help="upload the per-row matrices from host memory every frame (the reference's OpenCL backend does, "
                          "opencl.rs:406) instead of keeping the pre-packed tables of the clip resident in HBM")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.profile_every is None:
+        args.profile_every = 8 if args.full else 0
+    return args
 
 
 # ---------------------------------------------------------------------------------------------- launcher
@@ -232,6 +244,21 @@ def host_threads():
         n = max(1, int(quota + 0.5))
         why += ", CFS quota of the container: %.1f CPUs" % quota
     return n, why
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: each array as out_dir/<name>.npy in float32 (every pixel type the library writes is exact in it).  Arrays that exceed `budget`
+    bytes together are each replaced by the same share of their elements, a sample drawn with a seed of the array's name and kept in index order:
+    two runs with the same arguments write the same positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total, keep = sum(np.asarray(a).size for a in arrays.values()), budget // 4
+    for name, a in arrays.items():
+        a = np.asarray(a).astype(np.float32)
+        if total > keep:
+            idx = np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, a.size * keep // total, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 class _FrameView:
@@ -658,6 +685,15 @@ def worker(args):
         rank_crcs = [g[0] for g in shard.gather_checksums(dist, [crc], cdev)]
         crc = shard.reduce_checksum(dist, crc, cdev)
 
+    # ---- what the last timed step computed (--dump-outputs): the destination planes of its frame, pixels as a caller of the path receives them
+    if args.dump_outputs and rank == 0:
+        last, planes_out = plan(n_steps - 1)[2], {}
+        for p, pl in enumerate(frames[0].planes):
+            ow, oh, ostride = pl["out_size"]
+            rows_b = dst_host(last, p)[:oh * ostride].reshape(oh, ostride)[:, :ow * pl["params"].bytes_per_pixel]
+            planes_out["plane%d" % p] = np.ascontiguousarray(rows_b).view(abi.PIXEL_TYPES[types[p]][1])
+        dump_outputs(args.dump_outputs, planes_out)
+
     luma_px = frames[0].luma_pixels()
     alg_bytes = frames[0].algorithmic_bytes()
     frames_done = total if args.c5 else n_steps * world
@@ -714,8 +750,8 @@ def worker(args):
                            "frames_per_launch": round(fpl, 3), "kernel_ms_per_frame": round(per_launch_ms / fpl, 5),
                            "algorithmic_bytes_per_launch": int(alg_bytes * fpl), "launches": launches}
 
-    # ---- parity of the timed region's own output, and the CPU baseline (rank 0) ---------------------------------
-    if rank == 0 and not (args.no_parity and (args.no_cpu_baseline or world > 1)):
+    # ---- parity of the timed region's own output, and the CPU baseline (rank 0, --full) ---------------------------------
+    if rank == 0 and args.full and not (args.no_parity and (args.no_cpu_baseline or world > 1)):
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import _oracle as O
         checks, seen_d = [], set()

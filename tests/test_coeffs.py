@@ -1,6 +1,6 @@
-"""The 32-phase tap table: generator output == committed tables == the reference's literal table (when mounted)."""
+"""The 32-phase tap table: generator output == committed tables == the reference's literal table (tests/golden/ref_coeffs.json)."""
+import json
 import os
-import re
 import sys
 
 import numpy as np
@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import gen_coeffs  # noqa: E402
 
-REF = "/root/reference/src/core/stabilization/cpu_undistort.rs"
+REF_COEFFS = os.path.join(ROOT, "tests", "golden", "ref_coeffs.json")     # written by tests/golden/make_ref_coeffs.py
 
 
 def parse_inc(path):
@@ -32,13 +32,8 @@ def test_bilinear_rows_are_exact_k_over_32():
     assert np.array_equal(t[:, 1], k * np.float32(0.03125)) and np.array_equal(t[:, 0], np.float32(1.0) - k * np.float32(0.03125))
 
 
-def test_table_equals_reference_literals_when_mounted():
-    if not os.path.exists(REF):
-        import pytest
-        pytest.skip("reference tree not mounted on this box")
-    src = open(REF).read()
-    m = re.search(r"pub const COEFFS.*?= \[(.*?)\];", src, re.S)
-    body = re.sub(r"//.*", "", m.group(1))
-    ref = np.array([float(t) for t in body.replace("\n", " ").split(",") if t.strip()], dtype=np.float32)[:448]
+def test_table_equals_reference_literals():
+    ref = np.array(json.load(open(REF_COEFFS))["coeffs"], dtype=np.float32)
+    assert ref.size == 448
     ours = np.array(gen_coeffs.table(), dtype=np.float32)
     assert np.array_equal(ref.view(np.uint32), ours.view(np.uint32))

@@ -55,7 +55,7 @@ def test_every_collective_of_the_sharded_run_on_device_tensors(tmp_path):
 
 def test_bench_as_a_one_rank_rccl_job():
     """the driver's N > 1 launch shape with N = 1: RANK / WORLD_SIZE from the environment, process group on RCCL, control tensors on the device"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "4", "--backend", "nccl", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "4", "--backend", "nccl", "--full", "--no-cpu-baseline",
                         "--width", "1280", "--height", "720"], env=_env(29542), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
