@@ -673,9 +673,10 @@ static int run_planes(gfw_ctx *c, int nplanes, const gfw_buffers *planes, const 
 
     GfwCommon C;
     GfwYuvArgs Y;
-    int bps = 0, n0 = 1, dw = 1, dh = 1; bool interleaved = false, fast1 = false;
+    int bps = 0, n0 = 1, dw = 1, dh = 1, p1_err = GFW_OK; bool interleaved = false, fast1 = false;
     const bool fused = build_yuv_args(c, nplanes, planes, params, pixel_types, launches, c->matrices_on_device ? nullptr : matrices,
-                                      matrix_count, mesh_len, Y, bps, n0, dw, dh, interleaved, fast1);
+                                      matrix_count, mesh_len, Y, bps, n0, dw, dh, interleaved, fast1, batch, p1_err);
+    if (p1_err != GFW_OK) return p1_err;              // (the held frames' launch, sent because the first pass's table was about to be rebuilt)
     // gfw_set_frame_checksums: this frame's word.  The specialised fused kernel takes the checksum in its store path when every plane starts on a 64-bit word and
     // every element it stores lies inside one (strides aligned to the element: always, but for a caller's odd sub-buffer); everything else is followed by a pass
     // over what it wrote.  In a clip launch the alignment is the first frame's to answer for the kernel choice and every frame's to meet (checked where frames join).
@@ -705,6 +706,7 @@ static int run_planes(gfw_ctx *c, int nplanes, const gfw_buffers *planes, const 
         for (int i = 0; i < nplanes; ++i) all_device = all_device && planes[i].input.kind != GFW_BUF_HOST && planes[i].output.kind != GFW_BUF_HOST;
         if (jf && batch && all_device && c->bslot_cur < 0 && c->mslot_cur < 0) {      // (a table of the cross-stream ring is ordered by events: frame by frame)
             // the frame joins the clip launch being assembled; a frame that does not share the pending ones' kernel or first-pass table goes out behind them
+            // (a frame that REBUILT the table has already sent them on their way, before the copy: p1_setup — they read the table with the range they were set up for)
             if (batch->n > 0 && (batch->fn != jf || batch->CA.Y.p1_table != Y.p1_table || batch->CA.Y.p1_rho_max != Y.p1_rho_max ||
                                  batch->CA.Y.p1_rho_scale != Y.p1_rho_scale || batch->CA.Y.p1_eps != Y.p1_eps || batch->CA.Y.p1_ew != Y.p1_ew ||
                                  !clip_same_params(batch->CA.Y, Y) || clip_overlaps(batch, planes, nplanes))) {

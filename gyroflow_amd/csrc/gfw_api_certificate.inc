@@ -48,7 +48,12 @@ static P1Derivs p1_s_derivs(double rho, const float *k) {
     d.s2 = A2 * P + 2.0 * A1 * P1 * w1 + A * (P2 * w1 * w1 + P1 * w2);
     return d;
 }
-static int p1_prepare_table(gfw_ctx *c, const gfw_kernel_params &p, float rho_max) {
+// The table lives in one buffer per context, d_p1_table.  Frames held for a clip launch (a ClipBatch: gfw_api_clip.inc) read it when that launch goes out, with the
+// range constants of the table they were set up against: a rebuild sends them on their way first (as ck_table does), and stream order puts the copy behind them.
+// `err` carries the error of that launch out of the functions below that answer with a bool.
+struct ClipBatch;
+static int clip_flush(gfw_ctx *c, ClipBatch *b);
+static int p1_prepare_table(gfw_ctx *c, const gfw_kernel_params &p, float rho_max, ClipBatch *pending, int &err) {
     if (c->p1_valid && memcmp(c->p1_k, p.k, sizeof(c->p1_k)) == 0 && rho_max <= c->p1_rho_max && rho_max >= 0.5f * c->p1_rho_max) return GFW_OK;
     const int N = GFW_P1_TABLE_N;
     std::vector<float2> tab(N + 1);
@@ -110,6 +115,8 @@ static int p1_prepare_table(gfw_ctx *c, const gfw_kernel_params &p, float rho_ma
     const double etab = h * h / 8.0 * s2max + (smax + h * slope) / 16777216.0;
     if (!(etab == etab) || !(smax == smax) || !(slope == slope) || !(kappa == kappa) || !(t32 == t32)) { c->p1_valid = false; return GFW_OK; }
     if (!c->dry) {
+        err = clip_flush(c, pending);                               // (a pending launch names the table that is about to move)
+        if (err != GFW_OK) return err;
         HIP_TRY(c->d_p1_table.ensure((N + 1) * sizeof(float2)), GFW_ERR_HIP);
         HIP_TRY(hipMemcpyAsync(c->d_p1_table.ptr, tab.data(), (N + 1) * sizeof(float2), hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
         HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);      // `tab` is a stack-lifetime source
@@ -300,7 +307,8 @@ static void p1_radial_free(gfw_ctx *c) { delete c->p1_radial; c->p1_radial = nul
 //   the table by f r_max e_table per path's share (chord of an interval h under T2, the entries' and the fma's roundings); the last two products and the fma 3 u vmag;
 //   the EXACT path beyond its linear forms and divisions (in D): its r (2u), r_norm = k1 p (1u), the quotient, the product by pos, by f, the sum with c (5u vmag in
 //   all) and the Newton result itself, f nu2 (p1_prepare_radial_gopro).
-static bool p1_setup_radial(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_matrices, int matrix_count, double rho_max, bool hrs, GfwYuvArgs &Y, bool &table_ok) {
+static bool p1_setup_radial(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_matrices, int matrix_count, double rho_max, bool hrs, GfwYuvArgs &Y, bool &table_ok,
+                            ClipBatch *pending, int &err) {
     double r_need = sqrt(rho_max);
     P1Radial *R = c->p1_radial;
     if (!(R && R->ok && R->model == c->model && memcmp(R->k, p0.k, sizeof(R->k)) == 0 && r_need <= R->r_max && r_need >= 0.7 * R->r_max)) {
@@ -310,6 +318,8 @@ static bool p1_setup_radial(gfw_ctx *c, const gfw_kernel_params &p0, const float
         R->model = c->model;
         if (!p1_prepare_radial(c->model, p0, r_need, *R, &tab)) { R->ok = false; return false; }
         if (!c->dry) {
+            err = clip_flush(c, pending);                           // (a pending launch names the table that is about to move)
+            if (err != GFW_OK) { R->ok = false; return false; }
             if (c->d_p1_table.ensure((GFW_P1_TABLE_N + 1) * sizeof(float2)) != hipSuccess) { R->ok = false; return false; }
             if (hipMemcpyAsync(c->d_p1_table.ptr, tab.data(), (GFW_P1_TABLE_N + 1) * sizeof(float2), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
                 hipStreamSynchronize(c->stream) != hipSuccess) { R->ok = false; return false; }      // (`tab` is a stack-lifetime source)
@@ -350,7 +360,7 @@ static bool p1_setup_radial(gfw_ctx *c, const gfw_kernel_params &p0, const float
     return true;
 }
 // Fill the first-pass fields of the fused kernel's arguments; returns true when the certified pass may be used.
-static bool p1_setup(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_matrices, int matrix_count, GfwYuvArgs &Y, bool &table_ok) {
+static bool p1_setup(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_matrices, int matrix_count, GfwYuvArgs &Y, bool &table_ok, ClipBatch *pending, int &err) {
     Y.p1_table = nullptr; Y.audit = nullptr; table_ok = false;
     if (c->kernel_variant == 2) return false;                   // forced exact first pass (tests / A-B benchmarking)
     const bool radial = p1_model_radial_served(c->model);       // (round 6) GoPro, Sony, generic polynomial: certified through a table over r, in specialised builds only
@@ -383,10 +393,10 @@ static bool p1_setup(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_mat
     }
     if (!(rho_max == rho_max)) return false;
     if (rho_max > 64.0) rho_max = 64.0;
-    if (radial) return p1_setup_radial(c, p0, h_matrices, matrix_count, rho_max, hrs, Y, table_ok);
+    if (radial) return p1_setup_radial(c, p0, h_matrices, matrix_count, rho_max, hrs, Y, table_ok, pending, err);
     if (!(c->p1_valid && memcmp(c->p1_k, p0.k, sizeof(c->p1_k)) == 0 && rho_max <= c->p1_rho_max && rho_max >= 0.5 * c->p1_rho_max))
         rho_max = fmin(rho_max * 1.15, 64.0);                   // head-room so that frame-to-frame motion does not rebuild the table
-    if (p1_prepare_table(c, p0, (float)rho_max) != GFW_OK || !c->p1_valid) return false;
+    if (p1_prepare_table(c, p0, (float)rho_max, pending, err) != GFW_OK || !c->p1_valid) return false;
     const double f = fabs((double)(hrs ? p0.f[0] : p0.f[1])), cc = fabs((double)(hrs ? p0.c[0] : p0.c[1]));
     const double rmax = sqrt((double)c->p1_rho_max);
     const double vmag = f * rmax * c->p1_smax + cc;

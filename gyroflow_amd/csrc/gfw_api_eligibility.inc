@@ -1,9 +1,10 @@
 // gfw_api_eligibility.inc — which frames the fused kernel serves, and its argument block (included by gfw_api.hip: one translation unit)
 // Decide whether the frame qualifies for the fused YUV kernel and, if so, build its argument block.
 // Anything not proven here runs through the generic per-plane kernel (same results, slower).
+// `pending`: the frames held for a clip launch on this context, sent first if the first pass's table has to be rebuilt; `err` is that launch's error (else GFW_OK).
 static bool build_yuv_args(gfw_ctx *c, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params, const int *pixel_types,
                            const GfwPlane *launches, const float *h_matrices, int matrix_count, size_t mesh_len,
-                           GfwYuvArgs &Y, int &bytes_per_sample, int &n0, int &dw, int &dh, bool &interleaved, bool &fast1) {
+                           GfwYuvArgs &Y, int &bytes_per_sample, int &n0, int &dw, int &dh, bool &interleaved, bool &fast1, ClipBatch *pending, int &err) {
     if (c->kernel_variant == 1) return false;                       // forced generic (tests / A-B benchmarking)
     if (nplanes < 1 || nplanes > 4) return false;
     const gfw_kernel_params &p0 = params[0];
@@ -184,7 +185,7 @@ static bool build_yuv_args(gfw_ctx *c, int nplanes, const gfw_buffers *planes, c
     Y.grid_limit = c->tune_grid > 0 ? c->tune_grid : c->num_cus * 6;
     Y.ablate = 0;                                                             // (reserved: the timing ablations live in GFW_TESTING builds of the kernel source only, gfw_frame.hip)
     bool table_ok = false;
-    fast1 = (extras || p0.output_width > 65535 || p0.output_height > 65535) ? false : p1_setup(c, p0, h_matrices, matrix_count, Y, table_ok);   // deferred pixels are parked as (x | y << 16)
+    fast1 = (extras || p0.output_width > 65535 || p0.output_height > 65535) ? false : p1_setup(c, p0, h_matrices, matrix_count, Y, table_ok, pending, err);   // deferred pixels are parked as (x | y << 16)
     const int rb = gfw_yuv_rows_per_lane(fast1, Y.audit ? 0 : c->tune_rb);
     Y.tiles_x = (Y.cw + 63) / 64; Y.tiles_y = (Y.ch + 4 * rb - 1) / (4 * rb);
     return true;

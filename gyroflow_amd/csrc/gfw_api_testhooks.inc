@@ -90,8 +90,8 @@ extern "C" int gfw_debug_jit_key(int nplanes, const gfw_buffers *planes, const g
     memset(launches, 0, sizeof(launches));
     for (int i = 0; i < nplanes; ++i) { launches[i].src = (const uint8_t *)planes[i].input.data; launches[i].dst = (uint8_t *)planes[i].output.data; }
     GfwYuvArgs Y;
-    int bps = 0, n0 = 1, dw = 1, dh = 1; bool interleaved = false, fast1 = false;
-    if (!build_yuv_args(&c, nplanes, planes, params, pixel_types, launches, matrices_on_device ? nullptr : h_matrices, matrix_count, 0, Y, bps, n0, dw, dh, interleaved, fast1)) {
+    int bps = 0, n0 = 1, dw = 1, dh = 1, err = GFW_OK; bool interleaved = false, fast1 = false;
+    if (!build_yuv_args(&c, nplanes, planes, params, pixel_types, launches, matrices_on_device ? nullptr : h_matrices, matrix_count, 0, Y, bps, n0, dw, dh, interleaved, fast1, nullptr, err)) {
         set_error("not a frame the fused kernel serves"); return GFW_ERR_UNSUPPORTED_BUFFER; }
     fill_common(&c, &params[0], nullptr, nullptr, 0, Y.common);
     const int jit_model = jit_model_of(Y);
