@@ -35,7 +35,10 @@ static int clip_frames_per_launch(size_t bytes_per_frame, size_t budget, int n_c
 }
 static int clip_launch_limit(const GfwYuvArgs &Y, int nplanes, int n_call) {
     size_t bytes = 0;
-    for (int i = 0; i < nplanes && i < 4; ++i) bytes += ((size_t)(Y.pl[i].src_stride < 0 ? -Y.pl[i].src_stride : Y.pl[i].src_stride) + (size_t)(Y.pl[i].dst_stride < 0 ? -Y.pl[i].dst_stride : Y.pl[i].dst_stride)) * (size_t)Y.pl[i].h;
+    for (int i = 0; i < nplanes && i < 4; ++i) {     // source rows of the plane + destination rows of its OUTPUT (a scaled render's differ: 1080p -> 4K writes four times what it reads)
+        const size_t out_rows = (size_t)(i == 0 ? Y.out_h : Y.ch);
+        bytes += (size_t)(Y.pl[i].src_stride < 0 ? -Y.pl[i].src_stride : Y.pl[i].src_stride) * (size_t)Y.pl[i].h + (size_t)(Y.pl[i].dst_stride < 0 ? -Y.pl[i].dst_stride : Y.pl[i].dst_stride) * out_rows;
+    }
     return clip_frames_per_launch(bytes, clip_launch_bytes(), n_call);
 }
 // the launch's table of partial sums: one word per frame, workgroup and wave (gfw_frame.hip ck_flush)
