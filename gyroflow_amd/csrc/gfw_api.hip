@@ -125,7 +125,7 @@ struct gfw_ctx {
     bool dry = false;                              // gfw_debug_jit_key: argument blocks are built, nothing touches a device
     std::string arch;                              // gcnArchName of the device
     std::string jit_header; int jit_seen = 0;      // bake header of the frames being seen, and how many in a row
-    GfwYuvArgs jit_key; int jit_key_misc[8] = {}; bool jit_key_valid = false;      // the clip those frames belong to (argument block, per-frame fields blanked)
+    GfwYuvArgs jit_key; int jit_key_misc[9] = {}; bool jit_key_valid = false;      // the clip those frames belong to (argument block, per-frame fields blanked)
     hipFunction_t jit_fn = nullptr; int jit_grid = 0;                               // its specialised kernel once loaded
     bool jit_dead = false;                                                          // ... or the verdict that there will be none for this clip (build failed / cache full)
     GfwJitInfo jit_info = {GFW_JIT_UNAVAILABLE, 0.0, std::string()};
@@ -693,7 +693,8 @@ static int run_planes(gfw_ctx *c, int nplanes, const gfw_buffers *planes, const 
             Y.checksum = (aligned && lane_rows < 8 * 32768ll) ? 1 : 0;
         }
         int jgrid = 0;
-        hipFunction_t jf = jit_for(c, Y, bps, params[0].interpolation, n0, dw, dh, interleaved, fast1, &jgrid);
+        const bool perframe = batch && batch->perframe;      // (gfw_undistort_clip_params: the per-frame flavour, whose key blanks the per-frame fields)
+        hipFunction_t jf = jit_for(c, Y, bps, params[0].interpolation, n0, dw, dh, interleaved, fast1, &jgrid, perframe);
         if (!jf && fast1 && Y.p1_rform) {
             // a table over r is read by specialised builds only: until one is loaded (or for good, without hiprtc and without a cached kernel) the frame takes the
             // ahead-of-time generic-model kernel and its exact first pass — whose tiles are one lane-row tall
@@ -709,13 +710,14 @@ static int run_planes(gfw_ctx *c, int nplanes, const gfw_buffers *planes, const 
             // (a frame that REBUILT the table has already sent them on their way, before the copy: p1_setup — they read the table with the range they were set up for)
             if (batch->n > 0 && (batch->fn != jf || batch->CA.Y.p1_table != Y.p1_table || batch->CA.Y.p1_rho_max != Y.p1_rho_max ||
                                  batch->CA.Y.p1_rho_scale != Y.p1_rho_scale || batch->CA.Y.p1_eps != Y.p1_eps || batch->CA.Y.p1_ew != Y.p1_ew ||
-                                 !clip_same_params(batch->CA.Y, Y) || clip_overlaps(batch, planes, nplanes))) {
+                                 !(perframe ? clip_same_params_pf(batch->CA.Y, Y) : clip_same_params(batch->CA.Y, Y)) || clip_overlaps(batch, planes, nplanes))) {
                 const int frc = clip_flush(c, batch); if (frc != GFW_OK) return frc;
             }
             if (batch->n == 0) { batch->CA.Y = Y; batch->fn = jf; batch->grid = jgrid; batch->first = planes; batch->backend = fast1 ? "yuv_fused_p1_jit" : "yuv_fused_jit";
                                  batch->limit = clip_launch_limit(Y, nplanes, batch->n_call); }
             batch->sums[batch->n] = sum;
             sum_commit(c, sum);                       // the frame is part of the pending launch from here on
+            if (perframe) batch->pf[batch->n] = frame_slot(Y);
             GfwFrameDyn &F = batch->CA.fr[batch->n++];
             for (int i = 0; i < 4; ++i) { F.src[i] = Y.pl[i].src; F.dst[i] = Y.pl[i].dst; }
             F.matrices = Y.matrices;
@@ -734,7 +736,11 @@ static int run_planes(gfw_ctx *c, int nplanes, const gfw_buffers *planes, const 
             CA.Y = Y; CA.n_frames = 1; CA.pad_ = 0;
             for (int i = 0; i < 4; ++i) { CA.fr[0].src[i] = Y.pl[i].src; CA.fr[0].dst[i] = Y.pl[i].dst; }
             CA.fr[0].matrices = Y.matrices;
-            HIP_TRY(gfw_jit_launch(jf, CA, jgrid, c->stream), GFW_ERR_HIP);
+            if (perframe) {                           // (a frame of gfw_undistort_clip_params that cannot join a launch — host buffers, a table of the ring — still takes its call's kernel)
+                GfwClipArgsPF PF;
+                PF.C = CA; memset(PF.fr_pf, 0, sizeof(PF.fr_pf)); PF.fr_pf[0] = frame_slot(Y);
+                HIP_TRY(gfw_jit_launch_pf(jf, PF, jgrid, c->stream), GFW_ERR_HIP);
+            } else HIP_TRY(gfw_jit_launch(jf, CA, jgrid, c->stream), GFW_ERR_HIP);
             if (sum_taken) { const int krc = ck_finish(c, CA, jgrid, &sum); if (krc != GFW_OK) return krc; }
             timeline_dump(c, jf);
             c->last_backend = fast1 ? "yuv_fused_p1_jit" : "yuv_fused_jit";
@@ -940,6 +946,36 @@ int gfw_undistort_clip(gfw_ctx *c, int n_frames, int nplanes, const gfw_buffers 
     const int frc = clip_flush(c, &batch);
     // GFW_OPT_SYNCHRONOUS (the default) means what it means for gfw_undistort_frame: the outputs are complete when the call returns — a frame that
     // joined a clip launch left run_planes before its own synchronisation point (round-3 advisor finding)
+    if (c->synchronous) { const hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess && frc == GFW_OK) { set_error("hipStreamSynchronize failed: %s", hipGetErrorString(e)); return GFW_ERR_HIP; } }
+    return frc;
+}
+
+// The frame loop of a render whose KernelParams move from frame to frame (FrameTransform::at_timestamp fills them per frame: the adaptive-zoom fov and its
+// centre, keyframed lens correction and background margin; the render loop sets FILL_WITH_BACKGROUND per frame).  Frames run exactly as gfw_undistort_frame would
+// run each with its own params; frames that share everything else leave in launches of the per-frame flavour of the specialised kernel,
+// each frame's fields in its slot of the launch.  Every frame is validated through run_planes: there is no shared block to vouch for a frame.
+int gfw_undistort_clip_params(gfw_ctx *c, int n_frames, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params,
+                              const int *pixel_types, const float *const *matrices, int matrix_count) {
+    if (!c) { set_error("null context"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (n_frames < 0 || !planes || !params || !pixel_types || !matrices) { set_error("null clip arrays"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (nplanes < 1 || nplanes > 8) { set_error("nplanes %d", nplanes); return GFW_ERR_INVALID_ARGUMENT; }
+    for (int i = 0; i < nplanes; ++i)
+        if (pixel_types[i] < 0 || pixel_types[i] >= GFW_PIX_COUNT) { set_error("plane %d: unknown pixel type %d", i, pixel_types[i]); return GFW_ERR_INVALID_ARGUMENT; }
+    { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
+    ClipBatch batch;
+    batch.n_call = n_frames;
+    batch.perframe = true;
+    // the first-pass table's envelope: the call knows every frame's fov and zoom centre, so the table is sized once for all of them (p1_setup)
+    for (int f = 0; f < n_frames; ++f) {
+        double hx, hy;
+        p1_corner_extent(params[(size_t)f * nplanes], hx, hy);
+        batch.env_hx = fmax(batch.env_hx, hx); batch.env_hy = fmax(batch.env_hy, hy);
+    }
+    for (int f = 0; f < n_frames; ++f) {
+        const int rc = run_planes(c, nplanes, planes + (size_t)f * nplanes, params + (size_t)f * nplanes, pixel_types, matrices[f], matrix_count, nullptr, 0, &batch);
+        if (rc != GFW_OK) { (void)clip_flush(c, &batch); if (c->synchronous) (void)hipStreamSynchronize(c->stream); return rc; }
+    }
+    const int frc = clip_flush(c, &batch);
     if (c->synchronous) { const hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess && frc == GFW_OK) { set_error("hipStreamSynchronize failed: %s", hipGetErrorString(e)); return GFW_ERR_HIP; } }
     return frc;
 }

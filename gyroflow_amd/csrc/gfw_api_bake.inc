@@ -15,7 +15,9 @@ static int jit_rows(bool fast1) {
     static const int env = [] { const char *e = getenv("GFW_JIT_RB_FAST"); const int v = e ? atoi(e) : 0; return (v >= 1 && v * 4 <= 64) ? v : 0; }();
     return (fast1 && env > 0) ? env : gfw_yuv_rows_per_lane(fast1, 0);
 }
-static std::string bake_header(const GfwYuvArgs &Y_in, bool fast1) {
+// perframe: the header of the per-frame flavour (GFW_JIT_PERFRAME, gfw_undistort_clip_params) — translation2d and FILL_WITH_BACKGROUND are not literals there (the
+// kernel reads them from each frame's slot), so they are left out: a use that slipped past the flavour would not compile.
+static std::string bake_header(const GfwYuvArgs &Y_in, bool fast1, bool perframe = false) {
     GfwYuvArgs Y = Y_in;
     { const int rb = jit_rows(fast1); Y.tiles_y = (Y.ch + 4 * rb - 1) / (4 * rb); }          // (the launch's own tiling: the argument block carries the ahead-of-time kernels')
     std::string o;
@@ -25,14 +27,15 @@ static std::string bake_header(const GfwYuvArgs &Y_in, bool fast1) {
     bake_i(o, "hrs", Y.hrs); bake_i(o, "model", Y.model); bake_i(o, "k_all_zero", Y.k_all_zero);
     bake_i(o, "background_mode", Y.background_mode); bake_i(o, "extras", Y.extras); bake_i(o, "ablate", 0);
     bake_i(o, "digital", (Y.extras & 2) ? Y.common.digital : 0);
-    bake_i(o, "fill_bg", Y.fill_bg); bake_i(o, "rot_on", Y.rot_on); bake_i(o, "fix_range", Y.fix_range); bake_i(o, "checksum", Y.checksum);
+    if (!perframe) bake_i(o, "fill_bg", Y.fill_bg);
+    bake_i(o, "rot_on", Y.rot_on); bake_i(o, "fix_range", Y.fix_range); bake_i(o, "checksum", Y.checksum);
     bake_i(o, "hstretch_div", Y.hstretch_div); bake_i(o, "vstretch_div", Y.vstretch_div); bake_f(o, "hstretch", Y.hstretch); bake_f(o, "vstretch", Y.vstretch);
     // (an audit build — GFW_OPT_KERNEL_VARIANT 3 / 4 on a clip whose certified first pass lives in specialised builds only, the radial models' — reads the counters' address from the arguments)
     o += Y.audit ? "#define GFW_BK_audit (A.audit)\n" : "#define GFW_BK_audit ((unsigned long long *)nullptr)\n";
     { char b[64]; snprintf(b, sizeof(b), "#define GFW_P1_RFORM (%d)\n", Y.p1_rform ? 1 : 0); o += b; }
     char nm[48];
     for (int i = 0; i < 2; ++i) { snprintf(nm, sizeof(nm), "f_%d", i); bake_f(o, nm, Y.f[i]); snprintf(nm, sizeof(nm), "c_%d", i); bake_f(o, nm, Y.c[i]);
-                                  snprintf(nm, sizeof(nm), "t2_%d", i); bake_f(o, nm, Y.t2[i]); }
+                                  if (!perframe) { snprintf(nm, sizeof(nm), "t2_%d", i); bake_f(o, nm, Y.t2[i]); } }
     for (int i = 0; i < 4; ++i) { snprintf(nm, sizeof(nm), "k_%d", i); bake_f(o, nm, Y.k[i]); }
     bake_f(o, "r_limit_sq", Y.r_limit_sq);
     const GfwMapConst *maps[4] = {&Y.map_lx, &Y.map_ly, &Y.map_cx, &Y.map_cy};
@@ -81,7 +84,7 @@ static int jit_waves(int n0, int matrix_count, int jit_model, int extras, int ta
     return (n0 == 1 && matrix_count > 1) ? 8 : 7;
 }
 // The definition list of a specialised build (with the bake header: everything that names the kernel)
-static std::vector<std::string> jit_defs(const GfwYuvArgs &Y, int bps, int taps, int n0, int dw, int dh, bool interleaved, bool fast1, int jit_model, int waves) {
+static std::vector<std::string> jit_defs(const GfwYuvArgs &Y, int bps, int taps, int n0, int dw, int dh, bool interleaved, bool fast1, int jit_model, int waves, bool perframe = false) {
     (void)Y;
     char b[64];
     std::vector<std::string> defs;
@@ -96,6 +99,7 @@ static std::vector<std::string> jit_defs(const GfwYuvArgs &Y, int bps, int taps,
     snprintf(b, sizeof(b), "GFW_JIT_IL=%d", interleaved ? 1 : 0); defs.push_back(b);
     snprintf(b, sizeof(b), "GFW_JIT_RB=%d", jit_rows(fast1)); defs.push_back(b);
     snprintf(b, sizeof(b), "GFW_JIT_FAST1=%d", fast1 ? 1 : 0); defs.push_back(b);
+    if (perframe) defs.push_back("GFW_JIT_PERFRAME=1");                                   // (absent otherwise: the other flavours' definition lists — their cache names — are unchanged)
     if (const char *extra = getenv("GFW_JIT_DEFS")) {                                    // experiments: further ';'-separated definitions for the build
         std::string cur;
         for (const char *p = extra; ; ++p) { if (*p == ';' || *p == 0) { if (!cur.empty()) defs.push_back(cur); cur.clear(); if (!*p) break; } else cur += *p; }
@@ -106,8 +110,10 @@ static int jit_model_of(const GfwYuvArgs &Y) {
     return (Y.model == GFW_MODEL_OPENCV_FISHEYE && (Y.extras & ~2) == 0) ? GFW_MODEL_OPENCV_FISHEYE : ((Y.extras & (16 | 32)) ? -2 : -1);
 }
 // The specialised kernel for this frame's arguments, or nullptr (not eligible / not wanted / not ready / failed): the caller then
-// launches the ahead-of-time kernel.
-static hipFunction_t jit_for(gfw_ctx *c, const GfwYuvArgs &Y, int bps, int taps, int n0, int dw, int dh, bool interleaved, bool fast1, int *grid) {
+// launches the ahead-of-time kernel.  perframe: the per-frame flavour (gfw_undistort_clip_params): its launches take GfwClipArgsPF (gfw_jit_launch_pf), and its
+// key blanks the fields the frames carry in their slots as well — translation2d and the fill flag here, fov / lens-correction amount / margin / feather with `kp` —
+// so that one kernel serves the clip and the kJitAfter count runs on under a moving zoom centre.
+static hipFunction_t jit_for(gfw_ctx *c, const GfwYuvArgs &Y, int bps, int taps, int n0, int dw, int dh, bool interleaved, bool fast1, int *grid, bool perframe = false) {
     // every frame the fused kernel serves can be specialised: the fisheye model alone or under a digital lens (extras 0 / 2) takes the lean
     // projection (MODEL = 1); everything else the generic-model body with the lens model, the digital lens and the feature bits as literals
     // (MODEL = -1, or -2 with background mode 3 / the Sony mesh) — the run-time switch over 14 lens models folds to the one in use
@@ -123,7 +129,8 @@ static hipFunction_t jit_for(gfw_ctx *c, const GfwYuvArgs &Y, int bps, int taps,
     memset(K.p1_lat, 0, sizeof(K.p1_lat));
     memset(&K.kp, 0, sizeof(K.kp));
     { const int dig = K.common.digital; memset(&K.common, 0, sizeof(K.common)); K.common.digital = dig; }
-    const int key_misc[8] = {bps, taps, n0, dw, dh, interleaved ? 1 : 0, fast1 ? 1 : 0, c->tune_grid};
+    if (perframe) { K.t2[0] = K.t2[1] = 0.0f; K.fill_bg = 0; }
+    const int key_misc[9] = {bps, taps, n0, dw, dh, interleaved ? 1 : 0, fast1 ? 1 : 0, c->tune_grid, perframe ? 1 : 0};
     const bool same = c->jit_key_valid && memcmp(&K, &c->jit_key, sizeof(K)) == 0 && memcmp(key_misc, c->jit_key_misc, sizeof(key_misc)) == 0;
     if (same) {
         if (c->jit_seen < (1 << 30)) ++c->jit_seen;
@@ -131,12 +138,15 @@ static hipFunction_t jit_for(gfw_ctx *c, const GfwYuvArgs &Y, int bps, int taps,
         if (c->jit_dead) return nullptr;                                                 // decided: ahead of time for the rest of the clip, no lookup per frame
     } else {
         c->jit_key = K; memcpy(c->jit_key_misc, key_misc, sizeof(key_misc)); c->jit_key_valid = true;
-        c->jit_header = bake_header(Y, fast1); c->jit_seen = 1; c->jit_fn = nullptr; c->jit_dead = false;
+        c->jit_header = bake_header(Y, fast1, perframe); c->jit_seen = 1; c->jit_fn = nullptr; c->jit_dead = false;
         c->jit_info = GfwJitInfo{GFW_JIT_UNAVAILABLE, 0.0, std::string()};
     }
     if (c->jit_mode == 1 && c->jit_seen < gfw_ctx::kJitAfter && !audit_build) return nullptr;          // one or two frames are not a clip
-    const int waves = jit_waves(n0, Y.matrix_count, jit_model, Y.extras, taps, bps, dh, Y.checksum);
-    std::vector<std::string> defs = jit_defs(Y, bps, taps, n0, dw, dh, interleaved, fast1, jit_model, waves);
+    int waves = jit_waves(n0, Y.matrix_count, jit_model, Y.extras, taps, bps, dh, Y.checksum);
+    // (the per-frame flavour of the lens-correction body keeps one more value of the frame alive through the pixel loop: at eight waves 24 bytes went to scratch
+    // on 4K NV12, so it gets seven — as the checksum build does; every other body keeps its constant build's waves: tests/test_kernel_resources_perframe.py)
+    if (perframe && (Y.extras & 8) && waves == 8) waves = 7;
+    std::vector<std::string> defs = jit_defs(Y, bps, taps, n0, dw, dh, interleaved, fast1, jit_model, waves, perframe);
     if (audit_build) defs.push_back("GFW_JIT_AUDIT=1");
     hipFunction_t fn = gfw_jit_get(c->device, c->arch, defs, c->jit_header, c->jit_mode == 2 || audit_build, &c->jit_info);
     if (!fn) { c->jit_dead = c->jit_info.state == GFW_JIT_FAILED || c->jit_info.state == GFW_JIT_UNAVAILABLE; return nullptr; }

@@ -52,6 +52,7 @@ static P1Derivs p1_s_derivs(double rho, const float *k) {
 // range constants of the table they were set up against: a rebuild sends them on their way first (as ck_table does), and stream order puts the copy behind them.
 // `err` carries the error of that launch out of the functions below that answer with a bool.
 struct ClipBatch;
+static void clip_envelope(const ClipBatch *b, double &hx, double &hy);      // (gfw_api_clip.inc)
 static int clip_flush(gfw_ctx *c, ClipBatch *b);
 static int p1_prepare_table(gfw_ctx *c, const gfw_kernel_params &p, float rho_max, ClipBatch *pending, int &err) {
     if (c->p1_valid && memcmp(c->p1_k, p.k, sizeof(c->p1_k)) == 0 && rho_max <= c->p1_rho_max && rho_max >= 0.5f * c->p1_rho_max) return GFW_OK;
@@ -360,6 +361,12 @@ static bool p1_setup_radial(gfw_ctx *c, const gfw_kernel_params &p0, const float
     return true;
 }
 // Fill the first-pass fields of the fused kernel's arguments; returns true when the certified pass may be used.
+// The half-extents of the output frame's corner ray in normalised camera coordinates (new_k = f / fov, frame_transform.rs:37-51; the zoom centre moves it by
+// translation2d) — the first pass's range estimate for device-resident tables
+static void p1_corner_extent(const gfw_kernel_params &p0, double &hx, double &hy) {
+    hx = 0.5 * p0.output_width * (double)p0.fov / fmax(fabs((double)p0.f[0]), 1e-6) + fabs((double)p0.translation2d[0]) * (double)p0.fov / fmax(fabs((double)p0.f[0]), 1e-6);
+    hy = 0.5 * p0.output_height * (double)p0.fov / fmax(fabs((double)p0.f[1]), 1e-6) + fabs((double)p0.translation2d[1]) * (double)p0.fov / fmax(fabs((double)p0.f[1]), 1e-6);
+}
 static bool p1_setup(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_matrices, int matrix_count, GfwYuvArgs &Y, bool &table_ok, ClipBatch *pending, int &err) {
     Y.p1_table = nullptr; Y.audit = nullptr; table_ok = false;
     if (c->kernel_variant == 2) return false;                   // forced exact first pass (tests / A-B benchmarking)
@@ -386,8 +393,10 @@ static bool p1_setup(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_mat
     } else {
         // device-resident matrices: no host view of the geometry.  Bound the corner ray from the intrinsics
         // (new_k = f / fov, frame_transform.rs:37-51) and allow 15 degrees of stabilisation rotation on top (rays beyond it simply take the exact path).
-        const double hx = 0.5 * p0.output_width * (double)p0.fov / fmax(fabs((double)p0.f[0]), 1e-6) + fabs((double)p0.translation2d[0]) * (double)p0.fov / fmax(fabs((double)p0.f[0]), 1e-6);
-        const double hy = 0.5 * p0.output_height * (double)p0.fov / fmax(fabs((double)p0.f[1]), 1e-6) + fabs((double)p0.translation2d[1]) * (double)p0.fov / fmax(fabs((double)p0.f[1]), 1e-6);
+        // (a launch of gfw_undistort_clip_params: the envelope of its frames — one table serves every frame of the call, built at most once)
+        double hx, hy;
+        p1_corner_extent(p0, hx, hy);
+        clip_envelope(pending, hx, hy);
         const double ang = atan(sqrt(hx * hx + hy * hy)) + 0.26;
         rho_max = ang < 1.45 ? tan(ang) * tan(ang) : 64.0;
     }

@@ -13,7 +13,25 @@ struct ClipBatch {
     const gfw_buffers *first = nullptr;          // planes of the frame that opened the pending launch (fully validated by run_planes)
     const char *backend = "";
     unsigned long long *sums[GFW_CLIP_MAX] = {};   // gfw_set_frame_checksums: where each frame's checksum goes (the launch's kernel takes it: CA.Y.checksum)
+    // gfw_undistort_clip_params: every frame brings its own KernelParams.  Its launches take the per-frame flavour of the specialised kernel (GFW_JIT_PERFRAME),
+    // pf[k] is frame k's slot, and the first-pass table is sized once for the envelope of the call's frames (p1_setup: env_hx / env_hy, the largest
+    // corner-ray half-extents over the frames' fov and translation2d)
+    bool perframe = false;
+    GfwFramePer pf[GFW_CLIP_MAX] = {};
+    double env_hx = 0.0, env_hy = 0.0;
 };
+static void clip_envelope(const ClipBatch *b, double &hx, double &hy) {
+    if (b && b->perframe) { hx = fmax(hx, b->env_hx); hy = fmax(hy, b->env_hy); }
+}
+// A frame's slot of a per-frame launch: what FrameTransform::at_timestamp and the render loop move from frame to frame (DESIGN.md section 3.2a)
+static GfwFramePer frame_slot(const GfwYuvArgs &Y) {
+    GfwFramePer F;
+    F.t2[0] = Y.t2[0]; F.t2[1] = Y.t2[1];
+    F.fov = Y.kp.fov; F.lens_correction_amount = Y.kp.lens_correction_amount;
+    F.background_margin = Y.kp.background_margin; F.background_margin_feather = Y.kp.background_margin_feather;
+    F.fill_bg = Y.fill_bg; F.pad_ = 0;
+    return F;
+}
 // gfw_set_frame_checksums: the word of the next frame submitted on the context (nullptr: off)
 // (peek: the ring index advances — sum_commit — only once the frame has been enqueued; a call that fails consumes no slot, so "frame k submitted" keeps meaning what gfwarp.h says)
 static unsigned long long *next_sum(gfw_ctx *c) { return (c->sums && c->sum_n) ? c->sums + (c->sum_k % c->sum_n) : nullptr; }
@@ -86,6 +104,18 @@ static bool clip_same_params(const GfwYuvArgs &a, const GfwYuvArgs &b) {
     for (int i = 0; i < 4; ++i) if (a.pl[i].src_len != b.pl[i].src_len || a.pl[i].dst_len != b.pl[i].dst_len) return false;
     return true;
 }
+// The same for a launch of the per-frame flavour: the argument blocks must agree once the per-frame fields are blanked — in the manner of jit_for's key.  The feature
+// bits those fields select (extras: a lens-correction amount below 1, background mode 3, refraction) stay in the comparison, so a frame whose amount reaches 1.0
+// opens a new launch (the flavour's kernel is another).
+static bool clip_same_params_pf(const GfwYuvArgs &a, const GfwYuvArgs &b) {
+    GfwYuvArgs x = a, y = b;
+    for (GfwYuvArgs *v : {&x, &y}) {
+        v->t2[0] = v->t2[1] = 0.0f; v->fill_bg = 0;
+        v->kp.fov = 0.0f; v->kp.lens_correction_amount = 0.0f; v->kp.background_margin = 0.0f; v->kp.background_margin_feather = 0.0f;
+        v->kp.translation2d[0] = v->kp.translation2d[1] = 0.0f; v->kp.flags &= ~GFW_FLAG_FILL_WITH_BACKGROUND;
+    }
+    return clip_same_params(x, y);
+}
 static bool clip_overlaps(const ClipBatch *b, const gfw_buffers *planes, int nplanes) {
     auto hit = [](const uint8_t *p, size_t pl, const uint8_t *q, size_t ql) { return p && q && p < q + ql && q < p + pl; };
     for (int k = 0; k < b->n; ++k) {
@@ -118,7 +148,13 @@ static int clip_flush(gfw_ctx *c, ClipBatch *b) {
     if (!b || b->n == 0) return GFW_OK;
     b->CA.n_frames = b->n; b->CA.pad_ = 0;
     prof_begin(c);
-    const hipError_t e = gfw_jit_launch(b->fn, b->CA, b->grid, c->stream);
+    hipError_t e;
+    if (b->perframe) {
+        GfwClipArgsPF PF;
+        PF.C = b->CA;
+        memcpy(PF.fr_pf, b->pf, sizeof(PF.fr_pf));
+        e = gfw_jit_launch_pf(b->fn, PF, b->grid, c->stream);
+    } else e = gfw_jit_launch(b->fn, b->CA, b->grid, c->stream);
     int crc = GFW_OK;
     if (e == hipSuccess && b->CA.Y.checksum) crc = ck_finish(c, b->CA, b->grid, b->sums);
     prof_end(c, b->n);

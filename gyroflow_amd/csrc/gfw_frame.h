@@ -73,6 +73,11 @@ struct GfwYuvArgs {
 #define GFW_CLIP_MAX 16         // frames per launch (= GFW_CLIP_FRAMES_MAX of gfwarp.h)
 struct GfwFrameDyn { const uint8_t *src[4]; uint8_t *dst[4]; const float *matrices; };
 struct GfwClipArgs { GfwYuvArgs Y; int32_t n_frames; int32_t pad_; GfwFrameDyn fr[GFW_CLIP_MAX]; };
+// The launch of the per-frame flavour (GFW_JIT_PERFRAME builds, gfw_undistort_clip_params): each frame also brings the KernelParams fields that a render
+// moves from frame to frame (FrameTransform::at_timestamp: the adaptive-zoom fov and its centre, keyframed lens correction and background margin; the render
+// loop's FILL_WITH_BACKGROUND).  The flavour reads them from fr_pf[frame] instead of literals or `Y.kp`; 2 224 + 16 x 32 B stays inside the 4 KB of arguments.
+struct GfwFramePer { float t2[2]; float fov, lens_correction_amount, background_margin, background_margin_feather; int32_t fill_bg; int32_t pad_; };
+struct GfwClipArgsPF { GfwClipArgs C; GfwFramePer fr_pf[GFW_CLIP_MAX]; };
 
 #if !defined(GFW_JIT) || !GFW_JIT
 int gfw_yuv_rows_per_lane(bool fast1, int tune_rb);

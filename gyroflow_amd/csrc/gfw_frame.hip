@@ -105,6 +105,13 @@
 #ifndef GFW_BAKE
 #define GFW_BAKE 0               // 1: the clip-invariant arguments are the literals GFW_BK_<field> of the bake header in front of this file (read through AF())
 #endif
+#ifndef GFW_JIT_PERFRAME
+#define GFW_JIT_PERFRAME 0       // 1 (baked builds only): the per-frame flavour of gfw_undistort_clip_params — translation2d, fov, lens_correction_amount, background
+                                 // margin and feather and FILL_WITH_BACKGROUND come from the current frame's slot of the launch (GfwClipArgsPF.fr_pf), not literals or Y.kp
+#endif
+#if GFW_JIT_PERFRAME && !GFW_BAKE
+#error "GFW_JIT_PERFRAME is a flavour of the run-time specialised (baked) build"
+#endif
 #ifndef GFW_TLB
 #define GFW_TLB(k) do {} while (0)
 #define GFW_TLB_START() do {} while (0)
@@ -132,6 +139,22 @@
 #define GFW_BAKED_DIGITAL false
 #define GFW_BAKED_DIGITAL_MODEL (-1)
 #define GFW_CLIP_DIGITAL (A.common.digital)
+#endif
+// The fields a render moves from frame to frame: plane 0's KernelParams / the baked flag — or, in the per-frame flavour, the current
+// frame's slot (wave-uniform: scalar loads).  The fill flag is held from one frame change of the tile walk to the next; the four floats are read where the
+// pixel loop uses them.
+#if GFW_JIT_PERFRAME
+#define GFW_FR_FOV (fr_pf[cur_frame].fov)
+#define GFW_FR_AMOUNT (fr_pf[cur_frame].lens_correction_amount)
+#define GFW_FR_MARGIN (fr_pf[cur_frame].background_margin)
+#define GFW_FR_FEATHER (fr_pf[cur_frame].background_margin_feather)
+#define GFW_FR_FILL fr_fill
+#else
+#define GFW_FR_FOV (A.kp.fov)
+#define GFW_FR_AMOUNT (A.kp.lens_correction_amount)
+#define GFW_FR_MARGIN (A.kp.background_margin)
+#define GFW_FR_FEATHER (A.kp.background_margin_feather)
+#define GFW_FR_FILL (AF(fill_bg) != 0)
 #endif
 
 // Timing ablations (wrong output by design) exist only in builds that say GFW_TESTING=1 — the A/B builds of tools/ through GFW_JIT_DEFS, from a library whose embedded
@@ -1107,16 +1130,16 @@ __device__ __forceinline__ void store_pair1(uint8_t *dst, int off, uint32_t v0, 
 // coordinates for every plane, so alpha and the second point are the same for a luma pixel and the chroma site that shares its
 // coordinate.  Served by the GFW_MODEL_GENERIC_EXTRA instantiation only (extras & 16).
 struct Feather { float alpha, x2, y2; };
-__device__ __forceinline__ Feather feather_of(float ux, float uy, const GfwYuvArgs &A) {
+__device__ __forceinline__ Feather feather_of(float ux, float uy, const GfwYuvArgs &A, const float margin, const float feather_amount) {    // (margin, feather: GFW_FR_*)
     const float width_f = (float)AF(width), height_f = (float)AF(height);
     const float widthf = width_f - 1.0f, heightf = height_f - 1.0f;
-    const float feather = fmaxf(A.kp.background_margin_feather * heightf, 0.0001f);
+    const float feather = fmaxf(feather_amount * heightf, 0.0001f);
     Feather f{1.0f, ux, uy};
     if ((ux > widthf - feather) || (ux < feather) || (uy > heightf - feather) || (uy < feather)) {
         f.alpha = fmaxf(fminf(fminf(fminf(fminf(widthf - ux, heightf - uy), ux), uy) / feather, 1.0f), 0.0f);
         float p2x = ux / width_f, p2y = uy / height_f;
-        p2x = ((p2x - 0.5f) * (1.0f - A.kp.background_margin)) + 0.5f;
-        p2y = ((p2y - 0.5f) * (1.0f - A.kp.background_margin)) + 0.5f;
+        p2x = ((p2x - 0.5f) * (1.0f - margin)) + 0.5f;
+        p2y = ((p2y - 0.5f) * (1.0f - margin)) + 0.5f;
         f.x2 = p2x * width_f; f.y2 = p2y * height_f;
     }
     return f;
@@ -1258,8 +1281,9 @@ namespace {
 // The kernel body.  `clip` (baked builds only): the per-frame pointers of the frames of one launch — the frames of a clip share every
 // other argument, so a launch can carry several of them and the occupancy tail of one frame is filled by the next (the effect two
 // HIP streams showed: 79.3 -> 71.7 us per C2 frame, profiles/r03_ab_northstar.txt) without a second stream or a second launch.
+// `fr_pf` (GFW_JIT_PERFRAME builds only): the frames' per-frame KernelParams fields, indexed by frame like clip->fr (never tested, for the reason given for `clip`).
 template <int MODEL, typename T, int N0, int I, int DW, int DH, bool INTERLEAVED_UV, int RB, bool FAST1, bool AUDIT>
-__device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwClipArgs *clip) {
+__device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwClipArgs *clip, const GfwFramePer *fr_pf = nullptr) {
     // A baked build (run time, gfw_jit.hip) reads every clip-invariant argument as a literal from the bake header (AF(x) = GFW_BK_x): the
     // loads, the uniform branches and the scalar registers they pin disappear — the reference bakes its per-clip constants into the
     // OpenCL source it compiles per clip the same way (opencl.rs:181-214).  Pointers and the per-frame fields stay arguments.
@@ -1378,14 +1402,28 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
         for (int i = tid; i < 448; i += 256) s_lut[i] = GFW_COEFFS[i];
         __syncthreads();
     }
-    const bool two_pass = AF(matrix_count) > 1 && !GFW_ABL(1) && !AF(fill_bg);
+#if GFW_JIT_PERFRAME
+    // the current frame's fields (frame 0 first; the tile walk loads the next frame's at its frame change)
+    bool fr_fill = fr_pf[0].fill_bg != 0;
+    // two_pass_clip: the launch has a first pass at all (its set-up: certificates, range constants); two_pass: the CURRENT frame takes it (not a filled one).
+    // Past the fill branch of phase 3 the two agree, and phase 3 asks two_pass_clip: a literal, so the flavour carries no default_row path it never takes.
+    const bool two_pass_clip = AF(matrix_count) > 1 && !GFW_ABL(1);
+    bool two_pass = two_pass_clip && !fr_fill;
+#else
+    const bool two_pass = AF(matrix_count) > 1 && !GFW_ABL(1) && !GFW_FR_FILL;
+    const bool two_pass_clip = two_pass;
+#endif
     const bool hrs = AF(hrs) != 0;
 
     // uniform floats of the pixel loops
     Lens L;
     L.f0 = AFA(f, 0); L.f1 = AFA(f, 1); L.c0 = AFA(c, 0); L.c1 = AFA(c, 1);
     L.k0 = AFA(k, 0); L.k1 = AFA(k, 1); L.k2 = AFA(k, 2); L.k3 = AFA(k, 3);
+#if GFW_JIT_PERFRAME
+    L.t2x = fr_pf[0].t2[0]; L.t2y = fr_pf[0].t2[1]; L.rl2 = AF(r_limit_sq);
+#else
     L.t2x = AFA(t2, 0); L.t2y = AFA(t2, 1); L.rl2 = AF(r_limit_sq);
+#endif
     Maps MP;
     MP.mul_lx = AFM(map_lx, mul); MP.mul_ly = AFM(map_ly, mul); MP.mul_cx = AFM(map_cx, mul); MP.mul_cy = AFM(map_cy, mul);
     MP.den_x = AFM(map_lx, den); MP.rcp_x = AFM(map_lx, rcp); MP.den_y = AFM(map_ly, den); MP.rcp_y = AFM(map_ly, rcp);
@@ -1411,7 +1449,7 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
     // matrix.  E >= 0.2 px, a NaN anywhere, or an r-limit test that the margin in pass1_fast cannot decide: no pixel of the frame is certified.
     // Thread j of the workgroup evaluates frame j of the launch ONCE, into LDS; a frame change reads two words.  (Evaluated by every wave at
     // every frame change — 35 wave-uniform vector instructions behind the matrix loads — it cost 1.05 us of C2's 46: profiles/r04_ab_certificate.txt.)
-    if (FAST1 && two_pass) {
+    if (FAST1 && two_pass_clip) {
         if (tid < n_frames) {
 #if GFW_BAKE
             const float *mid = (tid > 0 ? clip->fr[tid].matrices : matrices) + (size_t)(AF(matrix_count) >> 1) * GFW_MAT_STRIDE;   // (frame 0: the argument block's own table)
@@ -1421,7 +1459,12 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
             const float m0 = mid[0], m1 = mid[1], m3 = mid[3], m4 = mid[4], m6 = mid[6], m7 = mid[7], m8 = mid[8];
             bool lattice = LAT && !(L.rl2 > 0.0f) && A.p1_lat[5] == 0.0f;            // (p1_lat[5]: the per-pixel form on request — audits of that form, A/B runs)
             // (the lattice's nodes reach up to a tile beyond the frame's last pixel)
-            const float ax = fmaxf(fabsf(L.t2x), fabsf((float)(AF(out_w) + (lattice ? 64 * DW : 0)) + L.t2x)), ay = fmaxf(fabsf(L.t2y), fabsf((float)(AF(out_h) + (lattice ? 4 * RB * DH : 0)) + L.t2y));
+#if GFW_JIT_PERFRAME
+            const float t2x = fr_pf[tid].t2[0], t2y = fr_pf[tid].t2[1];              // (frame tid's own zoom centre)
+#else
+            const float t2x = L.t2x, t2y = L.t2y;
+#endif
+            const float ax = fmaxf(fabsf(t2x), fabsf((float)(AF(out_w) + (lattice ? 64 * DW : 0)) + t2x)), ay = fmaxf(fabsf(t2y), fabsf((float)(AF(out_h) + (lattice ? 4 * RB * DH : 0)) + t2y));
             const float px = ax * fabsf(m0) + ay * fabsf(m1), py = ax * fabsf(m3) + ay * fabsf(m4), pw = ax * fabsf(m6) + ay * fabsf(m7);
             const float wmin = fmaxf(0.0009765625f, 0.125f * (pw + fabsf(m8)));
             const float wden = fmaxf(m8 - pw, wmin);
@@ -1476,8 +1519,8 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
         Q.eps = gfw_uniform(q.x); Q.wmin = gfw_uniform(q.y); Q.rho_lim = gfw_uniform(q.z); Q.gap = 0.5f - Q.eps;
         p1_lattice = LAT && gfw_uniform(q.w) != 0.0f;
     };
-    if (two_pass) {
-        load_mid();
+    if (two_pass_clip) {
+        if (two_pass) load_mid();
         if (FAST1) {
             Q.rho_max = A.p1_rho_max; Q.rho_scale = A.p1_rho_scale; Q.kmax = A.p1_kmax;
             Q.f = AF(p1_f); Q.c = AF(p1_c); Q.lim = (float)(AF(hrs) ? AF(width) : AF(height));
@@ -1538,6 +1581,11 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
             PL0.src = clip->fr[fi].src[0]; PL0.dst = clip->fr[fi].dst[0]; PL1.src = clip->fr[fi].src[1]; PL1.dst = clip->fr[fi].dst[1];
             PL2.src = clip->fr[fi].src[2]; PL2.dst = clip->fr[fi].dst[2]; PL3.src = clip->fr[fi].src[3]; PL3.dst = clip->fr[fi].dst[3];
             matrices = clip->fr[fi].matrices;
+#if GFW_JIT_PERFRAME
+            L.t2x = fr_pf[fi].t2[0]; L.t2y = fr_pf[fi].t2[1];
+            fr_fill = fr_pf[fi].fill_bg != 0;
+            two_pass = two_pass_clip && !fr_fill;
+#endif
             if (two_pass) {
                 load_mid();
                 if (FAST1) p1_bound(fi);
@@ -1693,7 +1741,7 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
                     int sy = 0;
                     if (live) {
                         float ox = (float)lx + L.t2x, oy = (float)ly + L.t2y;
-                        if (MODEL != GFW_MODEL_OPENCV_FISHEYE && (AF(extras) & 8)) gfw_lens_correction_blend<(MODEL == GFW_MODEL_GENERIC_EXTRA ? -1 : MODEL)>(ox, oy, A.kp, A.common, AF(model), GFW_CLIP_DIGITAL);   // :429-460
+                        if (MODEL != GFW_MODEL_OPENCV_FISHEYE && (AF(extras) & 8)) gfw_lens_correction_blend<(MODEL == GFW_MODEL_GENERIC_EXTRA ? -1 : MODEL)>(ox, oy, A.kp, A.common, AF(model), GFW_CLIP_DIGITAL, GFW_FR_FOV, GFW_FR_AMOUNT);   // :429-460
                         sy = pass1_exact<MODEL>(ox, oy, M, matrices, L, A);
                     }
                     srow(r * NPX + k, tid) = (unsigned short)(live ? min(sy, AF(matrix_count) - 1) : 0);
@@ -1710,7 +1758,7 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
             for (int r = 0; r < RB; ++r) {
                 const int cy = cy0 + r;
                 if (!WHOLE && cy >= AF(ch)) break;
-                if (AF(fill_bg)) {
+                if (GFW_FR_FILL) {
                     // FILL_WITH_BACKGROUND (cpu_undistort.rs:558-561; the render loop sets it for frames outside the trim ranges): `*pix_out = bg_t` for every
                     // pixel of the plane — no projection, no taps
                     #pragma unroll
@@ -1749,7 +1797,7 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
                         {
                             float ox[DW], oy[DW], m8[DW]; float4 ma[DW], mb[DW];
                             uint32_t rows2 = 0u;                  // the pair's two rows, one dword (already clamped to the table)
-                            if constexpr (DW == 2) if (two_pass) rows2 = *reinterpret_cast<const uint32_t *>(&s_rows[r * DH + j][tid][0]);
+                            if constexpr (DW == 2) if (two_pass_clip) rows2 = *reinterpret_cast<const uint32_t *>(&s_rows[r * DH + j][tid][0]);
                             int row[DW];
                             #pragma unroll
                             for (int i = 0; i < DW; ++i) {
@@ -1757,7 +1805,7 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
                                 // (translation2d == +0 in a baked build: x + (+0) is x for every x >= +0, and (float)(lx + 1) is (float)lx + 1 below 2^24 — a conversion and three adds per pair)
                                 if (GFW_BAKE && gfw_f2u(L.t2x) == 0u) ox[i] = (i == 0) ? (float)lx : ox[0] + (float)i; else ox[i] = (float)lx + L.t2x;
                                 if (GFW_BAKE && gfw_f2u(L.t2y) == 0u) oy[i] = (i == 0) ? (float)ly : oy[0]; else oy[i] = (float)ly + L.t2y;
-                                row[i] = two_pass ? (DW == 2 ? (int)(i == 0 ? (rows2 & 0xffffu) : (rows2 >> 16)) : (int)s_rows[r * DH + j][tid][i])
+                                row[i] = two_pass_clip ? (DW == 2 ? (int)(i == 0 ? (rows2 & 0xffffu) : (rows2 >> 16)) : (int)s_rows[r * DH + j][tid][i])
                                                   : min(default_row<MODEL>(ox[i], oy[i], A), AF(matrix_count) - 1);
                             }
                             // (the rows of a lane-row through a 16-row LDS window — one cooperative dwordx4 instead of these six fetches — measured 42.3 = 42.3 us per C2
@@ -1791,7 +1839,7 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
                                 if (odd[i]) {
                                     const int lx = cx * DW + i;
                                     const float ox = (float)lx + L.t2x, oy = (float)ly + L.t2y;
-                                    const int row = two_pass ? (int)s_rows[r * DH + j][tid][i] : min(default_row<MODEL>(ox, oy, A), AF(matrix_count) - 1);
+                                    const int row = two_pass_clip ? (int)s_rows[r * DH + j][tid][i] : min(default_row<MODEL>(ox, oy, A), AF(matrix_count) - 1);
                                     const GfwPt p = rd_row<MODEL>(ox, oy, row, matrices, L, A);
                                     pu[i] = p.x; pv[i] = p.y; ok_i = p.ok;
                                 }
@@ -1899,8 +1947,8 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
                     const int lx = cx * DW + i, ly = cy * DH + j;
                     if (!WHOLE && (lx >= AF(out_w) || ly >= AF(out_h))) continue;
                     float ox = (float)lx + L.t2x, oy = (float)ly + L.t2y;
-                    if (MODEL != GFW_MODEL_OPENCV_FISHEYE && (AF(extras) & 8)) gfw_lens_correction_blend<(MODEL == GFW_MODEL_GENERIC_EXTRA ? -1 : MODEL)>(ox, oy, A.kp, A.common, AF(model), GFW_CLIP_DIGITAL);       // :429-460
-                    const int sy = two_pass ? (int)srow(r * NPX + k, tid) : default_row<MODEL>(ox, oy, A);      // (two_pass: already clamped to the table; the min below is then idle)
+                    if (MODEL != GFW_MODEL_OPENCV_FISHEYE && (AF(extras) & 8)) gfw_lens_correction_blend<(MODEL == GFW_MODEL_GENERIC_EXTRA ? -1 : MODEL)>(ox, oy, A.kp, A.common, AF(model), GFW_CLIP_DIGITAL, GFW_FR_FOV, GFW_FR_AMOUNT);       // :429-460
+                    const int sy = two_pass_clip ? (int)srow(r * NPX + k, tid) : default_row<MODEL>(ox, oy, A);      // (two_pass: already clamped to the table; the min below is then idle)
                     GfwPt p;
                     if (GFW_ABL(8)) { p.x = ox * 0.5f; p.y = oy * 0.5f; p.ok = true; }              // timing ablation only
                     else {
@@ -1931,7 +1979,7 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
                     }
                     if (k == 0) { u0 = p.x; v0 = p.y; ok0 = p.ok; }
                     if (MODEL == GFW_MODEL_GENERIC_EXTRA && (AF(extras) & 16) && p.ok) {          // background mode 3: two samples, blended (:576-613)
-                        feather_store<T, N0, I, true>(p.x, p.y, feather_of(p.x, p.y, A), PL0, bg_y, lim_y, MP.mul_lx, MP.mul_ly, MP, lx, ly, s_lut);
+                        feather_store<T, N0, I, true>(p.x, p.y, feather_of(p.x, p.y, A, GFW_FR_MARGIN, GFW_FR_FEATHER), PL0, bg_y, lim_y, MP.mul_lx, MP.mul_ly, MP, lx, ly, s_lut);
                         continue;
                     }
                     const float lu = map_c<INF_COORDS>(p.x, MP.mul_lx, MP.den_x, MP.rcp_x), lv = map_c<INF_COORDS>(p.y, MP.mul_ly, MP.den_y, MP.rcp_y);   // cpu_undistort.rs:511-514
@@ -1942,7 +1990,7 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
                 }
                 }
                 if (MODEL == GFW_MODEL_GENERIC_EXTRA && (AF(extras) & 16) && ok0 && AF(nplanes) > 1) {  // background mode 3 for the chroma site
-                    const Feather f = feather_of(u0, v0, A);
+                    const Feather f = feather_of(u0, v0, A, GFW_FR_MARGIN, GFW_FR_FEATHER);
                     if (INTERLEAVED_UV) feather_store<T, 2, I, true>(u0, v0, f, PL1, bg_c, lim_u, MP.mul_cx, MP.mul_cy, MP, cx, cy, s_lut);
                     else {
                         // the named planes, not A_in.pl[]: in a clip launch they carry the CURRENT frame's pointers (the argument block's own are frame 0's)
@@ -2073,12 +2121,19 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
 #if GFW_JIT
 }  // namespace
 // The one instantiation a run-time build contains: template arguments and the bake header come from gfw_jit.hip.
-extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GFW_JIT_WAVES, 8))) void gfw_jit_kernel(const GfwClipArgs C) {
 #ifndef GFW_JIT_AUDIT
 #define GFW_JIT_AUDIT 0          // 1: the audit instantiation (GFW_OPT_KERNEL_VARIANT 3 / 4 on a clip whose certified first pass exists only in specialised builds)
 #endif
+#if GFW_JIT_PERFRAME
+// the per-frame flavour: the launch's argument block carries a slot per frame (GfwClipArgsPF); the body indexes the slot array, never takes `&C` of a field it copies
+extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GFW_JIT_WAVES, 8))) void gfw_jit_kernel(const GfwClipArgsPF C) {
+    gfw_yuv_body<GFW_JIT_MODEL, GFW_JIT_T, GFW_JIT_N0, GFW_FRAME_TAPS, GFW_JIT_DW, GFW_JIT_DH, (GFW_JIT_IL != 0), GFW_JIT_RB, (GFW_JIT_FAST1 != 0), (GFW_JIT_AUDIT != 0)>(C.C.Y, &C.C, C.fr_pf);
+}
+#else
+extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GFW_JIT_WAVES, 8))) void gfw_jit_kernel(const GfwClipArgs C) {
     gfw_yuv_body<GFW_JIT_MODEL, GFW_JIT_T, GFW_JIT_N0, GFW_FRAME_TAPS, GFW_JIT_DW, GFW_JIT_DH, (GFW_JIT_IL != 0), GFW_JIT_RB, (GFW_JIT_FAST1 != 0), (GFW_JIT_AUDIT != 0)>(C.Y, &C);
 }
+#endif
 #else
 // Register budget: the specialised-fisheye instantiations are held to GFW_WAVES_PER_EU waves per SIMD; the generic-model ones (every
 // other lens, digital lenses, refraction, IBIS/OIS, lens-correction blend) to GFW_GENERIC_WAVES_PER_EU (tools/kernel_resources.py

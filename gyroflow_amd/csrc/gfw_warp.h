@@ -635,16 +635,18 @@ __device__ __forceinline__ GfwPt gfw_rotate_and_distort(float px, float py, int 
 // The lens-correction blend of undistort_coord (cpu_undistort.rs:429-460): the output position moves towards its
 // undistorted counterpart by (1 - lens_correction_amount) before any projection.
 // (lens, digital: the clip's lens model and digital lens — C.model / C.digital, or literals in a run-time specialised kernel)
+// (fov, amount: P.fov and P.lens_correction_amount — or, in the per-frame flavour of a clip launch, the current frame's own: gfw_frame.hip GFW_JIT_PERFRAME)
 template <int MODEL>
-__device__ __forceinline__ void gfw_lens_correction_blend(float &opx, float &opy, const gfw_kernel_params &P, const GfwCommon &C, const int lens, const int digital) {
-        const float factor = gfw_max(1.0f - P.lens_correction_amount, 0.001f);          // :526
+__device__ __forceinline__ void gfw_lens_correction_blend(float &opx, float &opy, const gfw_kernel_params &P, const GfwCommon &C, const int lens, const int digital,
+                                                          const float fov, const float amount) {
+        const float factor = gfw_max(1.0f - amount, 0.001f);          // :526
         const float ocx = (float)P.output_width / 2.0f, ocy = (float)P.output_height / 2.0f;
-        const float ofx = P.f[0] / P.fov / factor, ofy = P.f[1] / P.fov / factor;
+        const float ofx = P.f[0] / fov / factor, ofy = P.f[1] / fov / factor;
         float nx = opx, ny = opy;
         if ((P.flags & 2) == 2 && digital != GFW_MODEL_NONE) {
-            const float uzx = (nx - ocx) * P.fov + ocx, uzy = (ny - ocy) * P.fov + ocy;
+            const float uzx = (nx - ocx) * fov + ocx, uzy = (ny - ocy) * fov + ocy;
             const GfwPt pt = gfw_lens::undistort<-1>(digital, uzx, uzy, P, C);
-            if (pt.ok) { nx = (pt.x - ocx) / P.fov + ocx; ny = (pt.y - ocy) / P.fov + ocy; }
+            if (pt.ok) { nx = (pt.x - ocx) / fov + ocx; ny = (pt.y - ocy) / fov + ocy; }
         }
         nx = (nx - ocx) / ofx; ny = (ny - ocy) / ofy;
         const GfwPt pt = gfw_lens::undistort<MODEL>(lens, nx, ny, P, C);
@@ -659,8 +661,12 @@ __device__ __forceinline__ void gfw_lens_correction_blend(float &opx, float &opy
             }
         }
         nx = (nx * ofx) + ocx; ny = (ny * ofy) + ocy;
-        opx = nx * (1.0f - P.lens_correction_amount) + (opx * P.lens_correction_amount);
-        opy = ny * (1.0f - P.lens_correction_amount) + (opy * P.lens_correction_amount);
+        opx = nx * (1.0f - amount) + (opx * amount);
+        opy = ny * (1.0f - amount) + (opy * amount);
+}
+template <int MODEL>
+__device__ __forceinline__ void gfw_lens_correction_blend(float &opx, float &opy, const gfw_kernel_params &P, const GfwCommon &C, const int lens, const int digital) {
+    gfw_lens_correction_blend<MODEL>(opx, opy, P, C, lens, digital, P.fov, P.lens_correction_amount);
 }
 template <int MODEL>
 __device__ __forceinline__ void gfw_lens_correction_blend(float &opx, float &opy, const gfw_kernel_params &P, const GfwCommon &C) {

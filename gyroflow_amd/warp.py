@@ -350,6 +350,18 @@ class ClipCall:
             self.be._check(rc)
 
 
+class ClipParamsCall(ClipCall):
+    """Pre-marshalled ``gfw_undistort_clip_params`` call: as ``ClipCall``, but ``params`` is a list of per-frame plane lists (``KernelParams``) — frame f's
+    own blocks, as ``FrameTransform::at_timestamp`` fills them per frame (adaptive zoom, keyframes, the render loop's fill flag)."""
+
+    def __init__(self, backend, frames, params, pixel_types, matrices, matrix_count=None):
+        if len(params) != len(frames) or any(len(p) != len(fr) for p, fr in zip(params, frames)):
+            raise ValueError("params: one list of per-plane KernelParams per frame")
+        super().__init__(backend, frames, params[0], pixel_types, matrices, matrix_count)
+        self.parr = (abi.KernelParams * (self.nf * self.n))(*[p for fp in params for p in fp])
+        self.fn = backend.lib.gfw_undistort_clip_params
+
+
 def run_plane(src, in_size, dst, out_size, params, pixel_type, model, digital, matrices, mesh=None, **rects):
     """Convenience: create a backend, warp one HOST plane in place into ``dst``."""
     b = host_buffers(src, in_size, dst, out_size, **rects)

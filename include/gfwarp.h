@@ -264,6 +264,19 @@ int gfw_undistort_clip(gfw_ctx *ctx, int n_frames, int nplanes,
                        const gfw_kernel_params *params,
                        const int *pixel_types,
                        const float *const *matrices, int matrix_count);
+/* The same frame loop for a clip whose KernelParams change from frame to frame — FrameTransform::at_timestamp fills them per frame
+ * (frame_transform.rs: the adaptive-zoom fov and translation2d, keyframed lens_correction_amount, background_margin and
+ * background_margin_feather; the render loop sets GFW_FLAG_FILL_WITH_BACKGROUND per frame, rendering/mod.rs:538-540).
+ * `params` holds n_frames * nplanes entries, frame-major like `planes`: frame f's own block per plane; `pixel_types` (nplanes) is shared.
+ * Results are bit-identical to n_frames ordered gfw_undistort_frame calls, each given its own frame's params.  Ordering, overlap,
+ * synchronous-default, checksum-ring and error behaviour are those of gfw_undistort_clip.  Frames that differ only in fov,
+ * lens_correction_amount, translation2d, background_margin / _feather, the fill flag and their matrices share launches; a frame that
+ * changes anything else (lens, sizes, a lens-correction amount reaching 1.0, ...) starts a new launch. */
+int gfw_undistort_clip_params(gfw_ctx *ctx, int n_frames, int nplanes,
+                              const gfw_buffers *planes,
+                              const gfw_kernel_params *params,
+                              const int *pixel_types,
+                              const float *const *matrices, int matrix_count);
 
 /* ---- options / stream ---------------------------------------------------*/
 enum {
