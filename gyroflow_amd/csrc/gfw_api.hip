@@ -123,6 +123,7 @@ struct gfw_ctx {
     // clip, warp ahead-of-time meanwhile; 2 build at the first frame and wait for it
     int jit_mode = 1;
     bool dry = false;                              // gfw_debug_jit_key: argument blocks are built, nothing touches a device
+    unsigned long long dry_audit = 0;              // (a dry audit's counters: never written, only named by the key's header)
     std::string arch;                              // gcnArchName of the device
     std::string jit_header; int jit_seen = 0;      // bake header of the frames being seen, and how many in a row
     GfwYuvArgs jit_key; int jit_key_misc[9] = {}; bool jit_key_valid = false;      // the clip those frames belong to (argument block, per-frame fields blanked)

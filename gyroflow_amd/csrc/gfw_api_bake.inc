@@ -109,6 +109,24 @@ static std::vector<std::string> jit_defs(const GfwYuvArgs &Y, int bps, int taps,
 static int jit_model_of(const GfwYuvArgs &Y) {
     return (Y.model == GFW_MODEL_OPENCV_FISHEYE && (Y.extras & ~2) == 0) ? GFW_MODEL_OPENCV_FISHEYE : ((Y.extras & (16 | 32)) ? -2 : -1);
 }
+// Whether an audit (GFW_OPT_KERNEL_VARIANT 3 / 4) takes a specialised audit build (GFW_JIT_AUDIT=1) rather than the ahead-of-time audit instantiations: where the
+// first pass to be audited lives in specialised builds only — a table over r (the radial models), and every launch of the per-frame flavour, whose certificate
+// half-width is each frame's own (its translation2d) and whose kernel no ahead-of-time instantiation is
+static bool jit_audit_build(const gfw_ctx *c, const GfwYuvArgs &Y, bool perframe) {
+    return Y.audit && (Y.p1_rform || perframe) && (c->kernel_variant == 3 || c->kernel_variant == 4);
+}
+// The definition list jit_for builds these arguments with (also behind gfw_debug_jit_key / gfw_debug_jit_key_clip_params); `waves` receives the budget
+static std::vector<std::string> jit_build_defs(const GfwYuvArgs &Y, int bps, int taps, int n0, int dw, int dh, bool interleaved, bool fast1, bool perframe, bool audit_build, int *waves_out) {
+    const int jit_model = jit_model_of(Y);
+    int waves = jit_waves(n0, Y.matrix_count, jit_model, Y.extras, taps, bps, dh, Y.checksum);
+    // (the per-frame flavour of the lens-correction body keeps one more value of the frame alive through the pixel loop: at eight waves 24 bytes went to scratch
+    // on 4K NV12, so it gets seven — as the checksum build does; every other body keeps its constant build's waves: tests/test_kernel_resources_perframe.py)
+    if (perframe && (Y.extras & 8) && waves == 8) waves = 7;
+    std::vector<std::string> defs = jit_defs(Y, bps, taps, n0, dw, dh, interleaved, fast1, jit_model, waves, perframe);
+    if (audit_build) defs.push_back("GFW_JIT_AUDIT=1");
+    if (waves_out) *waves_out = waves;
+    return defs;
+}
 // The specialised kernel for this frame's arguments, or nullptr (not eligible / not wanted / not ready / failed): the caller then
 // launches the ahead-of-time kernel.  perframe: the per-frame flavour (gfw_undistort_clip_params): its launches take GfwClipArgsPF (gfw_jit_launch_pf), and its
 // key blanks the fields the frames carry in their slots as well — translation2d and the fill flag here, fov / lens-correction amount / margin / feather with `kp` —
@@ -117,10 +135,9 @@ static hipFunction_t jit_for(gfw_ctx *c, const GfwYuvArgs &Y, int bps, int taps,
     // every frame the fused kernel serves can be specialised: the fisheye model alone or under a digital lens (extras 0 / 2) takes the lean
     // projection (MODEL = 1); everything else the generic-model body with the lens model, the digital lens and the feature bits as literals
     // (MODEL = -1, or -2 with background mode 3 / the Sony mesh) — the run-time switch over 14 lens models folds to the one in use
-    // (kernel variants and the audit take the ahead-of-time instantiations — except the audit of a table over r: that first pass exists in specialised builds only)
-    const bool audit_build = Y.audit && Y.p1_rform && (c->kernel_variant == 3 || c->kernel_variant == 4);
+    // (kernel variants and the audit take the ahead-of-time instantiations — except the audit of a table over r and of a per-frame launch: jit_audit_build)
+    const bool audit_build = jit_audit_build(c, Y, perframe);
     if (c->jit_mode == 0 || ((c->kernel_variant != 0 || Y.audit) && !audit_build) || Y.ablate) return nullptr;
-    const int jit_model = jit_model_of(Y);
     // the same clip as the previous frame?  Compared on the argument block itself with its per-frame fields blanked (the header text and the
     // cache lookup cost ~15 us of host time, a frame's worth of validation): header, key and function are rebuilt only when it changes
     GfwYuvArgs K = Y;
@@ -142,12 +159,8 @@ static hipFunction_t jit_for(gfw_ctx *c, const GfwYuvArgs &Y, int bps, int taps,
         c->jit_info = GfwJitInfo{GFW_JIT_UNAVAILABLE, 0.0, std::string()};
     }
     if (c->jit_mode == 1 && c->jit_seen < gfw_ctx::kJitAfter && !audit_build) return nullptr;          // one or two frames are not a clip
-    int waves = jit_waves(n0, Y.matrix_count, jit_model, Y.extras, taps, bps, dh, Y.checksum);
-    // (the per-frame flavour of the lens-correction body keeps one more value of the frame alive through the pixel loop: at eight waves 24 bytes went to scratch
-    // on 4K NV12, so it gets seven — as the checksum build does; every other body keeps its constant build's waves: tests/test_kernel_resources_perframe.py)
-    if (perframe && (Y.extras & 8) && waves == 8) waves = 7;
-    std::vector<std::string> defs = jit_defs(Y, bps, taps, n0, dw, dh, interleaved, fast1, jit_model, waves, perframe);
-    if (audit_build) defs.push_back("GFW_JIT_AUDIT=1");
+    int waves = 0;
+    const std::vector<std::string> defs = jit_build_defs(Y, bps, taps, n0, dw, dh, interleaved, fast1, perframe, audit_build, &waves);
     hipFunction_t fn = gfw_jit_get(c->device, c->arch, defs, c->jit_header, c->jit_mode == 2 || audit_build, &c->jit_info);
     if (!fn) { c->jit_dead = c->jit_info.state == GFW_JIT_FAILED || c->jit_info.state == GFW_JIT_UNAVAILABLE; return nullptr; }
     int g = c->tune_grid > 0 ? c->tune_grid : c->num_cus * waves;

@@ -350,7 +350,8 @@ static bool p1_setup_radial(gfw_ctx *c, const gfw_kernel_params &p0, const float
     c->p1_eps_last = (float)eps;
     Y.p1_f = hrs ? p0.f[0] : p0.f[1]; Y.p1_c = hrs ? p0.c[0] : p0.c[1];
     table_ok = true;
-    if (c->kernel_variant == 3 || c->kernel_variant == 4) {     // audit mode: count certificates and check each one (a specialised audit build: gfw_api_bake.inc)
+    if ((c->kernel_variant == 3 || c->kernel_variant == 4) && c->dry) Y.audit = &c->dry_audit;      // (gfw_debug_jit_key_clip_params: the key of the audit build, no device)
+    else if (c->kernel_variant == 3 || c->kernel_variant == 4) {     // audit mode: count certificates and check each one (a specialised audit build: gfw_api_bake.inc)
         const bool fresh = c->d_audit.cap == 0;
         if (c->d_audit.ensure(8 * sizeof(unsigned long long)) != hipSuccess) { table_ok = false; return false; }
         if (fresh) (void)hipMemsetAsync(c->d_audit.ptr, 0, 8 * sizeof(unsigned long long), c->stream);
@@ -444,7 +445,8 @@ static bool p1_setup(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_mat
         static const bool env_off = [] { const char *e = getenv("GFW_P1_LATTICE"); return e && e[0] == '0' && e[1] == 0; }();
         if (c->kernel_variant == 4 || env_off) Y.p1_lat[5] = 1.0f;
     }
-    if (c->kernel_variant == 3 || c->kernel_variant == 4) {     // audit mode: count certificates and check each one
+    if ((c->kernel_variant == 3 || c->kernel_variant == 4) && c->dry) Y.audit = &c->dry_audit;      // (gfw_debug_jit_key_clip_params: the key of the audit build, no device)
+    else if (c->kernel_variant == 3 || c->kernel_variant == 4) {     // audit mode: count certificates and check each one
         const bool fresh = c->d_audit.cap == 0;
         if (c->d_audit.ensure(8 * sizeof(unsigned long long)) != hipSuccess) { table_ok = false; return false; }
         if (fresh) (void)hipMemsetAsync(c->d_audit.ptr, 0, 8 * sizeof(unsigned long long), c->stream);

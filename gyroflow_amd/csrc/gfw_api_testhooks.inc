@@ -72,6 +72,17 @@ extern "C" int gfw_debug_source_id(char *out, size_t cap) {
     return (int)id.size();
 }
 
+static int jit_key_out(const char *arch, const std::vector<std::string> &defs, const std::string &header, char *defs_out, size_t defs_cap, char *header_out, size_t header_cap,
+                       char *name_out, size_t name_cap) {
+    std::string d;
+    for (const std::string &x : defs) { if (!d.empty()) d += ";"; d += x; }
+    const std::string name = gfw_jit_cache_name(arch, defs, header);
+    if (!defs_out || !header_out || !name_out || d.size() + 1 > defs_cap || header.size() + 1 > header_cap || name.size() + 1 > name_cap) {
+        set_error("output buffers too small"); return GFW_ERR_BUFFER_SIZE_MISMATCH; }
+    memcpy(defs_out, d.c_str(), d.size() + 1); memcpy(header_out, header.c_str(), header.size() + 1); memcpy(name_out, name.c_str(), name.size() + 1);
+    return GFW_OK;
+}
+
 // Build-time helper of the shipped kernel cache (tools/build_jit_cache.py; no device involved): what the library WOULD specialise a frame of these planes to —
 // the ';'-separated definition list, the bake header and the cache file name of the kernel (gfw_jit.hip) — exactly as run_planes / jit_for derive them on a
 // device, with `matrices_on_device` as the context option would be set (2: device-resident tables, the first pass's table range from the intrinsics).
@@ -94,14 +105,46 @@ extern "C" int gfw_debug_jit_key(int nplanes, const gfw_buffers *planes, const g
     if (!build_yuv_args(&c, nplanes, planes, params, pixel_types, launches, matrices_on_device ? nullptr : h_matrices, matrix_count, 0, Y, bps, n0, dw, dh, interleaved, fast1, nullptr, err)) {
         set_error("not a frame the fused kernel serves"); return GFW_ERR_UNSUPPORTED_BUFFER; }
     fill_common(&c, &params[0], nullptr, nullptr, 0, Y.common);
-    const int jit_model = jit_model_of(Y);
-    const std::vector<std::string> defs = jit_defs(Y, bps, params[0].interpolation, n0, dw, dh, interleaved, fast1, jit_model, jit_waves(n0, Y.matrix_count, jit_model, Y.extras, params[0].interpolation, bps, dh));
-    std::string d;
-    for (const std::string &x : defs) { if (!d.empty()) d += ";"; d += x; }
-    const std::string header = bake_header(Y, fast1), name = gfw_jit_cache_name(arch, defs, header);
-    if (d.size() + 1 > defs_cap || header.size() + 1 > header_cap || name.size() + 1 > name_cap) { set_error("output buffers too small"); return GFW_ERR_BUFFER_SIZE_MISMATCH; }
-    memcpy(defs_out, d.c_str(), d.size() + 1); memcpy(header_out, header.c_str(), header.size() + 1); memcpy(name_out, name.c_str(), name.size() + 1);
-    return GFW_OK;
+    const std::vector<std::string> defs = jit_build_defs(Y, bps, params[0].interpolation, n0, dw, dh, interleaved, fast1, false, false, nullptr);
+    return jit_key_out(arch, defs, bake_header(Y, fast1), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
+}
+
+// The same for the first launch of a gfw_undistort_clip_params call (the per-frame flavour): `planes` / `params` hold n_frames x nplanes entries as that call takes
+// them, so that the first pass's table is sized for the call's own envelope of fov and zoom centre; `host_matrices[f]` is frame f's rows[14] table (only frame 0's
+// is read, and only with matrices_on_device = 0).  `audit`: the key under GFW_OPT_KERNEL_VARIANT 3 (the audit build).  Returns 1 (outputs untouched) when that launch
+// would not be a specialised build at all (an audit of a frame without a certified first pass takes the ahead-of-time audit instantiations).
+extern "C" int gfw_debug_jit_key_clip_params(int n_frames, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params, const int *pixel_types, int distortion_model,
+                                             int digital_lens, const float *const *host_matrices, int matrix_count, int matrices_on_device, int audit, const char *arch,
+                                             char *defs_out, size_t defs_cap, char *header_out, size_t header_cap, char *name_out, size_t name_cap) {
+    if (!planes || !params || !pixel_types || !arch || n_frames < 1 || nplanes < 1 || nplanes > 4 || (!matrices_on_device && (!host_matrices || !host_matrices[0]))) {
+        set_error("bad arguments"); return GFW_ERR_INVALID_ARGUMENT; }
+    for (int f = 0; f < n_frames; ++f)
+        for (int i = 0; i < nplanes; ++i) {
+            if (pixel_types[i] < 0 || pixel_types[i] >= GFW_PIX_COUNT) { set_error("plane %d: unknown pixel type", i); return GFW_ERR_INVALID_ARGUMENT; }
+            const int rc = validate_plane(&planes[(size_t)f * nplanes + i], &params[(size_t)f * nplanes + i], pixel_types[i]);
+            if (rc != GFW_OK) return rc;
+        }
+    gfw_ctx c;
+    c.dry = true; c.model = distortion_model; c.digital = digital_lens; c.matrices_on_device = matrices_on_device; c.arch = arch; c.kernel_variant = audit ? 3 : 0;
+    ClipBatch batch;                                               // (as gfw_undistort_clip_params sets it up: the envelope of every frame of the call)
+    batch.n_call = n_frames; batch.perframe = true;
+    for (int f = 0; f < n_frames; ++f) {
+        double hx, hy;
+        p1_corner_extent(params[(size_t)f * nplanes], hx, hy);
+        batch.env_hx = fmax(batch.env_hx, hx); batch.env_hy = fmax(batch.env_hy, hy);
+    }
+    GfwPlane launches[4];
+    memset(launches, 0, sizeof(launches));
+    for (int i = 0; i < nplanes; ++i) { launches[i].src = (const uint8_t *)planes[i].input.data; launches[i].dst = (uint8_t *)planes[i].output.data; }
+    GfwYuvArgs Y;
+    int bps = 0, n0 = 1, dw = 1, dh = 1, err = GFW_OK; bool interleaved = false, fast1 = false;
+    if (!build_yuv_args(&c, nplanes, planes, params, pixel_types, launches, matrices_on_device ? nullptr : host_matrices[0], matrix_count, 0, Y, bps, n0, dw, dh, interleaved, fast1,
+                        &batch, err)) { set_error("not a frame the fused kernel serves"); return GFW_ERR_UNSUPPORTED_BUFFER; }
+    fill_common(&c, &params[0], nullptr, nullptr, 0, Y.common);
+    const bool audit_build = jit_audit_build(&c, Y, true);
+    if ((c.kernel_variant != 0 || Y.audit) && !audit_build) return 1;             // (jit_for: the ahead-of-time kernel)
+    const std::vector<std::string> defs = jit_build_defs(Y, bps, params[0].interpolation, n0, dw, dh, interleaved, fast1, true, audit_build, nullptr);
+    return jit_key_out(arch, defs, bake_header(Y, fast1, true), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
 }
 
 extern "C" int gfw_checksum64(gfw_ctx *c, const void *d_buf, size_t bytes, unsigned long long *d_out) {

@@ -1458,21 +1458,31 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
 #endif
             const float m0 = mid[0], m1 = mid[1], m3 = mid[3], m4 = mid[4], m6 = mid[6], m7 = mid[7], m8 = mid[8];
             bool lattice = LAT && !(L.rl2 > 0.0f) && A.p1_lat[5] == 0.0f;            // (p1_lat[5]: the per-pixel form on request — audits of that form, A/B runs)
-            // (the lattice's nodes reach up to a tile beyond the frame's last pixel)
 #if GFW_JIT_PERFRAME
             const float t2x = fr_pf[tid].t2[0], t2y = fr_pf[tid].t2[1];              // (frame tid's own zoom centre)
 #else
             const float t2x = L.t2x, t2y = L.t2y;
 #endif
-            const float ax = fmaxf(fabsf(t2x), fabsf((float)(AF(out_w) + (lattice ? 64 * DW : 0)) + t2x)), ay = fmaxf(fabsf(t2y), fabsf((float)(AF(out_h) + (lattice ? 4 * RB * DH : 0)) + t2y));
-            const float px = ax * fabsf(m0) + ay * fabsf(m1), py = ax * fabsf(m3) + ay * fabsf(m4), pw = ax * fabsf(m6) + ay * fabsf(m7);
-            const float wmin = fmaxf(0.0009765625f, 0.125f * (pw + fabsf(m8)));
-            const float wden = fmaxf(m8 - pw, wmin);
-            const float rden = gfw_hw_rcp(wden) * 3.003f;                            // (3x; 1 ulp reciprocal and the roundings of the sums above: inside the 0.1 %)
-            const float omega = pw * rden, mu = fmaxf(px, py) * rden;
-            float E = __builtin_fmaf(A.p1_em, mu, __builtin_fmaf(A.p1_ew, omega, A.p1_eps));
+            // E over the points the frame's first pass evaluates: its pixels (the per-pixel form) or the lattice's nodes, which reach up to a tile beyond the frame's
+            // last pixel (ex, ey).  A frame whose lattice is rejected keeps the per-pixel form with the half-width over its PIXELS: taken over the nodes' extent
+            // it could reach 0.2 px where the pixels' does not, and the frame would lose its certified pass for no reason (tests/test_gpu_clip_params_cover.py).
+            struct P1Extent { float ax, ay, pw, wmin, wden, omega, mu, E; };
+            auto extent = [&](int ex, int ey) {
+                P1Extent r;
+                r.ax = fmaxf(fabsf(t2x), fabsf((float)(AF(out_w) + ex) + t2x)); r.ay = fmaxf(fabsf(t2y), fabsf((float)(AF(out_h) + ey) + t2y));
+                const float px = r.ax * fabsf(m0) + r.ay * fabsf(m1), py = r.ax * fabsf(m3) + r.ay * fabsf(m4);
+                r.pw = r.ax * fabsf(m6) + r.ay * fabsf(m7);
+                r.wmin = fmaxf(0.0009765625f, 0.125f * (r.pw + fabsf(m8)));
+                r.wden = fmaxf(m8 - r.pw, r.wmin);
+                const float rden = gfw_hw_rcp(r.wden) * 3.003f;                      // (3x; 1 ulp reciprocal and the roundings of the sums above: inside the 0.1 %)
+                r.omega = r.pw * rden; r.mu = fmaxf(px, py) * rden;
+                r.E = __builtin_fmaf(A.p1_em, r.mu, __builtin_fmaf(A.p1_ew, r.omega, A.p1_eps));
+                return r;
+            };
+            const P1Extent own = extent(0, 0);                     // the per-pixel form's half-width (its nodes ARE the pixels)
+            P1Extent ext = lattice ? extent(64 * DW, 4 * RB * DH) : own;
+            float E = ext.E;
             float rho_lim = A.p1_rho_max;
-            const float E_pixel = E;                           // the per-pixel form's half-width (its nodes ARE the pixels)
             if (lattice) {
                 // The interpolation's own error: bilinear interpolation of v over a cell of HX x HYR pixels misses it by at most HX^2/8 max|v_xx| + HYR^2/8 max|v_yy|.
                 // v = f c S(rho) + c0 with c = b (a for a horizontal shutter), (a, b) = (X, Y) / W, rho = a^2 + b^2.  Where W >= wden and rho <= rho_max:
@@ -1483,7 +1493,7 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
                 // with the host's bounds S0 >= |S|, U1 >= sqrt(rho) |S'|, U2 >= rho |S'|, T32 >= rho^1.5 |S''| over the table's range (gfw_api.hip p1_prepare_table) —
                 // the products are bounded together because S'' falls as rho grows: their separate maxima overstate the curvature twentyfold.  The same with m1, m4, m7 for y.
                 // The node coordinates' own rounding (ox = fl(lx + t2x)) moves v by u |ox| |v_x|: the last term.  1 % on top for this evaluation's own f32 roundings.
-                const float rw = gfw_hw_rcp(wden) * 1.001f, rmax = __builtin_sqrtf(A.p1_rho_max) * 1.0001f;
+                const float rw = gfw_hw_rcp(ext.wden) * 1.001f, rmax = __builtin_sqrtf(A.p1_rho_max) * 1.0001f;
                 const float S0 = A.p1_lat[0], U1 = A.p1_lat[1], U2 = A.p1_lat[2], T32 = A.p1_lat[3];
                 const float a1x = (fabsf(m0) + rmax * fabsf(m6)) * rw, b1x = (fabsf(m3) + rmax * fabsf(m6)) * rw;
                 const float a1y = (fabsf(m1) + rmax * fabsf(m7)) * rw, b1y = (fabsf(m4) + rmax * fabsf(m7)) * rw;
@@ -1495,21 +1505,26 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
                 const float gyy = k7 * c1y * S0 + 4.0f * c1y * n1y * U1 + n1y * n1y * (4.0f * T32 + 2.0f * U1) + 2.0f * n2y * U2;
                 const float gx = c1x * S0 + 2.0f * U2 * n1x, gy = c1y * S0 + 2.0f * U2 * n1y;                    // |(c S)_x|, |(c S)_y|
                 const float hx2 = 8.0f, hy2 = (float)(HYR * HYR) * 0.125f;                                       // HX^2 / 8 (HX = 8), HYR^2 / 8
-                E = E + 1.01f * fabsf(AF(p1_f)) * (hx2 * gxx + hy2 * gyy + 5.9604645e-8f * (ax * gx + ay * gy)) + A.p1_lat[4];
+                E = E + 1.01f * fabsf(AF(p1_f)) * (hx2 * gxx + hy2 * gyy + 5.9604645e-8f * (ext.ax * gx + ext.ay * gy)) + A.p1_lat[4];
                 rho_lim = A.p1_rho_max - 1.01f * 2.0f * rmax * (8.0f * n1x + (float)HYR * n1y);                  // |rho| moves by at most this much between a node and any point of its cells
                 // The curvature term scales with (8 / f)^2: a 4K frame adds a few thousandths of a pixel, a thumbnail whole pixels.  Beyond GFW_P1_LATTICE_MAX_E (every
                 // twelfth pixel undecided) — or a NaN — the frame keeps the per-pixel form and its own, smaller, half-width.
-                if (!(E <= GFW_P1_LATTICE_MAX_E) || !(rho_lim > 0.0f)) { lattice = false; E = E_pixel; rho_lim = A.p1_rho_max; }
+                if (!(E <= GFW_P1_LATTICE_MAX_E) || !(rho_lim > 0.0f)) { lattice = false; ext = own; E = own.E; rho_lim = A.p1_rho_max; }
             }
-            bool usable = (E < 0.2f) & (pw + m8 < 3.0e38f) & (rho_lim > 0.0f);        // (a NaN or an infinity among the operands fails a comparison)
+            bool usable = (E < 0.2f) & (ext.pw + m8 < 3.0e38f) & (rho_lim > 0.0f);    // (a NaN or an infinity among the operands fails a comparison)
             if (L.rl2 > 0.0f) {
                 // :139 in pass1_fast: lhs < 0.9999 rhs must imply the exact path's lhs <= rhs.  The two paths' X^2 + Y^2 differ by at most
                 // 1.05 u W^2 (2 sqrt2 rmax mu + 12.5 rho_max), their r_limit^2 W by r_limit^2 W u (omega + 8); W <= m8 + P_W; 1e-4 / u = 1677.7
                 const float rmax = __builtin_sqrtf(A.p1_rho_max);
-                usable = usable & (1.05f * (m8 + pw) * (2.83f * rmax * mu + 12.5f * A.p1_rho_max) + L.rl2 * (omega + 8.0f) <= 1677.0f * L.rl2);
+                usable = usable & (1.05f * (m8 + ext.pw) * (2.83f * rmax * ext.mu + 12.5f * A.p1_rho_max) + L.rl2 * (ext.omega + 8.0f) <= 1677.0f * L.rl2);
             }
-            s_p1[tid] = float4{E, usable ? wmin : __builtin_inff(), rho_lim, lattice ? 1.0f : 0.0f};  // W > inf never holds: every pixel of the frame goes to the exact path
-            if (AUDIT && usable) atomicMax(&AF(audit)[6], (unsigned long long)gfw_f2u(E));
+            s_p1[tid] = float4{E, usable ? ext.wmin : __builtin_inff(), rho_lim, lattice ? 1.0f : 0.0f};  // W > inf never holds: every pixel of the frame goes to the exact path
+#if GFW_JIT_PERFRAME
+            const bool takes_pass = fr_pf[tid].fill_bg == 0;                          // (a filled frame of the launch has no first pass: its E is no certificate's)
+#else
+            const bool takes_pass = true;
+#endif
+            if (AUDIT && usable && takes_pass) atomicMax(&AF(audit)[6], (unsigned long long)gfw_f2u(E));
         }
         __syncthreads();
     }

@@ -32,6 +32,13 @@ long  gfw_debug_jit_compile(const char *arch, const char *defines, const char *b
 int   gfw_debug_jit_key(int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params, const int *pixel_types, int distortion_model, int digital_lens,
                         const float *host_matrices, int matrix_count, int matrices_on_device, const char *arch,
                         char *defs_out, size_t defs_cap, char *header_out, size_t header_cap, char *name_out, size_t name_cap);
+/* The same for the first launch of a gfw_undistort_clip_params call (the per-frame flavour of the specialised kernel): planes / params hold n_frames x nplanes
+ * entries as that call takes them (the first pass's table covers the envelope of every frame's fov and zoom centre), host_matrices[f] frame f's rows[14] table
+ * (read with matrices_on_device = 0 only).  audit != 0: the key under GFW_OPT_KERNEL_VARIANT 3 (the audit build).  Returns 1, outputs untouched, when that launch
+ * would take an ahead-of-time kernel instead (an audit of a frame without a certified first pass). */
+int   gfw_debug_jit_key_clip_params(int n_frames, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params, const int *pixel_types, int distortion_model,
+                                    int digital_lens, const float *const *host_matrices, int matrix_count, int matrices_on_device, int audit, const char *arch,
+                                    char *defs_out, size_t defs_cap, char *header_out, size_t header_cap, char *name_out, size_t name_cap);
 
 /* Identity of the fused kernel's source this library was built from (length and 128-bit hash of the text it embeds for run-time specialisation; the ahead-of-time
  * kernels are compiled from the same files): measurements stored beside the repository (profiles/ *_traffic.json) name the source they were taken on, and bench.py

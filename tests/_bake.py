@@ -53,6 +53,9 @@ def bake_header(frame, rb=4, checksum=0):
     cpl = pls[1] if n >= 2 else pls[0]
     fw, fh = rotated_frame_size(p0)
     for name, mul, den in (("map_lx", pls[0]["size"][0], fw), ("map_ly", pls[0]["size"][1], fh), ("map_cx", cpl["size"][0], fw), ("map_cy", cpl["size"][1], fh)):
+        if n < 2 and name.startswith("map_c"):
+            fl[name + "_mul"] = fl[name + "_den"] = fl[name + "_rcp"] = 0.0           # (build_yuv_args: a single plane has no chroma maps — the kernel never reads them)
+            continue
         fl[name + "_mul"], fl[name + "_den"], fl[name + "_rcp"] = float(mul), float(den), float(one / np.float32(den))
     for i in range(4):
         if i < n:

@@ -135,19 +135,21 @@ def s_derivs(rho, k):
     return A * P, A1 * P + A * P1 * w1, A2 * P + 2.0 * A1 * P1 * w1 + A * (P2 * w1 * w1 + P1 * w2)
 
 
-def p1_table(p0, matrices, matrix_count):
+def p1_table(p0, matrices, matrix_count, rho_max=None):
     """gfw_api.hip p1_setup / p1_prepare_table restated: the s(rho) table of the certified first pass (f64 -> float2 entries), its range and
-    the certificate's coefficients.  -> (table [N+1][2] f32, rho_max, rho_scale, (e0, ew, em, host's E)) or None when the certified pass is not used."""
+    the certificate's coefficients.  -> (table [N+1][2] f32, rho_max, rho_scale, (e0, ew, em, host's E)) or None when the certified pass is not used.
+    `rho_max`: the table's range as given (device_rho: device-resident tables) instead of the host's from the matrices."""
     k = [float(p0.k[i]) for i in range(4)]
     hrs = bool(p0.flags & abi.FLAG_HORIZONTAL_RS)
     m = np.asarray(matrices, dtype=np.float64)[matrix_count >> 1]
-    rho_max = 0.0
-    for y in (0.0, p0.output_height * 0.5, float(p0.output_height)):
-        for x in (0.0, p0.output_width * 0.5, float(p0.output_width)):
-            ox, oy = x + p0.translation2d[0], y + p0.translation2d[1]
-            X, Y, Wd = ox * m[0] + oy * m[1] + m[2], ox * m[3] + oy * m[4] + m[5], ox * m[6] + oy * m[7] + m[8]
-            rho_max = 1e9 if not Wd > 0.05 else max(rho_max, (X * X + Y * Y) / (Wd * Wd))
-    rho_max = min(min(rho_max * 1.25 + 0.01, 64.0) * 1.15, 64.0)
+    if rho_max is None:
+        rho_max = 0.0
+        for y in (0.0, p0.output_height * 0.5, float(p0.output_height)):
+            for x in (0.0, p0.output_width * 0.5, float(p0.output_width)):
+                ox, oy = x + p0.translation2d[0], y + p0.translation2d[1]
+                X, Y, Wd = ox * m[0] + oy * m[1] + m[2], ox * m[3] + oy * m[4] + m[5], ox * m[6] + oy * m[7] + m[8]
+                rho_max = 1e9 if not Wd > 0.05 else max(rho_max, (X * X + Y * Y) / (Wd * Wd))
+        rho_max = min(min(rho_max * 1.25 + 0.01, 64.0) * 1.15, 64.0)
     rho_max = float(np.float32(rho_max))
 
     def s_of(rho):

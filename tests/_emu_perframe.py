@@ -23,7 +23,9 @@ def slot_of(fr):
 
 
 def _envelope_table(frames):
-    """The first pass's table sized for every frame of the launch (the library's envelope, gfw_undistort_clip_params): the frames' own tables, the widest one"""
+    """The first pass's table sized for the frames of the launch (the library's envelope, gfw_undistort_clip_params): the widest of the frames' own tables.  The
+    launch has a certified pass when frame 0 has one (the library decides on the frame that opens the launch); a later frame whose own table the host would decline
+    still runs under it — its certificate is its own, evaluated by the kernel from its own matrix and zoom centre."""
     fr0 = frames[0]
     p0 = fr0.planes[0]["params"]
     fisheye = fr0.model == abi.MODELS["opencv_fisheye"]
@@ -39,14 +41,50 @@ def _envelope_table(frames):
         else:
             t = None
         if t is None:
-            return None, rform
+            if fr is fr0:
+                return None, rform
+            continue
         if best is None or float(t[1]) > float(best[1]):
             best = t
     return best, rform
 
 
-def run_frames_pf(frames, grid=8):
-    """One launch of the per-frame flavour over `frames` (one shape, one lens and the same clip constants; <= 16) -> [[plane outputs] per frame]."""
+ARCH = b"gfx950:sramecc+:xnack-"       # (build_jit_cache.ARCH: part of the cache name only)
+
+
+def library_key(frames, audit=False, matrices_on_device=0, raw=False):
+    """gfw_debug_jit_key_clip_params: the definition list (dict) and bake header (text) of the kernel the library builds for the first launch of a
+    gfw_undistort_clip_params call over `frames` (host tables: frame 0's own; 2: device-resident tables, the call's envelope), or None where that launch would take
+    an ahead-of-time kernel.  raw=True: (definition list, header) as the library writes them, bytes."""
+    lib = abi.load_library()
+    n, npl = len(frames), len(frames[0].planes)
+    bufs, params, mats = [], [], []
+    for f, fr in enumerate(frames):                   # any non-null device pointers: the key holds no pointer
+        for p, pl in enumerate(fr.planes):
+            bufs.append(warp.device_buffers(0x100000 * (p + 1), pl["size"][2] * pl["size"][1], pl["size"], 0x90000000 + 0x100000 * p, pl["out_size"][2] * pl["out_size"][1], pl["out_size"]))
+            params.append(pl["params"])
+        mats.append(np.ascontiguousarray(fr.matrices, dtype=np.float32))
+    barr, parr = (abi.Buffers * len(bufs))(*bufs), (abi.KernelParams * len(params))(*params)
+    tarr = (C.c_int * npl)(*[abi.PIXEL_TYPES[pl["pixel_type"]][0] for pl in frames[0].planes])
+    marr = (C.c_void_p * n)(*[m.ctypes.data for m in mats])
+    defs, header, name = C.create_string_buffer(4096), C.create_string_buffer(1 << 16), C.create_string_buffer(128)
+    rc = lib.gfw_debug_jit_key_clip_params(n, npl, barr, parr, tarr, frames[0].model, frames[0].digital, marr, frames[0].matrices.shape[0], matrices_on_device,
+                                           1 if audit else 0, ARCH, defs, len(defs), header, len(header), name, len(name))
+    if rc == 1:
+        return None
+    assert rc == 0, (rc, lib.gfw_last_error())
+    if raw:
+        return defs.value, header.value
+    return dict(d.split("=", 1) for d in defs.value.decode().split(";")), header.value.decode()
+
+
+def run_frames_pf(frames, grid=8, audit=False, table=None):
+    """One launch of the per-frame flavour over `frames` (one shape, one lens and the same clip constants; <= 16) -> [[plane outputs] per frame].
+    The kernel built is the library's own: its definition list and bake header come from gfw_debug_jit_key_clip_params, and must equal this file's restatement
+    of them (the restatement is what the interpreter's arguments are derived from).
+    `audit`: the audit build (GFW_JIT_AUDIT=1, what GFW_OPT_KERNEL_VARIANT 3 / 4 launches) -> (outputs, dict of the audit words as _emu.run_frames(audit=True)
+    returns them; eps_px is word 6, the largest certificate half-width E of the launch's frames).
+    `table`: the first pass's table and range constants to launch with (a p1 tuple of _emu.p1_table) instead of the frames' envelope."""
     fr0 = frames[0]
     p0 = fr0.planes[0]["params"]
     assert E.fused_eligible(fr0), "not a frame the fused kernel serves"
@@ -57,31 +95,55 @@ def run_frames_pf(frames, grid=8):
     lean = fisheye and (extras & ~2) == 0
     jit_model = 1 if lean else (-2 if extras & (16 | 32) else -1)
     p1, rform = _envelope_table(frames)
+    if table is not None:
+        assert p1 is not None, "a table for a launch without a certified first pass"
+        p1 = table
     fast1 = p1 is not None
     rb = 4 if fast1 else 1
-    defs = {"GFW_FRAME_KIND": bps, "GFW_FRAME_TAPS": p0.interpolation, "GFW_JIT_WAVES": E.jit_waves(n0, p0.matrix_count, jit_model, extras, p0.interpolation, bps, dh),
+    waves = E.jit_waves(n0, p0.matrix_count, jit_model, extras, p0.interpolation, bps, dh)
+    if extras & 8 and waves == 8:
+        waves = 7                                     # (jit_build_defs: the flavour's lens-correction body at seven)
+    defs = {"GFW_FRAME_KIND": bps, "GFW_FRAME_TAPS": p0.interpolation, "GFW_JIT_WAVES": waves,
             "GFW_JIT_MODEL": jit_model, "GFW_JIT_T": {1: "uint8_t", 2: "uint16_t", 3: "_Float16", 4: "float"}[bps], "GFW_JIT_N0": n0, "GFW_JIT_DW": dw, "GFW_JIT_DH": dh,
             "GFW_JIT_IL": 1 if il else 0, "GFW_JIT_RB": rb, "GFW_JIT_FAST1": 1 if fast1 else 0, "GFW_JIT_PERFRAME": 1}
-    if rform and fast1:
-        defs["GFW_P1_RFORM"] = 1
+    if audit:
+        defs["GFW_JIT_AUDIT"] = 1
     header = _bake.bake_header(fr0, rb=rb)
     header, n1 = re.subn(r"#define GFW_BK_extras \(0\)", "#define GFW_BK_extras (%d)" % extras, header)
     header, n2 = re.subn(r"#define GFW_BK_digital \(0\)", "#define GFW_BK_digital (%d)" % (fr0.digital if extras & 2 else 0), header)
     # the per-frame flavour's header names neither translation2d nor the fill flag (gfw_api_bake.inc bake_header, perframe)
     header, n3 = re.subn(r"#define GFW_BK_(t2_[01]|fill_bg) [^\n]*\n", "", header)
     assert n1 == 1 and n2 == 1 and n3 == 3
+    if audit:
+        header = header.replace("#define GFW_BK_audit ((unsigned long long *)nullptr)", "#define GFW_BK_audit (A.audit)")
+    stretched = any(st > 0.001 and st != 1.0 for st in (p0.input_horizontal_stretch, p0.input_vertical_stretch))
+    if extras or stretched or not (fisheye or rform):
+        # (p1_setup never ran: build_yuv_args leaves the first pass's focal length and centre at zero — the kernel has no first pass to read them in)
+        header, n4 = re.subn(r"#define GFW_BK_(p1_[fc]) [^\n]*\n", lambda m: "#define GFW_BK_%s __builtin_bit_cast(float, 0x00000000u)\n" % m.group(1), header)
+        assert n4 == 2
+    # the library's key for the same launch: the restatement must be it, line for line (GFW_P1_RFORM is the header's: the radial models' table, whether or not
+    # the host certifies the launch)
+    key = library_key(frames, audit=audit)
+    assert key is not None, "the library would launch an ahead-of-time kernel for these frames"
+    lib_defs, lib_header = key
+    assert lib_defs == {k: str(v) for k, v in defs.items()}, (lib_defs, defs)
+    lib_lines = [l for l in lib_header.splitlines() if not l.startswith("#define GFW_P1_RFORM ")]
+    assert sorted(lib_lines) == sorted(header.splitlines()), sorted(set(lib_lines) ^ set(header.splitlines()))
+    if fast1 or not rform:
+        assert "#define GFW_P1_RFORM (%d)" % (1 if rform else 0) in lib_header.splitlines(), (rform, fast1)
     small = len(frames) * p0.output_width * p0.output_height < 400000
-    lib = C.CDLL(E.build(defs, header, driver="emu_perframe_driver.inc", opt="-O0" if small else "-O1",
-                         extra_flags=("-DGFW_JIT=1", "-DGFW_BAKE=1", "-DEMU_VOTES=0", "-DEMU_HW_ULP=0", "-DEMU_AUDIT=0")))
+    lib = C.CDLL(E.build(lib_defs, lib_header, driver="emu_perframe_driver.inc", opt="-O0" if small else "-O1",
+                         extra_flags=("-DGFW_JIT=1", "-DGFW_BAKE=1", "-DEMU_VOTES=0", "-DEMU_HW_ULP=0", "-DEMU_AUDIT=%d" % (1 if audit else 0))))
     lib.gfw_emu_launch_pf.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p,
                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     n = len(frames)
-    pints, pfloats = np.zeros(24, np.int32), np.zeros(20, np.float32)
+    pints, pfloats = np.zeros(24, np.int32), np.zeros(20, np.float32)       # [16..23]: the declared lengths (audit builds range-check against them)
     for i, pl in enumerate(fr0.planes):
         q = pl["params"]
         pints[4 * i:4 * i + 4] = (q.stride, pl["out_size"][2], pl["size"][0], pl["size"][1])
         pfloats[5 * i:5 * i + 4] = [np.float32(q.background[c]) * np.float32(q.max_pixel_value) for c in range(4)]
         pfloats[5 * i + 4] = q.pixel_value_limit
+        pints[16 + 2 * i], pints[16 + 2 * i + 1] = len(pl["src"]), len(pl["dst"])
     srcs, dsts, mats, keep, outs = (C.c_void_p * (4 * n))(), (C.c_void_p * (4 * n))(), (C.c_void_p * n)(), [], []
     for f, fr in enumerate(frames):
         packed = warp.pack_matrices(fr.matrices)
@@ -102,4 +164,10 @@ def run_frames_pf(frames, grid=8):
                                C.cast(C.byref(p0), C.c_void_p), C.cast(C.byref(com), C.c_void_p), grid, pints.ctypes.data, pfloats.ctypes.data,
                                p1[4].ctypes.data if fast1 else None, C.cast(slots, C.c_void_p))
     assert rc == 0, "gfw_emu_launch_pf -> %d" % rc
+    if audit:
+        words = (C.c_ulonglong * 8)()
+        lib.gfw_emu_audit(words, 1)
+        f32 = lambda w: float(np.array([int(w) & 0xFFFFFFFF], dtype=np.uint32).view(np.float32)[0])
+        return outs, {"certified": int(words[0]), "wrong": int(words[1]), "queued": int(words[2]), "queue_overflow": int(words[3]), "gap_px": f32(words[4]),
+                      "out_of_range": int(words[5]), "eps_px": f32(words[6]) if fast1 else None, "eps_word": int(words[6]), "fast1": fast1}
     return outs

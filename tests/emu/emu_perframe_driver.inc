@@ -5,6 +5,12 @@
 
 static GfwClipArgsPF emu_clip_args_pf;
 static void emu_jit_body() { gfw_jit_kernel(emu_clip_args_pf); }
+#if defined(EMU_AUDIT) && EMU_AUDIT
+// the audit build of the flavour (GFW_JIT_AUDIT=1, bake header GFW_BK_audit (A.audit): what jit_for builds for a per-frame launch under GFW_OPT_KERNEL_VARIANT 3 / 4)
+// — every accepted certificate of the first pass re-derived exactly, every tap / store / matrix row / table entry range-checked: counters in emu_audit_words
+static unsigned long long emu_audit_words[8];
+extern "C" void gfw_emu_audit(unsigned long long *out, int reset) { memcpy(out, emu_audit_words, sizeof(emu_audit_words)); if (reset) memset(emu_audit_words, 0, sizeof(emu_audit_words)); }
+#endif
 
 // As gfw_emu_launch (emu_driver.inc), plus `slots`: n_frames GfwFramePer records — frame f's translation2d, fov, lens_correction_amount, background margin and
 // feather, fill flag.  `kp` is the launch's first frame's KernelParams (the clip-constant fields; the kernel reads the per-frame ones from the slots).
@@ -34,5 +40,9 @@ extern "C" int gfw_emu_launch_pf(int n_frames, const uint8_t *const *src, uint8_
     if (kp) memcpy(&C.Y.kp, kp, sizeof(C.Y.kp));
     if (common) memcpy(&C.Y.common, common, sizeof(C.Y.common));
     C.Y.common.matrices = matrices[0];
+#if defined(EMU_AUDIT) && EMU_AUDIT
+    C.Y.audit = emu_audit_words;
+    for (int p = 0; p < 4; ++p) if (plane_ints) { C.Y.pl[p].src_len = plane_ints[16 + 2 * p]; C.Y.pl[p].dst_len = plane_ints[16 + 2 * p + 1]; }    // (the declared lengths)
+#endif
     return emu::run_grid(grid, emu_jit_body);
 }

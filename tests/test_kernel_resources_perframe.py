@@ -18,14 +18,11 @@ import kernel_resources as KR  # noqa: E402
 SCAN = os.path.join(ROOT, "tools", "scan_trans_hazard.py")
 
 
-def perframe_key(defs, header, blend=False):
-    """the per-frame flavour of a constant-parameter key, as gfw_api_bake.inc derives it: one more definition, no translation2d / fill flag literals; the
-    lens-correction body budgeted at eight waves gets seven (jit_for)"""
-    header, n = re.subn(rb"#define GFW_BK_(t2_[01]|fill_bg) [^\n]*\n", b"", header)
-    assert n == 3
-    if blend:
-        defs = defs.replace(b"GFW_JIT_WAVES=8", b"GFW_JIT_WAVES=7")
-    return defs + b";GFW_JIT_PERFRAME=1", header
+def perframe_key(fr):
+    """the per-frame flavour's key of a one-frame gfw_undistort_clip_params call on device-resident tables, from the library itself
+    (gfw_debug_jit_key_clip_params): one more definition, no translation2d / fill flag literals; the lens-correction body budgeted at eight waves gets seven"""
+    import _emu_perframe as EP
+    return EP.library_key([fr], matrices_on_device=2, raw=True)
 
 
 def compile_(lib, defs, header, out):
@@ -53,7 +50,10 @@ def test_the_per_frame_flavour_keeps_the_constant_builds_resources(tmp_path, wha
     const = compile_(lib, defs, header, str(tmp_path / "const.co"))
     out = str(tmp_path / "perframe.co")
     blend = kw["base_overrides"].get("lens_correction_amount", 1.0) < 1.0 and b"GFW_JIT_WAVES=8" in defs
-    pf = compile_(lib, *perframe_key(defs, header, blend), out)
+    pf_defs, pf_header = perframe_key(fr)
+    assert pf_defs.split(b";") == [d.replace(b"GFW_JIT_WAVES=8", b"GFW_JIT_WAVES=7") if blend else d for d in defs.split(b";")] + [b"GFW_JIT_PERFRAME=1"], (what, pf_defs)
+    assert re.findall(rb"#define GFW_BK_(t2_[01]|fill_bg) ", pf_header) == [] and len(re.findall(rb"#define GFW_BK_(?:t2_[01]|fill_bg) ", header)) == 3, what
+    pf = compile_(lib, pf_defs, pf_header, out)
     assert const[".private_segment_fixed_size"] == 0 and pf[".private_segment_fixed_size"] == 0, (what, const[".private_segment_fixed_size"], pf[".private_segment_fixed_size"])
     want = min(KR.waves_per_simd(const[".vgpr_count"]), 7 if blend else 8)
     assert KR.waves_per_simd(pf[".vgpr_count"]) >= want, (what, pf[".vgpr_count"], const[".vgpr_count"])
