@@ -20,6 +20,7 @@
 #include "gfw_launch.h"
 #include "gfw_frame.h"
 #include "gfw_matrices.h"
+#include "gfw_zoom.h"
 #include "gfw_jit.h"
 #include <stdlib.h>
 #include <map>
@@ -99,6 +100,8 @@ struct gfw_ctx {
     double p1_u1 = 0.0, p1_u2 = 0.0, p1_t32 = 0.0; // max sqrt(rho) |s'|, rho |s'|, rho^1.5 |s''| over the table's range: the curvature of the first pass's value across a lattice cell (gfw_frame.hip)
     DevBuf d_pts_in, d_pts_out, d_pts_rot, d_pts_shift, d_pts_mesh;   // gfw_undistort_points staging
     DevBuf d_tracks;                              // quaternion tracks
+    // gfw_zoom_fovs: frame descriptors (+ caller-given rotations) staged through pinned memory, results for host outputs
+    DevBuf d_zoom_in, d_zoom_out; void *h_zoom = nullptr; size_t h_zoom_cap = 0; hipEvent_t zoom_copied = nullptr;
     // context-owned per-row tables built on the device (gfw_build_matrices): a small ring, built on copy_stream so that
     // frame N+1's table is produced while frame N is being warped; events order builder and consumer both ways
     struct BuiltSlot { DevBuf buf; hipEvent_t built = nullptr, consumed = nullptr; bool used = false; };   // buf = rows + 4 doubles of builder scratch
@@ -316,6 +319,7 @@ void gfw_destroy(gfw_ctx *c) {
     for (auto &e : c->timing_copied) if (e) (void)hipEventDestroy(e);
     for (auto &b : c->bslots) { b.buf.release(); if (b.built) (void)hipEventDestroy(b.built); if (b.consumed) (void)hipEventDestroy(b.consumed); }
     c->d_pts_in.release(); c->d_pts_out.release(); c->d_pts_rot.release(); c->d_pts_shift.release(); c->d_pts_mesh.release();
+    c->d_zoom_in.release(); c->d_zoom_out.release(); if (c->h_zoom) (void)hipHostFree(c->h_zoom); if (c->zoom_copied) (void)hipEventDestroy(c->zoom_copied);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     for (auto &s : c->mslots) {
         if (s.h) (void)hipHostFree(s.h);

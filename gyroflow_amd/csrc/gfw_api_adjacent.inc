@@ -239,3 +239,152 @@ extern "C" int gfw_stmap_undistort(gfw_ctx *c, const gfw_kernel_params *p, const
     if (c->synchronous || !coords_on_device) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);
     return GFW_OK;
 }
+
+// Adaptive zoom, first half: FovIterative::find_fov of every frame (fov_iterative.rs:91-134) in one launch, a workgroup per frame (gfw_zoom.hip).
+// See include/gfwarp.h for the argument contract.
+extern "C" int gfw_zoom_fovs(gfw_ctx *c, const gfw_kernel_params *p, const gfw_zoom_search *search, const gfw_zoom_frame *frames, int n_frames,
+                             const float *rotations, double *fov_minimal, double *debug_points, int out_on_device) {
+    if (!c || !p || !search || n_frames < 0) { set_error("bad zoom arguments (null context / params / search, or n_frames < 0)"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (n_frames == 0) return GFW_OK;                                        // fov_iterative.rs:33 `if timestamps.is_empty() { return Vec::new(); }`
+    if (!frames || !fov_minimal) { set_error("bad zoom arguments (null frames / fov_minimal)"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (search->width < 1 || search->height < 1 || search->org_output_width < 1 || search->org_output_height < 1 || !(search->fov_algorithm_margin == search->fov_algorithm_margin) ||
+        search->horizontal_readout < 0 || search->horizontal_readout > 1) {
+        set_error("bad zoom search: %d x %d, output %d x %d, margin %g, horizontal_readout %d", search->width, search->height, search->org_output_width, search->org_output_height,
+                  (double)search->fov_algorithm_margin, search->horizontal_readout);
+        return GFW_ERR_INVALID_ARGUMENT; }
+    if (p->flags & (256 | 512 | 1024)) {                                     // HAS_IBIS_DATA | HAS_MESH_DATA | HAS_FPD_DATA
+        set_error("the zoom search does not cover per-frame IBIS/OIS shifts, lens meshes or focal-plane distortion data (flags 0x%x): map the outline with gfw_undistort_points", p->flags);
+        return GFW_ERR_INVALID_ARGUMENT; }
+    if (!rotations && c->tracks.org_n < 1 && c->tracks.sm_n < 1) { set_error("no rotations given and no quaternion tracks set (gfw_set_quaternion_tracks)"); return GFW_ERR_INVALID_ARGUMENT; }
+    for (int i = 0; i < n_frames; ++i) {
+        if (frames[i].suppress_rotation < 0 || frames[i].suppress_rotation > 1) { set_error("frame %d: suppress_rotation %d", i, frames[i].suppress_rotation); return GFW_ERR_INVALID_ARGUMENT; }
+        if (rotations && frames[i].frame_readout_time_ms != 0.0) {
+            set_error("frame %d: caller-given rotations are one per frame, but frame_readout_time_ms = %g needs one per point", i, frames[i].frame_readout_time_ms);
+            return GFW_ERR_INVALID_ARGUMENT; }
+    }
+    { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
+    HIP_TRY(hipSetDevice(c->device), GFW_ERR_HIP);
+    // descriptors (and rotations) through pinned memory: the copy is enqueued, the caller's arrays are free on return
+    const size_t fb = sizeof(gfw_zoom_frame) * (size_t)n_frames, rb = rotations ? sizeof(float) * 9 * (size_t)n_frames : 0;
+    if (!c->zoom_copied) HIP_TRY(hipEventCreateWithFlags(&c->zoom_copied, hipEventDisableTiming), GFW_ERR_HIP);
+    HIP_TRY(hipEventSynchronize(c->zoom_copied), GFW_ERR_HIP);              // the copy that last read the pinned block is done
+    if (c->h_zoom_cap < fb + rb) {
+        if (c->h_zoom) (void)hipHostFree(c->h_zoom);
+        c->h_zoom = nullptr; c->h_zoom_cap = 0;
+        HIP_TRY(hipHostMalloc(&c->h_zoom, fb + rb), GFW_ERR_HIP);
+        c->h_zoom_cap = fb + rb;
+    }
+    if (c->d_zoom_in.cap < fb + rb) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);      // a launch in flight may still read the block about to be replaced
+    HIP_TRY(c->d_zoom_in.ensure(fb + rb), GFW_ERR_HIP);
+    memcpy(c->h_zoom, frames, fb);
+    if (rb) memcpy((char *)c->h_zoom + fb, rotations, rb);
+    HIP_TRY(hipMemcpyAsync(c->d_zoom_in.ptr, c->h_zoom, fb + rb, hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
+    HIP_TRY(hipEventRecord(c->zoom_copied, c->stream), GFW_ERR_HIP);
+    const size_t ob = sizeof(double) * (size_t)n_frames, db = debug_points ? sizeof(double) * 2 * GFW_ZOOM_RECT * (size_t)n_frames : 0;
+    double *d_fov = fov_minimal, *d_dbg = debug_points;
+    if (!out_on_device) {
+        HIP_TRY(c->d_zoom_out.ensure(ob + db), GFW_ERR_HIP);
+        d_fov = (double *)c->d_zoom_out.ptr; d_dbg = debug_points ? d_fov + n_frames : nullptr;
+    }
+    GfwZoomArgs A;
+    memset(&A, 0, sizeof(A));
+    A.T = c->tracks;
+    A.frames = (const gfw_zoom_frame *)c->d_zoom_in.ptr;
+    A.rotations = rotations ? (const float *)((const char *)c->d_zoom_in.ptr + fb) : nullptr;
+    A.fov_minimal = d_fov; A.debug_points = d_dbg;
+    A.horizontal = search->horizontal_readout;
+    A.w = (float)search->width; A.h = (float)search->height; A.margin = search->fov_algorithm_margin;
+    // FovIterative::new (fov_iterative.rs:74-80), f32
+    const float ratio = (float)search->width / (float)search->org_output_width;                  // (.max(1): validated >= 1)
+    const float out_dim0 = (float)search->org_output_width * ratio, out_dim1 = (float)search->org_output_height * ratio;
+    A.out_dim0 = out_dim0; A.inv_aspect = out_dim1 / out_dim0;
+    A.readout_dim = search->horizontal_readout ? search->width : search->height;
+    GfwCommon C;
+    fill_common(c, p, nullptr, nullptr, 0, C);
+    HIP_TRY(gfw_launch_zoom(*p, C, A, n_frames, c->stream), GFW_ERR_HIP);
+    c->last_backend = "zoom_fovs";
+    if (!out_on_device) {
+        HIP_TRY(hipMemcpyAsync(fov_minimal, d_fov, ob, hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
+        if (db) HIP_TRY(hipMemcpyAsync(debug_points, d_dbg, db, hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
+    }
+    if (c->synchronous || !out_on_device) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);
+    return GFW_OK;
+}
+
+// Adaptive zoom, second half, on the host: zooming/mod.rs:55-68 and zoom_dynamic.rs in f64, the reference's operation order.
+static int zoom_frames_per_window(double window, double fps) {               // zoom_dynamic.rs:84-90 (`as usize` saturates; NaN -> 0)
+    const double v = floor(window * fps);
+    long long frames = !(v == v) || v <= 0.0 ? 0 : (v >= 1e9 ? 1000000000LL : (long long)v);
+    if (frames % 2 == 0) frames += 1;
+    return (int)frames;
+}
+static std::vector<double> zoom_pad_edge(const std::vector<double> &a, size_t before, size_t after) {       // :119-131
+    std::vector<double> out(a.size() + before + after, 0.0);
+    const double first = a.empty() ? 0.0 : a.front(), last = a.empty() ? 0.0 : a.back();
+    for (size_t i = 0; i < a.size(); ++i) out[before + i] = a[i];
+    for (size_t i = 0; i < before; ++i) out[i] = first;
+    for (size_t i = before + a.size(); i < out.size(); ++i) out[i] = last;
+    return out;
+}
+static std::vector<double> zoom_envelope_follower(const std::vector<double> &a, double alpha) {             // :170-194 with a constant alpha
+    const size_t n = a.size();
+    std::vector<double> rev(n), out(n);
+    if (!n) return out;
+    double q = a[n - 1];
+    for (size_t k = 0; k < n; ++k) { const double x = a[n - 1 - k]; q = fmin(x, x * alpha + q * (1.0 - alpha)); rev[k] = q; }      // smoothed_rev, in reversed order
+    q = rev[n - 1];
+    for (size_t k = 0; k < n; ++k) { const double x = rev[n - 1 - k]; q = fmin(x, x * alpha + q * (1.0 - alpha)); out[k] = q; }
+    return out;
+}
+extern "C" int gfw_zoom_smooth(const double *fov_minimal, int n, double adaptive_zoom_window, double scaled_fps, int method,
+                               const double *trim_ranges, int n_ranges, double *fovs_out, double *fov_minimal_out) {
+    if (n < 0 || n_ranges < 0 || (n && (!fov_minimal || !fovs_out)) || (n_ranges && !trim_ranges) || !(adaptive_zoom_window == adaptive_zoom_window)) {
+        set_error("bad zoom_smooth arguments (n %d, n_ranges %d, window %g)", n, n_ranges, adaptive_zoom_window); return GFW_ERR_INVALID_ARGUMENT; }
+    if (adaptive_zoom_window > 0.0001 && !(scaled_fps > 0.0)) { set_error("scaled_fps %g", scaled_fps); return GFW_ERR_INVALID_ARGUMENT; }
+    if (n == 0) return GFW_OK;
+    std::vector<double> v(fov_minimal, fov_minimal + n);
+    if (n_ranges > 0) {                                                      // fov_iterative.rs:59-69
+        const double l = (double)(n - 1);
+        double max_fov = v[0];
+        for (int i = 1; i < n; ++i) max_fov = fmax(max_fov, v[i]);
+        for (int i = 0; i < n; ++i) {
+            bool within = false;
+            for (int r = 0; r < n_ranges && !within; ++r) {
+                const double lo = floor(l * trim_ranges[r * 2]), hi = ceil(l * trim_ranges[r * 2 + 1]);
+                const double lo_u = !(lo == lo) || lo <= 0.0 ? 0.0 : lo, hi_u = !(hi == hi) || hi <= 0.0 ? 0.0 : hi;              // `as usize`
+                within = (double)i >= lo_u && (double)i <= hi_u;
+            }
+            if (!within) v[i] = max_fov;
+        }
+    }
+    if (fov_minimal_out) for (int i = 0; i < n; ++i) fov_minimal_out[i] = v[i];
+    if (adaptive_zoom_window < -0.9) {                                       // static zoom (mod.rs:55-61)
+        double m = v[0];
+        for (int i = 1; i < n; ++i) m = fmin(m, v[i]);
+        for (int i = 0; i < n; ++i) fovs_out[i] = m;
+    } else if (adaptive_zoom_window > 0.0001) {                              // dynamic zoom (zoom_dynamic.rs:56-79)
+        if (method == 1) {
+            const double first_pass_alpha = 1.0 - exp(-(1.0 / scaled_fps) / adaptive_zoom_window);
+            const double second_pass_alpha = 1.0 - exp(-(1.0 / scaled_fps) / 0.2);
+            v = zoom_envelope_follower(zoom_envelope_follower(v, first_pass_alpha), second_pass_alpha);
+        } else {
+            const int frames = zoom_frames_per_window(adaptive_zoom_window, scaled_fps);
+            const size_t half = (size_t)(frames / 2);
+            const std::vector<double> pad = zoom_pad_edge(v, half, half);
+            std::vector<double> mn((size_t)n);
+            for (int i = 0; i < n; ++i) { double m = pad[i]; for (int k = 1; k < frames; ++k) m = fmin(m, pad[(size_t)i + k]); mn[i] = m; }        // min_rolling
+            const std::vector<double> mpad = zoom_pad_edge(mn, half, half);
+            std::vector<double> g((size_t)frames);                           // gaussian_window_normalized(frames, frames / 6)
+            const double std_ = (double)frames / 6.0, sig2 = 2.0 * (std_ * std_);
+            double sum = 0.0;
+            for (int k = 0; k < frames; ++k) { const long long x = (long long)k - frames / 2; g[k] = exp(-((double)(x * x)) / sig2); }
+            for (int k = 0; k < frames; ++k) sum += g[k];
+            for (int k = 0; k < frames; ++k) g[k] /= sum;
+            for (int i = 0; i < n; ++i) { double s = 0.0; for (int k = 0; k < frames; ++k) s += mpad[(size_t)i + k] * g[k]; v[i] = s; }          // convolve
+        }
+        for (int i = 0; i < n; ++i) fovs_out[i] = v[i];
+    } else {
+        for (int i = 0; i < n; ++i) fovs_out[i] = 1.0;                       // disabled
+    }
+    return GFW_OK;
+}

@@ -15,64 +15,9 @@
 #include "gfw_warp.h"
 #include "gfw_matrices.h"
 #include "gfw_math.h"
+#include "gfw_quat.h"
 
 namespace {
-
-struct Q { double w, x, y, z; };
-__device__ __forceinline__ Q qmul(const Q &a, const Q &b) {
-    return Q{a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
-             a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
-}
-// nalgebra UnitQuaternion::slerp (Unit<Vector4>::try_slerp with the shorter-arc flip)
-__device__ __forceinline__ Q slerp(const Q &a, Q b, double t) {
-    double c = a.w * b.w + a.x * b.x + a.y * b.y + a.z * b.z;
-    if (c < 0.0) { b = Q{-b.w, -b.x, -b.y, -b.z}; c = -c; }
-    if (fabs(c) >= 1.0) return a;
-    const double hang = acos(c);
-    const double s = sqrt(1.0 - c * c);
-    if (s == 0.0) return a;
-    const double ta = sin((1.0 - t) * hang) / s, tb = sin(t * hang) / s;
-    return Q{a.w * ta + b.w * tb, a.x * ta + b.x * tb, a.y * ta + b.y * tb, a.z * ta + b.z * tb};
-}
-// Rust `f64 as i64`: truncate toward zero, saturate, NaN -> 0
-__device__ __forceinline__ int64_t f2i64(double v) {
-    if (!(v == v)) return 0;
-    if (v >= 9223372036854775807.0) return INT64_MAX;
-    if (v <= -9223372036854775808.0) return INT64_MIN;
-    return (int64_t)v;
-}
-// GyroSource::offset_at_timestamp (gyro_source/mod.rs:884-908): linear interpolation (and extrapolation) of the sync offsets
-__device__ double offset_at(const int64_t *ts, const double *v, int n, double timestamp_ms) {
-    if (n <= 0) return 0.0;
-    if (n == 1) return v[0];
-    const int64_t timestamp_us = f2i64(timestamp_ms * 1000.0);
-    int64_t lookup = timestamp_us;
-    if (lookup > ts[n - 1] - 1) lookup = ts[n - 1] - 1;           // .min(last_ts - 1)
-    if (lookup < ts[0] + 1) lookup = ts[0] + 1;                   // .max(first_ts + 1)
-    if (lookup < ts[0]) return 0.0;                               // range(..=lookup) empty
-    int lo = 0, hi = n - 1;                                       // last index with ts[i] <= lookup
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (ts[mid] <= lookup) lo = mid; else hi = mid - 1; }
-    if (ts[lo] == lookup) return v[lo];
-    if (lo + 1 >= n) return 0.0;                                  // range(lookup..) empty
-    const double time_delta = (double)(ts[lo + 1] - ts[lo]);
-    const double fract = (double)(timestamp_us - ts[lo]) / time_delta;
-    return v[lo] + (v[lo + 1] - v[lo]) * fract;
-}
-// GyroSource::quat_at_timestamp (gyro_source/mod.rs:857-882) over a sorted (timestamp_us -> quaternion) track
-__device__ Q quat_at(const GfwTracks &T, const int64_t *ts, const double *q, int n, double timestamp_ms) {
-    if (n < 2 || !(T.duration_ms > 0.0)) return Q{1.0, 0.0, 0.0, 0.0};
-    timestamp_ms -= offset_at(T.off_ts, T.off_ms, T.off_n, timestamp_ms);
-    int64_t lookup = f2i64(round(timestamp_ms * 1000.0));
-    if (lookup > ts[n - 1]) lookup = ts[n - 1];
-    if (lookup < ts[0]) lookup = ts[0];
-    int lo = 0, hi = n - 1;                     // last index with ts[i] <= lookup
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (ts[mid] <= lookup) lo = mid; else hi = mid - 1; }
-    const Q q1{q[lo * 4], q[lo * 4 + 1], q[lo * 4 + 2], q[lo * 4 + 3]};
-    if (ts[lo] == lookup || lo + 1 >= n) return q1;
-    const Q q2{q[lo * 4 + 4], q[lo * 4 + 5], q[lo * 4 + 6], q[lo * 4 + 7]};
-    const double fract = (double)(lookup - ts[lo]) / (double)(ts[lo + 1] - ts[lo]);
-    return slerp(q1, q2, fract);
-}
 
 // The row-independent factor smoothed(ts) * org(ts)^-1 (frame_transform.rs:255-256,289-291), once per frame: a
 // one-lane kernel in front of the row kernel, so that the 34 row waves do one slerp each instead of three.
@@ -83,11 +28,7 @@ __global__ void gfw_build_prefix_kernel(const GfwTracks T, const gfw_frame_timin
     const gfw_frame_timing &F = Fs[f];
     prefix += (size_t)f * 4;
     const double ts = F.timestamp_ms + F.per_frame_time_offset_ms;
-    Q q1 = quat_at(T, T.org_ts, T.org_q, T.org_n, ts);
-    const double n1 = q1.w * q1.w + q1.x * q1.x + q1.y * q1.y + q1.z * q1.z;
-    q1 = Q{q1.w / n1, -q1.x / n1, -q1.y / n1, -q1.z / n1};                         // inverse()
-    const Q sm = quat_at(T, T.sm_ts, T.sm_q, T.sm_n, ts);
-    const Q pre = qmul(sm, q1);
+    const Q pre = quat_prefix(T, ts);
     prefix[0] = pre.w; prefix[1] = pre.x; prefix[2] = pre.y; prefix[3] = pre.z;
 }
 // CatmullRom<Vector3<f64>>::interpolate (gyro_source/splines.rs:22-84) over `n` control points (position, x, y, z);
@@ -124,16 +65,8 @@ __global__ void gfw_build_matrices_kernel(const GfwTracks T, const gfw_frame_tim
     const double qt = (fabs(frt) > 0.0) ? start_ts + row_t * (double)y : start_ts;
     const Q pre{prefix[0], prefix[1], prefix[2], prefix[3]};
     Q q = qmul(pre, quat_at(T, T.org_ts, T.org_q, T.org_n, qt));
-    const double nn = sqrt(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
-    q = Q{q.w / nn, q.x / nn, q.y / nn, q.z / nn};
-    double r[3][3] = {
-        {1 - 2 * (q.y * q.y + q.z * q.z), 2 * (q.x * q.y - q.z * q.w), 2 * (q.x * q.z + q.y * q.w)},
-        {2 * (q.x * q.y + q.z * q.w), 1 - 2 * (q.x * q.x + q.z * q.z), 2 * (q.y * q.z - q.x * q.w)},
-        {2 * (q.x * q.z - q.y * q.w), 2 * (q.y * q.z + q.x * q.w), 1 - 2 * (q.x * q.x + q.y * q.y)}};
-    if (F.video_rotation_deg != 0.0) {                                             // image_rotation * R
-        const double a = F.video_rotation_deg * (3.14159265358979323846 / 180.0), ca = cos(a), sa = sin(a);
-        for (int j = 0; j < 3; ++j) { const double r0 = r[0][j], r1 = r[1][j]; r[0][j] = ca * r0 - sa * r1; r[1][j] = sa * r0 + ca * r1; }
-    }
+    double r[3][3];
+    quat_rotation(q, F.video_rotation_deg, r);
     if (F.framebuffer_inverted) { r[0][2] *= -1.0; r[1][2] *= -1.0; r[2][0] *= -1.0; r[2][1] *= -1.0; }
     else { r[0][1] *= -1.0; r[0][2] *= -1.0; r[1][0] *= -1.0; r[2][0] *= -1.0; }
     // IBIS / OIS terms of this row (frame_transform.rs:270-289)

@@ -96,7 +96,7 @@ class ComputeParams:
                  horizontal_rs=False, background=(0.0, 0.0, 0.0, 0.0), background_mode=0, background_margin=0.0,
                  background_margin_feather=0.0, lens_correction_amount=1.0, light_refraction_coefficient=1.0,
                  adaptive_zoom_center_offset=(0.0, 0.0), scaled_fps=30.0, org_quat_at=None, smoothed_quat_at=None,
-                 video_rotation=0.0, framebuffer_inverted=False):
+                 video_rotation=0.0, framebuffer_inverted=False, adaptive_zoom_window=0.0, fov_algorithm_margin=2.0, trim_ranges=()):
         self.lens = lens
         self.distortion_model, self.digital_lens, self.digital_lens_params = distortion_model, digital_lens, digital_lens_params
         self.width, self.height, self.output_width, self.output_height = width, height, output_width, output_height
@@ -112,6 +112,9 @@ class ComputeParams:
         self.org_quat_at = org_quat_at or ident
         self.smoothed_quat_at = smoothed_quat_at or ident
         self.video_rotation, self.framebuffer_inverted = video_rotation, framebuffer_inverted
+        # the adaptive-zoom search (zooming.calculate_fovs): window in seconds (< -0.9 static zoom, 0 disabled), the outline's margin in pixels
+        # (compute_params.rs:127), the render ranges as fractions of the clip
+        self.adaptive_zoom_window, self.fov_algorithm_margin, self.trim_ranges = adaptive_zoom_window, fov_algorithm_margin, list(trim_ranges)
 
 
 class FrameTransform:

@@ -228,6 +228,29 @@ class Backend:
                                                   index_mode, meshp, meshn, out.ctypes.data, 0))
         return out
 
+    def zoom_fovs(self, params, search, frames, rotations=None, debug=False, out_ptr=None, debug_ptr=None):
+        """FovIterative::find_fov of every frame of a clip in one device call (gfw_zoom_fovs).
+
+        ``params``: the KernelParams `undistort_points` builds; ``search``: abi.ZoomSearch; ``frames``: a ctypes array (or list) of
+        abi.ZoomFrame; ``rotations``: None (rotations from the tracks of set_quaternion_tracks) or [n][9] float32, one `new_k * R` per frame.
+        Returns float64 [n] — with ``debug`` also the first round's polygon, float64 [n][120][2] — or, with ``out_ptr`` (a device pointer to n
+        doubles; ``debug_ptr``: None or a device pointer to n * 240 doubles), None: the results stay on the device, in order on the stream."""
+        n = len(frames)
+        arr = frames if isinstance(frames, C.Array) else (abi.ZoomFrame * max(n, 1))(*frames)
+        rp = None
+        if rotations is not None:
+            rot = np.ascontiguousarray(rotations, dtype=np.float32).reshape(-1, 9)
+            assert rot.shape[0] == n
+            rp = rot.ctypes.data
+        if out_ptr is not None:
+            self._check(self.lib.gfw_zoom_fovs(self.ctx, C.byref(params), C.byref(search), C.cast(arr, C.c_void_p), n, rp, out_ptr, debug_ptr, 1))
+            return None
+        fov = np.zeros(n, dtype=np.float64)
+        dbg = np.zeros((n, abi.ZOOM_RECT_POINTS, 2), dtype=np.float64) if debug else None
+        self._check(self.lib.gfw_zoom_fovs(self.ctx, C.byref(params), C.byref(search), C.cast(arr, C.c_void_p), n, rp, fov.ctypes.data,
+                                           dbg.ctypes.data if debug else None, 0))
+        return (fov, dbg) if debug else fov
+
     def synchronize(self):
         self._check(self.lib.gfw_synchronize(self.ctx))
 
@@ -264,6 +287,20 @@ class Backend:
             mesh = np.ascontiguousarray(mesh, dtype=np.float32)
             meshp, meshn = mesh.ctypes.data, mesh.size
         self._check(self.lib.gfw_undistort_frame(self.ctx, n, barr, parr, tarr, mp, mc, meshp, meshn))
+
+
+def zoom_smooth(fov_minimal, adaptive_zoom_window, scaled_fps, method=0, trim_ranges=()):
+    """zooming/mod.rs:55-68 + zoom_dynamic.rs on the host (gfw_zoom_smooth; no context, no GPU): -> (fovs, fov_minimal after the trim ranges), float64 [n].
+    window < -0.9 static zoom, > 0.0001 dynamic (method 0 Gaussian filter, 1 envelope follower), else 1.0; ``trim_ranges``: (start, end) fractions of the clip."""
+    v = np.ascontiguousarray(fov_minimal, dtype=np.float64).reshape(-1)
+    tr = np.ascontiguousarray(trim_ranges, dtype=np.float64).reshape(-1, 2)
+    out, mn = np.zeros_like(v), np.zeros_like(v)
+    lib = abi.load_library()
+    rc = lib.gfw_zoom_smooth(v.ctypes.data if len(v) else None, len(v), float(adaptive_zoom_window), float(scaled_fps), int(method),
+                             tr.ctypes.data if len(tr) else None, len(tr), out.ctypes.data if len(v) else None, mn.ctypes.data if len(v) else None)
+    if rc != 0:
+        raise GfwError(rc, lib.gfw_last_error().decode())
+    return out, mn
 
 
 def pack_matrices(matrices):

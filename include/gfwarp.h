@@ -468,6 +468,63 @@ int   gfw_undistort_points(gfw_ctx *ctx, const gfw_kernel_params *params, const 
                            const float *rotations, int rotation_count, const float *shifts, int index_mode,
                            const double *mesh, size_t mesh_len, float *out, int out_on_device);
 
+/* ---- adaptive zoom: the per-frame FOV search of a whole clip in one device call (src/core/zooming/) ----
+ * calculate_fovs (zooming/mod.rs:35-70) = FovIterative::find_fov per frame (fov_iterative.rs:91-134), then zoom_dynamic::compute.
+ * gfw_zoom_fovs is the first half on the device, one workgroup per frame: the 120-point outline of the source frame
+ * (points_around_rect(w, h, 31, 31) with fov_algorithm_margin, :154-175) goes through undistort_points_with_rolling_shutter —
+ * per point the rotation of at_timestamp_for_points (frame_transform.rs:376-410: always the four sign flips of :402-403,
+ * whatever framebuffer_inverted says) and the inverse point map of gfw_undistort_points — the zoom centre is subtracted
+ * (:99-102), nearest_edge (:136-151) folds the points in index order, and up to four refinement rounds (:110-131) follow,
+ * restated as written: `rect[idx]` is indexed with the index into the polygon folded last (the 63-point one from the second
+ * round on), `idx.overflowing_sub(1).0 % len` makes rect[15] the left neighbour of rect[0], and a round whose second fold
+ * accepts nothing is followed by one more fold of the same 63 points before the loop ends.
+ *   params     the KernelParams undistort_points builds (:671-683) with input_*_stretch, as for gfw_undistort_points, for the
+ *              ComputeParams calculate_fovs patches (mod.rs:40-49: output size = source size); lens_correction_amount and fov
+ *              are NOT read from it but from each frame's descriptor
+ *   frames     one gfw_zoom_frame per frame (host memory)
+ *   rotations  NULL = rotations from the tracks of gfw_set_quaternion_tracks / gfw_set_sync_offsets; or [n_frames][9] f32 =
+ *              one `new_k * R` per frame given by the caller (no track is read; every frame_readout_time_ms must be 0): the
+ *              form whose result is bit-exact against the CPU statement.  From tracks the f64 acos / sin of the slerp are the
+ *              device library's: a rotation entry can differ from the host's in its last f32 bits (as for gfw_build_matrices).
+ *   fov_minimal   n_frames f64: (nearest.1.0 * 2.0 / output_dim.0) as f64, host or device memory (out_on_device)
+ *   debug_points  NULL, or [n_frames][120][2] f64 in the same memory space: the first round's mapped outline after the centre
+ *              offset, divided by the input size (zooming_debug_points, :103-105)
+ * One launch, in order on the context's stream; with device outputs an asynchronous context returns without waiting.  n_frames = 0 succeeds and writes nothing.
+ * NOT covered, rejected with GFW_ERR_INVALID_ARGUMENT: clips with per-frame IBIS/OIS shifts (frame_transform.rs:412-435) or a
+ * lens mesh / focal-plane distortion data (params->flags has HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA): such a clip keeps
+ * mapping its outline with gfw_undistort_points. */
+typedef struct gfw_zoom_frame {
+    double timestamp_ms;               /* frame centre */
+    double per_frame_time_offset_ms;   /* file_metadata.per_frame_time_offsets[frame] */
+    double frame_readout_time_ms;      /* signed, get_frame_readout_time(can_invert = false) */
+    double new_k[9];                   /* get_new_k(patched params, camera_matrix, fov), row-major */
+    double fov;                        /* get_fov(use_fovs = false) * focal-length compensation: the lens-correction blend's fov */
+    double video_rotation_deg;
+    double zoom_center[2];             /* adaptive_zoom_center_offset, or its keyframed value at the frame (fov_iterative.rs:41-57) */
+    double lens_correction_amount;     /* lens_correction_amount, or its keyframed value */
+    int32_t suppress_rotation;         /* 0 or 1 */
+    int32_t reserved;                  /* 0 */
+} gfw_zoom_frame;
+typedef struct gfw_zoom_search {
+    int32_t width, height;             /* compute_params.width / height (input_dim) */
+    int32_t org_output_width, org_output_height;   /* the output size before calculate_fovs patches it; both >= 1 (0 is rejected: the reference divides by it) */
+    float   fov_algorithm_margin;
+    int32_t horizontal_readout;        /* 1: a point's x picks its time and the row readout time is frame time / width */
+} gfw_zoom_search;
+int   gfw_zoom_fovs(gfw_ctx *ctx, const gfw_kernel_params *params, const gfw_zoom_search *search,
+                    const gfw_zoom_frame *frames, int n_frames, const float *rotations,
+                    double *fov_minimal, double *debug_points, int out_on_device);
+/* The second half, on the host in f64 with the reference's operation order (zooming/mod.rs:55-68, zoom_dynamic.rs); needs no
+ * context and no GPU.  adaptive_zoom_window < -0.9: static zoom (every fov = the minimum); > 0.0001: dynamic zoom over
+ * frames = floor(window * scaled_fps) made odd — method 0 Gaussian filter (pad_edge, min_rolling, pad_edge, convolve with the
+ * normalised Gaussian window of sigma frames / 6), method 1 envelope follower (two passes, the second with a 0.2 s constant;
+ * any other method is the Gaussian filter, as ZoomMethod::from); otherwise 1.0 everywhere.  trim_ranges: n_ranges pairs
+ * (start, end) as fractions of the clip (fov_iterative.rs:59-69), applied to fov_minimal first: frames outside every range get
+ * the maximum.  fovs_out and fov_minimal_out (the series after the trim ranges; may be NULL) hold n values each.
+ * The keyframed-window branch (zoom_dynamic.rs:22-55: ZoomingSpeed keyframes, video speed) is not covered. */
+int   gfw_zoom_smooth(const double *fov_minimal, int n, double adaptive_zoom_window, double scaled_fps, int method,
+                      const double *trim_ranges, int n_ranges, double *fovs_out, double *fov_minimal_out);
+
 /* First-pass audit of the fused kernel (GFW_OPT_KERNEL_VARIANT = 3): counters8 = {certified pixels,
  * certified-but-different-from-exact (must stay 0), queued to the exact path, queue overflows,
  * max |approximate - exact| coordinate over certified pixels as f32 bits, addresses outside their buffer (audit mode range-checks),

@@ -15,6 +15,8 @@
 //   gyroflow::GyroflowCoreError            src/core/lib.rs:2099-2141
 //   gyroflow::{Luma8, Luma16, ...}         src/core/stabilization/pixel_formats.rs (PixelType implementors)
 //
+//   gyroflow::calculate_fovs               src/core/zooming/mod.rs:35-70    (the adaptive-zoom fov series: one device call + host smoothing)
+//
 // `FrameTransform::at_timestamp` itself (quaternions -> per-row matrices) is input here: the caller provides
 // `matrices`, or builds them on the device with gfw_build_matrices / gfw_build_matrices_batch.
 #pragma once
@@ -282,5 +284,25 @@ class Stabilization {
   private:
     std::list<std::pair<uint64_t, gfw_ctx *>> backends_;
 };
+
+// ---- zooming/mod.rs:35-70 `calculate_fovs` over the two C calls: gfw_zoom_fovs (FovIterative::find_fov of every frame, one device call) and gfw_zoom_smooth
+// (static / dynamic / disabled zoom on the host).  `ctx`: a context of the clip's lens models whose tracks are set (gfw_set_quaternion_tracks), or
+// `rotations` = one `new_k * R` (9 f32) per frame.  `params`, `search`, `frames`: see include/gfwarp.h.  -> (fovs, minimal fovs).
+enum class ZoomMethod : int32_t { GaussianFilter = 0, EnvelopeFollower = 1 };                       // mod.rs:16-29
+inline std::pair<std::vector<double>, std::vector<double>> calculate_fovs(gfw_ctx *ctx, const KernelParams &params, const gfw_zoom_search &search,
+                                                                          const std::vector<gfw_zoom_frame> &frames, double adaptive_zoom_window, double scaled_fps,
+                                                                          ZoomMethod method, const std::vector<std::pair<double, double>> &trim_ranges = {},
+                                                                          const float *rotations = nullptr) {
+    const int n = (int)frames.size();
+    std::vector<double> minimal((size_t)n), fovs((size_t)n), trimmed((size_t)n), ranges;
+    if (n == 0) return {fovs, minimal};                                                             // mod.rs:36-38
+    int rc = gfw_zoom_fovs(ctx, &params, &search, frames.data(), n, rotations, minimal.data(), nullptr, 0);
+    if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+    for (const auto &r : trim_ranges) { ranges.push_back(r.first); ranges.push_back(r.second); }
+    rc = gfw_zoom_smooth(minimal.data(), n, adaptive_zoom_window, scaled_fps, (int)method, ranges.empty() ? nullptr : ranges.data(), (int)trim_ranges.size(),
+                         fovs.data(), trimmed.data());
+    if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+    return {fovs, trimmed};
+}
 
 }  // namespace gyroflow
