@@ -68,6 +68,14 @@ struct DevBuf {
     void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; cap = 0; }
 };
 
+// The fused kernel's instantiation, decided by build_yuv_args: gfw_launch_yuv's template arguments, jit_build_defs' leading definitions (all int: compared as memory)
+struct FusedShape {
+    int kind = 0, taps = 2, n0 = 1;              // sample kind (1 = u8, 2 = u16, 3 = f16, 4 = f32), sampler taps (2, 4, 8), channels of plane 0
+    int dw = 1, dh = 1, interleaved = 0;         // chroma subsampling; plane 1 holds both chroma channels
+    int fast1 = 0;                               // the certified first pass
+};
+struct JitKeyMisc { FusedShape shape; int tune_grid = 0, perframe = 0; };      // what jit_for's key holds beside the argument block
+
 struct gfw_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -129,7 +137,7 @@ struct gfw_ctx {
     unsigned long long dry_audit = 0;              // (a dry audit's counters: never written, only named by the key's header)
     std::string arch;                              // gcnArchName of the device
     std::string jit_header; int jit_seen = 0;      // bake header of the frames being seen, and how many in a row
-    GfwYuvArgs jit_key; int jit_key_misc[9] = {}; bool jit_key_valid = false;      // the clip those frames belong to (argument block, per-frame fields blanked)
+    GfwYuvArgs jit_key; JitKeyMisc jit_key_misc; bool jit_key_valid = false;        // the clip those frames belong to (argument block, per-frame fields blanked)
     hipFunction_t jit_fn = nullptr; int jit_grid = 0;                               // its specialised kernel once loaded
     bool jit_dead = false;                                                          // ... or the verdict that there will be none for this clip (build failed / cache full)
     GfwJitInfo jit_info = {GFW_JIT_UNAVAILABLE, 0.0, std::string()};
@@ -163,6 +171,18 @@ int flush_if_pending(gfw_ctx *c);
 static void gfw_forget_context(gfw_ctx *c);
 static void p1_radial_free(gfw_ctx *c);
 static void gfw_register_context(gfw_ctx *c);
+
+// The context forgets its specialised kernel: the next frame looks its clip up again.  keep_info: GFW_OPT_TUNE_GRID leaves gfw_jit_status's answer until then
+static void jit_reset(gfw_ctx *c, bool keep_info = false) {
+    c->jit_fn = nullptr; c->jit_key_valid = false; c->jit_dead = false;
+    if (!keep_info) c->jit_info = GfwJitInfo{GFW_JIT_UNAVAILABLE, 0.0, std::string()};
+}
+// The counters of an audit (GFW_OPT_KERNEL_VARIANT 3 / 4; gfw_get_audit), zeroed on the context's stream when first allocated
+static hipError_t audit_counters(gfw_ctx *c) {
+    const bool fresh = c->d_audit.cap == 0;
+    const hipError_t e = c->d_audit.ensure(8 * sizeof(unsigned long long));
+    return (e == hipSuccess && fresh) ? hipMemsetAsync(c->d_audit.ptr, 0, 8 * sizeof(unsigned long long), c->stream) : e;
+}
 
 static void prof_begin(gfw_ctx *c) {
     if (!c->profile) return;
@@ -340,10 +360,9 @@ int gfw_set_option(gfw_ctx *c, int option, int64_t value) {
                                  c->kernel_variant = (int)value; return GFW_OK;
     case GFW_OPT_PROFILE: c->profile = value != 0; return GFW_OK;
     case GFW_OPT_TUNE_ROWS: c->tune_rb = (int)value; return GFW_OK;
-    case GFW_OPT_TUNE_GRID: c->tune_grid = (int)value; c->jit_fn = nullptr; c->jit_key_valid = false; c->jit_dead = false; return GFW_OK;
+    case GFW_OPT_TUNE_GRID: c->tune_grid = (int)value; jit_reset(c, true); return GFW_OK;
     case GFW_OPT_JIT: if (value < 0 || value > 2) { set_error("GFW_OPT_JIT %lld", (long long)value); return GFW_ERR_INVALID_ARGUMENT; }
-                      c->jit_mode = (int)value; c->jit_fn = nullptr; c->jit_key_valid = false; c->jit_dead = false;
-                      c->jit_info = GfwJitInfo{GFW_JIT_UNAVAILABLE, 0.0, std::string()}; return GFW_OK;
+                      c->jit_mode = (int)value; jit_reset(c); return GFW_OK;
     case GFW_OPT_COALESCE_PLANES: if (value < 0 || value > 2) { set_error("GFW_OPT_COALESCE_PLANES %lld (0..2)", (long long)value); return GFW_ERR_INVALID_ARGUMENT; }
                                   { const int frc = gfw_flush(c); if (frc != GFW_OK) return frc; c->coalesce_planes = (int)value; return GFW_OK; }
     case GFW_OPT_FRAME_SYNC: { const int frc = gfw_flush(c); if (frc != GFW_OK) return frc; c->frame_sync = value != 0; return GFW_OK; }
@@ -387,9 +406,7 @@ int gfw_get_audit(gfw_ctx *c, unsigned long long *counters8, int reset) {
     { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
 
     HIP_TRY(hipSetDevice(c->device), GFW_ERR_HIP);
-    const bool fresh = c->d_audit.cap == 0;
-    HIP_TRY(c->d_audit.ensure(8 * sizeof(unsigned long long)), GFW_ERR_HIP);
-    if (fresh) HIP_TRY(hipMemsetAsync(c->d_audit.ptr, 0, 8 * sizeof(unsigned long long), c->stream), GFW_ERR_HIP);
+    HIP_TRY(audit_counters(c), GFW_ERR_HIP);
     HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);
     HIP_TRY(hipMemcpyAsync(counters8, c->d_audit.ptr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);      // (in order behind the audited launches)
     HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);
@@ -479,6 +496,12 @@ static hipError_t select_device(int device) {
     return hipSetDevice(device);
 }
 
+// rows[14] -> rows[16] on the host (upload_matrices, gfw_pack_matrices): cos / sin of the IBIS roll angle from the host libm, the reference's CPU path's very values (cpu_undistort.rs:159-160)
+static void pack_row(const float *m, float *o) {
+    memcpy(o, m, 14 * sizeof(float));
+    if (m[9] != 0.0f || m[10] != 0.0f || m[11] != 0.0f || m[12] != 0.0f || m[13] != 0.0f) { o[14] = cosf(-m[11]); o[15] = sinf(-m[11]); }
+    else { o[14] = 1.0f; o[15] = 0.0f; }
+}
 static int upload_matrices(gfw_ctx *c, const float *matrices, int matrix_count, const float **d_out) {
     if (!matrices) { set_error("null matrices"); return GFW_ERR_NO_STABILIZATION_DATA; }
     if (matrix_count > c->max_matrix_rows) {
@@ -501,15 +524,7 @@ static int upload_matrices(gfw_ctx *c, const float *matrices, int matrix_count, 
     if (c->matrices_on_device) {
         HIP_TRY(gfw_launch_repack(matrices, s.d, matrix_count, c->stream), GFW_ERR_HIP);
     } else {
-        // host repack into pinned memory; cos/sin of the IBIS roll angle come from the host libm so
-        // they are the very values the reference's CPU path uses (cpu_undistort.rs:159-160)
-        for (int r = 0; r < matrix_count; ++r) {
-            const float *m = matrices + (size_t)r * 14;
-            float *o = s.h + (size_t)r * GFW_MAT_STRIDE;
-            memcpy(o, m, 14 * sizeof(float));
-            if (m[9] != 0.0f || m[10] != 0.0f || m[11] != 0.0f || m[12] != 0.0f || m[13] != 0.0f) { o[14] = cosf(-m[11]); o[15] = sinf(-m[11]); }
-            else { o[14] = 1.0f; o[15] = 0.0f; }
-        }
+        for (int r = 0; r < matrix_count; ++r) pack_row(matrices + (size_t)r * 14, s.h + (size_t)r * GFW_MAT_STRIDE);      // into pinned memory
         HIP_TRY(hipMemcpyAsync(s.d, s.h, (size_t)matrix_count * GFW_MAT_STRIDE * sizeof(float), hipMemcpyHostToDevice, c->copy_stream), GFW_ERR_HIP);
         HIP_TRY(hipEventRecord(s.copied, c->copy_stream), GFW_ERR_HIP);
         HIP_TRY(hipStreamWaitEvent(c->stream, s.copied, 0), GFW_ERR_HIP);
@@ -530,7 +545,7 @@ static int matrices_consumed(gfw_ctx *c) {          // call after the kernels th
     return GFW_OK;
 }
 
-static void fill_common(gfw_ctx *c, const gfw_kernel_params *p, const float *d_mat, const float *d_mesh, int mesh_len, GfwCommon &C) {
+static void fill_common(const gfw_ctx *c, const gfw_kernel_params *p, const float *d_mat, const float *d_mesh, int mesh_len, GfwCommon &C) {
     memset(&C, 0, sizeof(C));
     C.matrices = d_mat; C.mesh = d_mesh; C.mesh_len = mesh_len;
     C.model = c->model; C.digital = c->digital;
@@ -584,14 +599,13 @@ static bool int_products_exact(int n_max, int n) {
     return (int64_t)(n_max - 1) * odd < (1 << 24);
 }
 
+// One frame as the entry points take it: gfw_undistort_frame's arguments, a frame of a clip call, the planes a PlaneGroup assembled
+struct FrameIn { int nplanes; const gfw_buffers *planes; const gfw_kernel_params *params; const int *pixel_types; const float *matrices; int matrix_count; const float *mesh; size_t mesh_len; };
 #include "gfw_api_certificate.inc"
 #include "gfw_api_eligibility.inc"
 #include "gfw_api_clip.inc"
 
 #include "gfw_api_bake.inc"
-// gfw_set_frame_checksums behind a kernel that does not take the sum itself: a pass over what the frame's kernels wrote — the pixels of each plane's output rect
-// (cpu_undistort.rs:546-551: nothing outside it is touched), whole pixels inside the declared length
-static int checksum_written(gfw_ctx *c, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params, unsigned long long *sum);
 // What a plane's kernels WRITE: the pixels of its output rect (cpu_undistort.rs:546-551: nothing outside it is touched), whole pixels inside the declared length,
 // as runs of rows: fn(byte offset of the run's first pixel, bytes per row, rows).  The last row may be cut short by the declared length.
 template <typename F>
@@ -612,6 +626,7 @@ static int for_written_region(const gfw_kernel_params &P, const gfw_buffer_desc 
     if (y1 > y0) return fn(y0 * stride + x0 * bpp, (x1 - x0) * bpp, y1 - y0);
     return GFW_OK;
 }
+// gfw_set_frame_checksums behind a kernel that does not take the sum itself: a pass over what the frame's kernels wrote
 static int checksum_written(gfw_ctx *c, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params, unsigned long long *sum) {
     for (int i = 0; i < nplanes; ++i) {
         const gfw_buffer_desc &o = planes[i].output;
@@ -623,39 +638,38 @@ static int checksum_written(gfw_ctx *c, int nplanes, const gfw_buffers *planes, 
     }
     return GFW_OK;
 }
-static int run_planes(gfw_ctx *c, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params, const int *pixel_types,
-                      const float *matrices, int matrix_count, const float *mesh, size_t mesh_len, ClipBatch *batch = nullptr) {
+// What run_planes' stages hand on: the planes as the kernels take them, the frame's tables on the device, its checksum word (gfw_set_frame_checksums; nullptr: off) ...
+struct StagedFrame { GfwPlane pl[8]; const float *d_mat = nullptr, *d_mesh = nullptr; unsigned long long *sum = nullptr; };
+// ... and the kernel that serves it: the fused one (Y, S) or the generic one per plane; the former's specialised build if there is one, which may take the checksum
+struct KernelChoice { bool fused = false, perframe = false; GfwYuvArgs Y; FusedShape S; hipFunction_t jf = nullptr; int jgrid = 0; bool sum_taken = false; };
+static const char *fused_backend(const FusedShape &S, bool jit) { return jit ? (S.fast1 ? "yuv_fused_p1_jit" : "yuv_fused_jit") : (S.fast1 ? "yuv_fused_p1" : "yuv_fused"); }
+// Stage 1: validate the call and stage what the kernels read — the checksum word, the matrices, the mesh, host planes
+static int stage_frame(gfw_ctx *c, const FrameIn &F, StagedFrame &G) {
     if (!c) { set_error("null context"); return GFW_ERR_INVALID_ARGUMENT; }
-    if (nplanes < 1 || nplanes > 8) { set_error("nplanes %d", nplanes); return GFW_ERR_INVALID_ARGUMENT; }
+    if (F.nplanes < 1 || F.nplanes > 8) { set_error("nplanes %d", F.nplanes); return GFW_ERR_INVALID_ARGUMENT; }
     HIP_TRY(select_device(c->device), GFW_ERR_HIP);
-    for (int i = 0; i < nplanes; ++i) {
-        const int rc = validate_plane(&planes[i], &params[i], pixel_types[i]);
+    for (int i = 0; i < F.nplanes; ++i) {
+        const int rc = validate_plane(&F.planes[i], &F.params[i], F.pixel_types[i]);
         if (rc != GFW_OK) return rc;
-        if (params[i].matrix_count != matrix_count) { set_error("plane %d: matrix_count %d != %d", i, params[i].matrix_count, matrix_count); return GFW_ERR_INVALID_ARGUMENT; }
+        if (F.params[i].matrix_count != F.matrix_count) { set_error("plane %d: matrix_count %d != %d", i, F.params[i].matrix_count, F.matrix_count); return GFW_ERR_INVALID_ARGUMENT; }
     }
-    if (mesh_len > GFW_MESH_MAX) { set_error("Buffer size mismatch buf_mesh_data! %d vs %zu", GFW_MESH_MAX, mesh_len); return GFW_ERR_BUFFER_SIZE_MISMATCH; }  // opencl.rs:352
-    { const int mrc = validate_mesh(mesh, mesh_len); if (mrc != GFW_OK) return mrc; }
+    if (F.mesh_len > GFW_MESH_MAX) { set_error("Buffer size mismatch buf_mesh_data! %d vs %zu", GFW_MESH_MAX, F.mesh_len); return GFW_ERR_BUFFER_SIZE_MISMATCH; }  // opencl.rs:352
+    { const int mrc = validate_mesh(F.mesh, F.mesh_len); if (mrc != GFW_OK) return mrc; }
     // gfw_set_frame_checksums: this frame's word (taken here, before anything is enqueued: a frame that writes host memory cannot be summed on the device)
-    unsigned long long *const sum = c->dry ? nullptr : next_sum(c);
-    if (sum) for (int i = 0; i < nplanes; ++i) if (planes[i].output.kind == GFW_BUF_HOST) { set_error("gfw_set_frame_checksums: plane %d writes a host buffer", i); return GFW_ERR_INVALID_ARGUMENT; }
-    const float *d_mat = nullptr;
-    int rc = upload_matrices(c, matrices, matrix_count, &d_mat);
-    if (rc != GFW_OK) return rc;
-    const float *d_mesh = nullptr;
-    if (mesh && mesh_len) {
-        HIP_TRY(hipMemcpyAsync(c->d_mesh.ptr, mesh, mesh_len * sizeof(float), hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
-        d_mesh = (const float *)c->d_mesh.ptr;
+    G.sum = c->dry ? nullptr : next_sum(c);
+    if (G.sum) for (int i = 0; i < F.nplanes; ++i) if (F.planes[i].output.kind == GFW_BUF_HOST) { set_error("gfw_set_frame_checksums: plane %d writes a host buffer", i); return GFW_ERR_INVALID_ARGUMENT; }
+    { const int rc = upload_matrices(c, F.matrices, F.matrix_count, &G.d_mat); if (rc != GFW_OK) return rc; }
+    if (F.mesh && F.mesh_len) {
+        HIP_TRY(hipMemcpyAsync(c->d_mesh.ptr, F.mesh, F.mesh_len * sizeof(float), hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
+        G.d_mesh = (const float *)c->d_mesh.ptr;
     }
-    if ((int)c->stage_src.size() < nplanes) { c->stage_src.resize(nplanes); c->stage_dst.resize(nplanes); }
-
-    GfwPlane launches_arr[8];
-    GfwPlane *launches = launches_arr;
-    for (int i = 0; i < nplanes; ++i) {
-        const gfw_buffers &b = planes[i];
-        GfwPlane &A = launches[i];
+    if ((int)c->stage_src.size() < F.nplanes) { c->stage_src.resize(F.nplanes); c->stage_dst.resize(F.nplanes); }
+    for (int i = 0; i < F.nplanes; ++i) {
+        const gfw_buffers &b = F.planes[i];
+        GfwPlane &A = G.pl[i];
         memset(&A, 0, sizeof(A));
-        A.p = params[i];
-        A.pix = pixel_types[i];
+        A.p = F.params[i];
+        A.pix = F.pixel_types[i];
         if (b.input.kind == GFW_BUF_HOST) {
             HIP_TRY(c->stage_src[i].ensure(b.input.len), GFW_ERR_HIP);
             HIP_TRY(hipMemcpyAsync(c->stage_src[i].ptr, b.input.data, b.input.len, hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);  // opencl.rs:359
@@ -664,7 +678,7 @@ static int run_planes(gfw_ctx *c, int nplanes, const gfw_buffers *planes, const 
         if (b.output.kind == GFW_BUF_HOST) {
             // Bytes the kernel never writes (stride padding, pixels outside output_rect) must keep the caller's content, as they do on the CPU path.  Rounds 1-5
             // uploaded the destination first and copied all of it back (33 MB more over the link per C2 frame than opencl.rs:408-413 moves); since round 6 nothing is
-            // uploaded and only what the kernels WRITE comes back (for_written_region below): the staging buffer's other bytes are never looked at.  (Page-locking
+            // uploaded and only what the kernels WRITE comes back (finish_frame: for_written_region): the staging buffer's other bytes are never looked at.  (Page-locking
             // the caller's ranges — hipHostRegister, least recently used out — was built and measured in the same call: 1.291 ms per C2 frame with it, 1.298 without;
             // the runtime's pageable path already runs at the link's rate, and a registration that outlives the caller's allocation is a hazard.  Not kept.)
             HIP_TRY(c->stage_dst[i].ensure(b.output.len), GFW_ERR_HIP);
@@ -675,146 +689,158 @@ static int run_planes(gfw_ctx *c, int nplanes, const gfw_buffers *planes, const 
         A.out_rows = (int32_t)((b.output.len + (size_t)b.output.stride - 1) / (size_t)b.output.stride);
         A.out_cols = b.output.stride / A.p.bytes_per_pixel;
     }
-
-    GfwCommon C;
-    GfwYuvArgs Y;
-    int bps = 0, n0 = 1, dw = 1, dh = 1, p1_err = GFW_OK; bool interleaved = false, fast1 = false;
-    const bool fused = build_yuv_args(c, nplanes, planes, params, pixel_types, launches, c->matrices_on_device ? nullptr : matrices,
-                                      matrix_count, mesh_len, Y, bps, n0, dw, dh, interleaved, fast1, batch, p1_err);
-    if (p1_err != GFW_OK) return p1_err;              // (the held frames' launch, sent because the first pass's table was about to be rebuilt)
-    // gfw_set_frame_checksums: this frame's word.  The specialised fused kernel takes the checksum in its store path when every plane starts on a 64-bit word and
-    // every element it stores lies inside one (strides aligned to the element: always, but for a caller's odd sub-buffer); everything else is followed by a pass
-    // over what it wrote.  In a clip launch the alignment is the first frame's to answer for the kernel choice and every frame's to meet (checked where frames join).
-    bool sum_taken = false;
-    if (fused) {
-        fill_common(c, &params[0], d_mat, (Y.extras & 32) ? d_mesh : nullptr, (Y.extras & 32) ? (int)mesh_len : 0, Y.common);
-        Y.matrices = d_mat;
-        if (sum) {
-            const int el = bps == 3 ? 2 : bps;        // bytes per element (sample kind 3: half floats)
-            bool aligned = true;
-            for (int i = 0; i < Y.nplanes; ++i) aligned = aligned && ((uintptr_t)Y.pl[i].dst & 7) == 0 && (Y.pl[i].dst_stride % el) == 0;    // (the kernel places an element in its word by its OFFSET)
-            // (the lane-row adds a frame's 8/16-bit samples up in 32-bit registers: fewer than 2^15 lane-rows per lane and frame even if eight workgroups shared the frame)
-            const long long lane_rows = (long long)Y.tiles_x * Y.tiles_y * gfw_yuv_rows_per_lane(fast1, 0) * dh;
-            Y.checksum = (aligned && lane_rows < 8 * 32768ll) ? 1 : 0;
-        }
-        int jgrid = 0;
-        const bool perframe = batch && batch->perframe;      // (gfw_undistort_clip_params: the per-frame flavour, whose key blanks the per-frame fields)
-        hipFunction_t jf = jit_for(c, Y, bps, params[0].interpolation, n0, dw, dh, interleaved, fast1, &jgrid, perframe);
-        if (!jf && fast1 && Y.p1_rform) {
-            // a table over r is read by specialised builds only: until one is loaded (or for good, without hiprtc and without a cached kernel) the frame takes the
-            // ahead-of-time generic-model kernel and its exact first pass — whose tiles are one lane-row tall
-            fast1 = false; Y.p1_table = nullptr; Y.audit = nullptr;
-            const int rb = gfw_yuv_rows_per_lane(false, 0);
-            Y.tiles_y = (Y.ch + 4 * rb - 1) / (4 * rb);
-        }
-        if (jf && Y.checksum) { const int krc = ck_table(c, jgrid, Y, batch); if (krc != GFW_OK) return krc; sum_taken = true; }
-        bool all_device = c->matrices_on_device != 0;
-        for (int i = 0; i < nplanes; ++i) all_device = all_device && planes[i].input.kind != GFW_BUF_HOST && planes[i].output.kind != GFW_BUF_HOST;
-        if (jf && batch && all_device && c->bslot_cur < 0 && c->mslot_cur < 0) {      // (a table of the cross-stream ring is ordered by events: frame by frame)
-            // the frame joins the clip launch being assembled; a frame that does not share the pending ones' kernel or first-pass table goes out behind them
-            // (a frame that REBUILT the table has already sent them on their way, before the copy: p1_setup — they read the table with the range they were set up for)
-            if (batch->n > 0 && (batch->fn != jf || batch->CA.Y.p1_table != Y.p1_table || batch->CA.Y.p1_rho_max != Y.p1_rho_max ||
-                                 batch->CA.Y.p1_rho_scale != Y.p1_rho_scale || batch->CA.Y.p1_eps != Y.p1_eps || batch->CA.Y.p1_ew != Y.p1_ew ||
-                                 !(perframe ? clip_same_params_pf(batch->CA.Y, Y) : clip_same_params(batch->CA.Y, Y)) || clip_overlaps(batch, planes, nplanes))) {
-                const int frc = clip_flush(c, batch); if (frc != GFW_OK) return frc;
-            }
-            if (batch->n == 0) { batch->CA.Y = Y; batch->fn = jf; batch->grid = jgrid; batch->first = planes; batch->backend = fast1 ? "yuv_fused_p1_jit" : "yuv_fused_jit";
-                                 batch->limit = clip_launch_limit(Y, nplanes, batch->n_call); }
-            batch->sums[batch->n] = sum;
-            sum_commit(c, sum);                       // the frame is part of the pending launch from here on
-            if (perframe) batch->pf[batch->n] = frame_slot(Y);
-            GfwFrameDyn &F = batch->CA.fr[batch->n++];
-            for (int i = 0; i < 4; ++i) { F.src[i] = Y.pl[i].src; F.dst[i] = Y.pl[i].dst; }
-            F.matrices = Y.matrices;
-            c->last_backend = fast1 ? "yuv_fused_p1_jit" : "yuv_fused_jit";
-            if (batch->n >= batch->limit) { const int frc = clip_flush(c, batch); if (frc != GFW_OK) return frc; }
-            if (sum && !sum_taken) {                  // (a frame of a launch whose kernel does not take sums: behind the launch it has just joined)
-                const int frc = clip_flush(c, batch); if (frc != GFW_OK) return frc;
-                const int src_ = checksum_written(c, nplanes, planes, params, sum); if (src_ != GFW_OK) return src_;
-            }
-            return GFW_OK;
-        }
-        if (batch) { const int frc = clip_flush(c, batch); if (frc != GFW_OK) return frc; }
-        prof_begin(c);
-        if (jf) {
-            GfwClipArgs CA;
-            CA.Y = Y; CA.n_frames = 1; CA.pad_ = 0;
-            for (int i = 0; i < 4; ++i) { CA.fr[0].src[i] = Y.pl[i].src; CA.fr[0].dst[i] = Y.pl[i].dst; }
-            CA.fr[0].matrices = Y.matrices;
-            if (perframe) {                           // (a frame of gfw_undistort_clip_params that cannot join a launch — host buffers, a table of the ring — still takes its call's kernel)
-                GfwClipArgsPF PF;
-                PF.C = CA; memset(PF.fr_pf, 0, sizeof(PF.fr_pf)); PF.fr_pf[0] = frame_slot(Y);
-                HIP_TRY(gfw_jit_launch_pf(jf, PF, jgrid, c->stream), GFW_ERR_HIP);
-            } else HIP_TRY(gfw_jit_launch(jf, CA, jgrid, c->stream), GFW_ERR_HIP);
-            if (sum_taken) { const int krc = ck_finish(c, CA, jgrid, &sum); if (krc != GFW_OK) return krc; }
-            timeline_dump(c, jf);
-            c->last_backend = fast1 ? "yuv_fused_p1_jit" : "yuv_fused_jit";
-        } else {
-            HIP_TRY(gfw_launch_yuv(Y, bps, params[0].interpolation, n0, dw, dh, interleaved, fast1, c->stream), GFW_ERR_HIP);
-            c->last_backend = fast1 ? "yuv_fused_p1" : "yuv_fused";
-        }
-    } else {
-        if (batch) { const int frc = clip_flush(c, batch); if (frc != GFW_OK) return frc; }
-        prof_begin(c);
-        for (int i = 0; i < nplanes; ++i) {
-            // EWA on planar chroma (round 6): planes i and i + 1 are single-channel planes of one pixel type, one geometry and — but for plane_index (never 0: the
-            // colour-range fix asks only whether a plane is luma) and the background — one KernelParams: the coordinates, jacobians and tap weights of their pixels
-            // are the same numbers.  One launch works them out once and keeps two sets of sums (gfw_plane_kernel<.., DUAL>): 1.43 -> 1.11 ms per C2 frame.
-            bool paired = false;
-            // (plane_index is read for one thing, the colour-range fix's luma / chroma scale: without the flag any two planes qualify — the four planes of a planar
-            // float frame leave as two launches —, with it two planes that are both chroma)
-            if (i + 1 < nplanes && params[i].interpolation >= 10 && PIX_N[pixel_types[i]] == 1 && pixel_types[i] == pixel_types[i + 1] &&
-                ((params[i].plane_index != 0 && params[i + 1].plane_index != 0) || (((params[i].flags | params[i + 1].flags) & GFW_FLAG_FIX_COLOR_RANGE) == 0))) {
-                gfw_kernel_params q = params[i + 1];
-                q.plane_index = params[i].plane_index;
-                memcpy(q.background, params[i].background, sizeof(q.background));
-                const GfwPlane &a = launches[i], &b = launches[i + 1];
-                // (the two launches it replaces run one after the other: the second plane may not read or overwrite what the first writes, nor the first the second's)
-                auto apart = [](const uint8_t *p, size_t pn, const uint8_t *r, size_t rn) { return p + pn <= r || r + rn <= p; };
-                const size_t il = planes[i].input.len, ol = (size_t)a.dst_len;
-                paired = memcmp(&q, &params[i], sizeof(q)) == 0 && a.dst_len == b.dst_len && a.dst_stride == b.dst_stride && a.out_rows == b.out_rows && a.out_cols == b.out_cols &&
-                         planes[i].input.len == planes[i + 1].input.len && apart(a.dst, ol, b.dst, ol) && apart(a.dst, ol, b.src, il) && apart(b.dst, ol, a.src, il);
-            }
-            fill_common(c, &params[i], d_mat, d_mesh, (int)mesh_len, C);
-            if (paired) {
-                GfwPlane two = launches[i];
-                two.src2 = launches[i + 1].src; two.dst2 = launches[i + 1].dst;
-                memcpy(two.background2, params[i + 1].background, sizeof(two.background2));
-                HIP_TRY(gfw_launch_plane(two, C, c->stream), GFW_ERR_HIP);
-                c->paired_launches++;
-                ++i;
-                continue;
-            }
-            HIP_TRY(gfw_launch_plane(launches[i], C, c->stream), GFW_ERR_HIP);
-        }
-        c->last_backend = "plane_generic";
+    return GFW_OK;
+}
+// Stage 2: which kernel — the fused one if build_yuv_args proves the frame eligible, its specialised build if jit_for has one
+static int choose_kernel(gfw_ctx *c, const FrameIn &F, const StagedFrame &G, ClipBatch *batch, KernelChoice &K) {
+    GfwYuvArgs &Y = K.Y; FusedShape &S = K.S;
+    { const int rc = build_yuv_args(c, F, G.pl, batch, Y, S, K.fused); if (rc != GFW_OK) return rc; }      // (the held frames' launch, sent because the first pass's table was about to be rebuilt)
+    if (!K.fused) return GFW_OK;
+    fill_common(c, &F.params[0], G.d_mat, (Y.extras & 32) ? G.d_mesh : nullptr, (Y.extras & 32) ? (int)F.mesh_len : 0, Y.common);
+    Y.matrices = G.d_mat;
+    // gfw_set_frame_checksums: the specialised fused kernel takes the checksum in its store path when every plane starts on a 64-bit word and every element it stores
+    // lies inside one (strides aligned to the element: always, but for a caller's odd sub-buffer); everything else is followed by a pass over what it wrote.  In a clip
+    // launch the alignment is the first frame's to answer for the kernel choice and every frame's to meet (checked where frames join).
+    if (G.sum) {
+        const int el = S.kind == 3 ? 2 : S.kind;      // bytes per element (sample kind 3: half floats)
+        bool aligned = true;
+        for (int i = 0; i < Y.nplanes; ++i) aligned = aligned && ((uintptr_t)Y.pl[i].dst & 7) == 0 && (Y.pl[i].dst_stride % el) == 0;    // (the kernel places an element in its word by its OFFSET)
+        // (the lane-row adds a frame's 8/16-bit samples up in 32-bit registers: fewer than 2^15 lane-rows per lane and frame even if eight workgroups shared the frame)
+        const long long lane_rows = (long long)Y.tiles_x * Y.tiles_y * gfw_yuv_rows_per_lane(S.fast1 != 0, 0) * S.dh;
+        Y.checksum = (aligned && lane_rows < 8 * 32768ll) ? 1 : 0;
     }
-    sum_commit(c, sum);                               // the frame's kernels are enqueued
-    if (sum && !sum_taken) { const int src_ = checksum_written(c, nplanes, planes, params, sum); if (src_ != GFW_OK) return src_; }
+    K.perframe = batch && batch->perframe;            // (gfw_undistort_clip_params: the per-frame flavour, whose key blanks the per-frame fields)
+    K.jf = jit_for(c, Y, S, K.perframe, &K.jgrid);
+    if (!K.jf && S.fast1 && Y.p1_rform) {
+        // a table over r is read by specialised builds only: until one is loaded (or for good, without hiprtc and without a cached kernel) the frame takes the
+        // ahead-of-time generic-model kernel and its exact first pass — whose tiles are one lane-row tall
+        S.fast1 = 0; Y.p1_table = nullptr; Y.audit = nullptr;
+        Y.tiles_y = tiles_y_of(Y, gfw_yuv_rows_per_lane(false, 0));
+    }
+    if (K.jf && Y.checksum) { const int krc = ck_table(c, K.jgrid, Y, batch); if (krc != GFW_OK) return krc; K.sum_taken = true; }
+    return GFW_OK;
+}
+// Way out 1: the frame joins the clip launch being assembled — if nothing of it is the host's, nor its table one of the cross-stream ring's (ordered by events: frame by frame)
+static bool frame_can_wait(const gfw_ctx *c, const FrameIn &F) {
+    bool all_device = c->matrices_on_device != 0;
+    for (int i = 0; i < F.nplanes; ++i) all_device = all_device && F.planes[i].input.kind != GFW_BUF_HOST && F.planes[i].output.kind != GFW_BUF_HOST;
+    return all_device && c->bslot_cur < 0 && c->mslot_cur < 0;
+}
+static int join_launch(gfw_ctx *c, const FrameIn &F, const KernelChoice &K, unsigned long long *sum, ClipBatch *batch) {
+    const GfwYuvArgs &Y = K.Y;
+    // a frame that does not share the pending ones' kernel or first-pass table goes out behind them
+    // (a frame that REBUILT the table has already sent them on their way, before the copy: p1_setup — they read the table with the range they were set up for)
+    if (batch->n > 0 && (batch->fn != K.jf || batch->CA.Y.p1_table != Y.p1_table || batch->CA.Y.p1_rho_max != Y.p1_rho_max ||
+                         batch->CA.Y.p1_rho_scale != Y.p1_rho_scale || batch->CA.Y.p1_eps != Y.p1_eps || batch->CA.Y.p1_ew != Y.p1_ew ||
+                         !(batch->perframe ? clip_same_params_pf(batch->CA.Y, Y) : clip_same_params(batch->CA.Y, Y)) || clip_overlaps(batch, F.planes, F.nplanes))) {
+        const int frc = clip_flush(c, batch); if (frc != GFW_OK) return frc;
+    }
+    if (batch->n == 0) { batch->CA.Y = Y; batch->fn = K.jf; batch->grid = K.jgrid; batch->first = F.planes; batch->backend = fused_backend(K.S, true);
+                         batch->limit = clip_launch_limit(Y, F.nplanes, batch->n_call); }
+    const GfwFramePer slot = frame_slot(Y);
+    { const int frc = clip_append(c, batch, frame_dyn(Y), K.perframe ? &slot : nullptr, sum); if (frc != GFW_OK) return frc; }
+    if (sum && !K.sum_taken) {                        // (a frame of a launch whose kernel does not take sums: behind the launch it has just joined)
+        const int frc = clip_flush(c, batch); if (frc != GFW_OK) return frc;
+        return checksum_written(c, F.nplanes, F.planes, F.params, sum);
+    }
+    return GFW_OK;
+}
+// Way out 2: one launch of the fused kernel for this frame alone
+static int launch_fused(gfw_ctx *c, const KernelChoice &K, unsigned long long *sum) {
+    const FusedShape &S = K.S;
+    if (K.jf) {
+        GfwClipArgs CA;
+        CA.Y = K.Y; CA.n_frames = 1; CA.pad_ = 0; CA.fr[0] = frame_dyn(K.Y);
+        const GfwFramePer slot = frame_slot(K.Y);      // (a frame of gfw_undistort_clip_params that cannot join a launch — host buffers, a table of the ring — still takes its call's kernel)
+        const int rc = jit_launch(c, K.jf, K.jgrid, CA, K.perframe ? &slot : nullptr, &sum); if (rc != GFW_OK) return rc;
+    } else HIP_TRY(gfw_launch_yuv(K.Y, S.kind, S.taps, S.n0, S.dw, S.dh, S.interleaved != 0, S.fast1 != 0, c->stream), GFW_ERR_HIP);
+    c->last_backend = fused_backend(S, K.jf != nullptr);
+    return GFW_OK;
+}
+// Way out 3: the generic kernel, plane by plane.  EWA on planar chroma (round 6): planes i and i + 1 are single-channel planes of one pixel type, one geometry and —
+// but for plane_index (never 0: the colour-range fix asks only whether a plane is luma) and the background — one KernelParams: the coordinates, jacobians and tap
+// weights of their pixels are the same numbers.  One launch works them out once and keeps two sets of sums (gfw_plane_kernel<.., DUAL>): 1.43 -> 1.11 ms per C2 frame.
+static bool ewa_pair(const FrameIn &F, const GfwPlane *pl, int i) {
+    const gfw_kernel_params *params = F.params;
+    // (plane_index is read for one thing, the colour-range fix's luma / chroma scale: without the flag any two planes qualify — the four planes of a planar
+    // float frame leave as two launches —, with it two planes that are both chroma)
+    if (!(i + 1 < F.nplanes && params[i].interpolation >= 10 && PIX_N[F.pixel_types[i]] == 1 && F.pixel_types[i] == F.pixel_types[i + 1] &&
+          ((params[i].plane_index != 0 && params[i + 1].plane_index != 0) || (((params[i].flags | params[i + 1].flags) & GFW_FLAG_FIX_COLOR_RANGE) == 0)))) return false;
+    gfw_kernel_params q = params[i + 1];
+    q.plane_index = params[i].plane_index;
+    memcpy(q.background, params[i].background, sizeof(q.background));
+    const GfwPlane &a = pl[i], &b = pl[i + 1];
+    // (the two launches it replaces run one after the other: the second plane may not read or overwrite what the first writes, nor the first the second's)
+    auto apart = [](const uint8_t *p, size_t pn, const uint8_t *r, size_t rn) { return p + pn <= r || r + rn <= p; };
+    const size_t il = F.planes[i].input.len, ol = (size_t)a.dst_len;
+    return memcmp(&q, &params[i], sizeof(q)) == 0 && a.dst_len == b.dst_len && a.dst_stride == b.dst_stride && a.out_rows == b.out_rows && a.out_cols == b.out_cols &&
+           F.planes[i].input.len == F.planes[i + 1].input.len && apart(a.dst, ol, b.dst, ol) && apart(a.dst, ol, b.src, il) && apart(b.dst, ol, a.src, il);
+}
+static int launch_per_plane(gfw_ctx *c, const FrameIn &F, const StagedFrame &G) {
+    for (int i = 0; i < F.nplanes; ++i) {
+        GfwCommon C;
+        fill_common(c, &F.params[i], G.d_mat, G.d_mesh, (int)F.mesh_len, C);
+        if (ewa_pair(F, G.pl, i)) {
+            GfwPlane two = G.pl[i];
+            two.src2 = G.pl[i + 1].src; two.dst2 = G.pl[i + 1].dst;
+            memcpy(two.background2, F.params[i + 1].background, sizeof(two.background2));
+            HIP_TRY(gfw_launch_plane(two, C, c->stream), GFW_ERR_HIP);
+            c->paired_launches++;
+            ++i;
+        } else HIP_TRY(gfw_launch_plane(G.pl[i], C, c->stream), GFW_ERR_HIP);
+    }
+    c->last_backend = "plane_generic";
+    return GFW_OK;
+}
+// The last stage: the frame's kernels are enqueued — its checksum, the profile bracket, the matrix slot, host outputs, the synchronous caller's wait
+static int finish_frame(gfw_ctx *c, const FrameIn &F, const StagedFrame &G, bool sum_taken) {
+    sum_commit(c, G.sum);
+    if (G.sum && !sum_taken) { const int src_ = checksum_written(c, F.nplanes, F.planes, F.params, G.sum); if (src_ != GFW_OK) return src_; }
     prof_end(c);
     { const int mrc = matrices_consumed(c); if (mrc != GFW_OK) return mrc; }
     if (c->ev_used > 4096) { (void)hipStreamSynchronize(c->stream); prof_harvest(c); }
-
     bool any_host_out = false;
-    for (int i = 0; i < nplanes; ++i) {
-        if (planes[i].output.kind == GFW_BUF_HOST) {
-            // opencl.rs:413 reads the whole buffer back; here: the written pixels only — one linear copy when the rows are written whole, else a pitched one
-            uint8_t *host = (uint8_t *)planes[i].output.data; const uint8_t *dev = (const uint8_t *)c->stage_dst[i].ptr; const long long stride = planes[i].output.stride;
-            const int crc = for_written_region(params[i], planes[i].output, [&](long long off, long long row_bytes, long long rows) -> int {
-                if (row_bytes == stride || rows == 1) HIP_TRY(hipMemcpyAsync(host + off, dev + off, (size_t)(rows == 1 ? row_bytes : row_bytes * rows), hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
-                else HIP_TRY(hipMemcpy2DAsync(host + off, (size_t)stride, dev + off, (size_t)stride, (size_t)row_bytes, (size_t)rows, hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
-                return GFW_OK;
-            });
-            if (crc != GFW_OK) return crc;
-            any_host_out = true;
-        }
+    for (int i = 0; i < F.nplanes; ++i) {
+        if (F.planes[i].output.kind != GFW_BUF_HOST) continue;
+        // opencl.rs:413 reads the whole buffer back; here: the written pixels only — one linear copy when the rows are written whole, else a pitched one
+        uint8_t *host = (uint8_t *)F.planes[i].output.data; const uint8_t *dev = (const uint8_t *)c->stage_dst[i].ptr; const long long stride = F.planes[i].output.stride;
+        const int crc = for_written_region(F.params[i], F.planes[i].output, [&](long long off, long long row_bytes, long long rows) -> int {
+            if (row_bytes == stride || rows == 1) HIP_TRY(hipMemcpyAsync(host + off, dev + off, (size_t)(rows == 1 ? row_bytes : row_bytes * rows), hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
+            else HIP_TRY(hipMemcpy2DAsync(host + off, (size_t)stride, dev + off, (size_t)stride, (size_t)row_bytes, (size_t)rows, hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
+            return GFW_OK;
+        });
+        if (crc != GFW_OK) return crc;
+        any_host_out = true;
     }
     if (c->synchronous || any_host_out) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);
     return GFW_OK;
 }
+// `batch`: the clip launch being assembled by the caller (a clip entry point, the frames a context holds), which this frame joins if it can and sends off if it cannot
+static int run_planes(gfw_ctx *c, const FrameIn &F, ClipBatch *batch = nullptr) {
+    StagedFrame G;
+    KernelChoice K;
+    { const int rc = stage_frame(c, F, G); if (rc != GFW_OK) return rc; }
+    { const int rc = choose_kernel(c, F, G, batch, K); if (rc != GFW_OK) return rc; }
+    if (K.jf && batch && frame_can_wait(c, F)) return join_launch(c, F, K, G.sum, batch);
+    { const int rc = clip_flush(c, batch); if (rc != GFW_OK) return rc; }      // (the calls are ordered: what is pending leaves first)
+    prof_begin(c);
+    { const int rc = K.fused ? launch_fused(c, K, G.sum) : launch_per_plane(c, F, G); if (rc != GFW_OK) return rc; }
+    return finish_frame(c, F, G, K.sum_taken);
+}
 
 #include "gfw_api_coalesce.inc"
 
+// (a context that takes no part in a held frame or launch, called by a thread that holds nothing: read without the lock)
+static bool nothing_pending(const gfw_ctx *c) {
+    return !(t_group && t_group->n > 0) && !(c->held && c->held->n > 0) && !c->needs_order && c->pending_planes.load(std::memory_order_relaxed) == 0;
+}
+// Entry points other than gfw_undistort_image keep their place in the order of calls: whatever is being held leaves first (no lock when nothing is)
+int flush_if_pending(gfw_ctx *c) { return (!c || nothing_pending(c)) ? GFW_OK : gfw_flush(c); }
+static int check_pixel_types(int nplanes, const int *pixel_types) {
+    for (int i = 0; i < nplanes; ++i)
+        if (pixel_types[i] < 0 || pixel_types[i] >= GFW_PIX_COUNT) { set_error("plane %d: unknown pixel type %d", i, pixel_types[i]); return GFW_ERR_INVALID_ARGUMENT; }
+    return GFW_OK;
+}
 extern "C" {
 
 int gfw_flush(gfw_ctx *c) {
@@ -822,14 +848,6 @@ int gfw_flush(gfw_ctx *c) {
     GroupLock lk(g_group_mu);
     return flush_context_locked(c, lk);
 }
-}  // extern "C"
-// Entry points other than gfw_undistort_image keep their place in the order of calls: whatever is being held leaves first (no lock when nothing is)
-int flush_if_pending(gfw_ctx *c) {
-    if (!c) return GFW_OK;
-    if (!(t_group && t_group->n > 0) && !(c->held && c->held->n > 0) && !c->needs_order && c->pending_planes.load(std::memory_order_relaxed) == 0) return GFW_OK;
-    return gfw_flush(c);
-}
-extern "C" {
 
 int gfw_undistort_image(gfw_ctx *c, const gfw_buffers *buffers, const gfw_kernel_params *params,
                         const float *matrices, int matrix_count, const uint8_t *drawing, size_t drawing_len,
@@ -848,9 +866,8 @@ int gfw_undistort_image(gfw_ctx *c, const gfw_buffers *buffers, const gfw_kernel
     bool holdable = may_hold && (!c->synchronous || c->frame_sync) && buffers && params && matrices && single_channel && c->kernel_variant == 0 &&
                           buffers->input.kind == GFW_BUF_HIP_DEVICE && buffers->output.kind == GFW_BUF_HIP_DEVICE && (!mesh || mesh_len == 0) &&
                           params->plane_index >= 0 && params->plane_index < 4 && matrix_count >= 1;
-    // (a context that never took part in a held frame, called by a thread that holds nothing: the round-3 path, no lock)
-    if (!holdable && !(t_group && t_group->n > 0) && !(c->held && c->held->n > 0) && !c->needs_order)
-        return run_planes(c, 1, buffers, params, &pt, matrices, matrix_count, mesh, mesh_len);
+    const FrameIn F = {1, buffers, params, &pt, matrices, matrix_count, mesh, mesh_len};
+    if (!holdable && nothing_pending(c)) return run_planes(c, F);      // (the round-3 path, no lock)
     GroupLock lk(g_group_mu);
     PlaneGroup *g = t_group;
     if (!g && holdable) { g = t_group = new PlaneGroup(); g->thread = std::this_thread::get_id(); g_groups.push_back(g); }
@@ -873,7 +890,7 @@ int gfw_undistort_image(gfw_ctx *c, const gfw_buffers *buffers, const gfw_kernel
     if (!cont && !(starts && c->coalesce_frames > 1)) { const int frc = flush_context_locked(c, lk); if (frc != GFW_OK) return frc; }
     if (!cont && !starts) {
         lk.unlock();
-        return run_planes(c, 1, buffers, params, &pt, matrices, matrix_count, mesh, mesh_len);
+        return run_planes(c, F);
     }
     {   // the errors of this plane belong to this call
         const int vrc = validate_plane(buffers, params, pt);
@@ -906,10 +923,9 @@ int gfw_undistort_image(gfw_ctx *c, const gfw_buffers *buffers, const gfw_kernel
 int gfw_undistort_frame(gfw_ctx *c, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params,
                         const int *pixel_types, const float *matrices, int matrix_count, const float *mesh, size_t mesh_len) {
     if (!planes || !params || !pixel_types) { set_error("null plane arrays"); return GFW_ERR_INVALID_ARGUMENT; }
-    for (int i = 0; i < nplanes; ++i)
-        if (pixel_types[i] < 0 || pixel_types[i] >= GFW_PIX_COUNT) { set_error("plane %d: unknown pixel type %d", i, pixel_types[i]); return GFW_ERR_INVALID_ARGUMENT; }
+    { const int prc = check_pixel_types(nplanes, pixel_types); if (prc != GFW_OK) return prc; }
     { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
-    return run_planes(c, nplanes, planes, params, pixel_types, matrices, matrix_count, mesh, mesh_len);
+    return run_planes(c, FrameIn{nplanes, planes, params, pixel_types, matrices, matrix_count, mesh, mesh_len});
 }
 
 int gfw_undistort_clip(gfw_ctx *c, int n_frames, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params,
@@ -917,42 +933,34 @@ int gfw_undistort_clip(gfw_ctx *c, int n_frames, int nplanes, const gfw_buffers 
     if (!c) { set_error("null context"); return GFW_ERR_INVALID_ARGUMENT; }
     if (n_frames < 0 || !planes || !params || !pixel_types || !matrices) { set_error("null clip arrays"); return GFW_ERR_INVALID_ARGUMENT; }
     { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
-
-    for (int i = 0; i < nplanes; ++i)
-        if (pixel_types[i] < 0 || pixel_types[i] >= GFW_PIX_COUNT) { set_error("plane %d: unknown pixel type %d", i, pixel_types[i]); return GFW_ERR_INVALID_ARGUMENT; }
+    { const int prc = check_pixel_types(nplanes, pixel_types); if (prc != GFW_OK) return prc; }
     // the frame loop of a render (rendering/mod.rs:487-547 calls process_pixels once per frame), here on the library side: frames that
     // share the specialised kernel leave in launches of up to GFW_CLIP_MAX frames, everything else exactly as gfw_undistort_frame
     ClipBatch batch;
     batch.n_call = n_frames;
     for (int f = 0; f < n_frames; ++f) {
+        const gfw_buffers *fp = planes + (size_t)f * nplanes;
         // A frame shaped exactly like the one that opened the pending launch (same descriptions but for the pointers; the parameters are
         // shared by construction) needs none of the per-frame validation again: its pointers join the launch.  ~10 us -> < 1 us of host time.
         bool words = true;                            // (the checksum build places an element by its offset: every plane on a 64-bit word, as run_planes checked for the launch's first frame)
-        if (c->sums && batch.n > 0) for (int i = 0; i < nplanes && i < 4; ++i) words = words && (((uintptr_t)planes[(size_t)f * nplanes + i].output.data + (uintptr_t)(batch.CA.fr[0].dst[i] - (uint8_t *)batch.first[i].output.data)) & 7) == 0;
-        if (batch.n > 0 && batch.n < batch.limit && (!c->sums || (batch.CA.Y.checksum && words)) && c->matrices_on_device == 2 && matrices[f] && clip_same_shape(batch.first, planes + (size_t)f * nplanes, nplanes) &&
-            !clip_ring_table(c, matrices[f]) && !clip_overlaps(&batch, planes + (size_t)f * nplanes, nplanes)) {
-            batch.sums[batch.n] = next_sum(c);
-            sum_commit(c, batch.sums[batch.n]);
-            GfwFrameDyn &F = batch.CA.fr[batch.n++];
+        if (c->sums && batch.n > 0) for (int i = 0; i < nplanes && i < 4; ++i) words = words && (((uintptr_t)fp[i].output.data + (uintptr_t)(batch.CA.fr[0].dst[i] - (uint8_t *)batch.first[i].output.data)) & 7) == 0;
+        if (batch.n > 0 && batch.n < batch.limit && (!c->sums || (batch.CA.Y.checksum && words)) && c->matrices_on_device == 2 && matrices[f] && clip_same_shape(batch.first, fp, nplanes) &&
+            !clip_ring_table(c, matrices[f]) && !clip_overlaps(&batch, fp, nplanes)) {
+            GfwFrameDyn D;
             for (int i = 0; i < 4; ++i) {
                 // (the kernel's planes begin at their rects' first pixels: the same offsets the launch's first frame was given — clip_same_shape compared the rects)
                 const ptrdiff_t so = i < nplanes ? batch.CA.fr[0].src[i] - (const uint8_t *)batch.first[i].input.data : 0, dof = i < nplanes ? batch.CA.fr[0].dst[i] - (uint8_t *)batch.first[i].output.data : 0;
-                F.src[i] = i < nplanes ? (const uint8_t *)planes[(size_t)f * nplanes + i].input.data + so : nullptr;
-                F.dst[i] = i < nplanes ? (uint8_t *)planes[(size_t)f * nplanes + i].output.data + dof : nullptr;
+                D.src[i] = i < nplanes ? (const uint8_t *)fp[i].input.data + so : nullptr;
+                D.dst[i] = i < nplanes ? (uint8_t *)fp[i].output.data + dof : nullptr;
             }
-            F.matrices = matrices[f];
-            c->last_backend = batch.backend;
-            if (batch.n >= batch.limit) { const int frc = clip_flush(c, &batch); if (frc != GFW_OK) return frc; }
+            D.matrices = matrices[f];
+            const int frc = clip_append(c, &batch, D, nullptr, next_sum(c)); if (frc != GFW_OK) return frc;
             continue;
         }
-        const int rc = run_planes(c, nplanes, planes + (size_t)f * nplanes, params, pixel_types, matrices[f], matrix_count, nullptr, 0, &batch);
-        if (rc != GFW_OK) { (void)clip_flush(c, &batch); if (c->synchronous) (void)hipStreamSynchronize(c->stream); return rc; }
+        const int rc = run_planes(c, FrameIn{nplanes, fp, params, pixel_types, matrices[f], matrix_count, nullptr, 0}, &batch);
+        if (rc != GFW_OK) return clip_end(c, &batch, rc);
     }
-    const int frc = clip_flush(c, &batch);
-    // GFW_OPT_SYNCHRONOUS (the default) means what it means for gfw_undistort_frame: the outputs are complete when the call returns — a frame that
-    // joined a clip launch left run_planes before its own synchronisation point (round-3 advisor finding)
-    if (c->synchronous) { const hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess && frc == GFW_OK) { set_error("hipStreamSynchronize failed: %s", hipGetErrorString(e)); return GFW_ERR_HIP; } }
-    return frc;
+    return clip_end(c, &batch, GFW_OK);
 }
 
 // The frame loop of a render whose KernelParams move from frame to frame (FrameTransform::at_timestamp fills them per frame: the adaptive-zoom fov and its
@@ -964,25 +972,15 @@ int gfw_undistort_clip_params(gfw_ctx *c, int n_frames, int nplanes, const gfw_b
     if (!c) { set_error("null context"); return GFW_ERR_INVALID_ARGUMENT; }
     if (n_frames < 0 || !planes || !params || !pixel_types || !matrices) { set_error("null clip arrays"); return GFW_ERR_INVALID_ARGUMENT; }
     if (nplanes < 1 || nplanes > 8) { set_error("nplanes %d", nplanes); return GFW_ERR_INVALID_ARGUMENT; }
-    for (int i = 0; i < nplanes; ++i)
-        if (pixel_types[i] < 0 || pixel_types[i] >= GFW_PIX_COUNT) { set_error("plane %d: unknown pixel type %d", i, pixel_types[i]); return GFW_ERR_INVALID_ARGUMENT; }
+    { const int prc = check_pixel_types(nplanes, pixel_types); if (prc != GFW_OK) return prc; }
     { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
     ClipBatch batch;
-    batch.n_call = n_frames;
-    batch.perframe = true;
-    // the first-pass table's envelope: the call knows every frame's fov and zoom centre, so the table is sized once for all of them (p1_setup)
+    clip_params_batch(batch, n_frames, nplanes, params);
     for (int f = 0; f < n_frames; ++f) {
-        double hx, hy;
-        p1_corner_extent(params[(size_t)f * nplanes], hx, hy);
-        batch.env_hx = fmax(batch.env_hx, hx); batch.env_hy = fmax(batch.env_hy, hy);
+        const int rc = run_planes(c, FrameIn{nplanes, planes + (size_t)f * nplanes, params + (size_t)f * nplanes, pixel_types, matrices[f], matrix_count, nullptr, 0}, &batch);
+        if (rc != GFW_OK) return clip_end(c, &batch, rc);
     }
-    for (int f = 0; f < n_frames; ++f) {
-        const int rc = run_planes(c, nplanes, planes + (size_t)f * nplanes, params + (size_t)f * nplanes, pixel_types, matrices[f], matrix_count, nullptr, 0, &batch);
-        if (rc != GFW_OK) { (void)clip_flush(c, &batch); if (c->synchronous) (void)hipStreamSynchronize(c->stream); return rc; }
-    }
-    const int frc = clip_flush(c, &batch);
-    if (c->synchronous) { const hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess && frc == GFW_OK) { set_error("hipStreamSynchronize failed: %s", hipGetErrorString(e)); return GFW_ERR_HIP; } }
-    return frc;
+    return clip_end(c, &batch, GFW_OK);
 }
 
 }  // extern "C"

@@ -8,6 +8,10 @@ static void bake_f(std::string &o, const char *name, float v) {
     uint32_t u; memcpy(&u, &v, 4);
     char b[128]; snprintf(b, sizeof(b), "#define GFW_BK_%s __builtin_bit_cast(float, 0x%08xu)\n", name, u); o += b;
 }
+static void split_defs(const char *text, std::vector<std::string> &defs) {             // a ';'-separated definition list, appended
+    std::string cur;
+    for (const char *p = text; ; ++p) { if (*p == ';' || *p == 0) { if (!cur.empty()) defs.push_back(cur); cur.clear(); if (!*p) break; } else cur += *p; }
+}
 static void bake_i(std::string &o, const char *name, long long v) { char b[128]; snprintf(b, sizeof(b), "#define GFW_BK_%s (%lld)\n", name, v); o += b; }
 // Luma block rows per lane of a SPECIALISED kernel (its tile = 64 DW x 4 RB DH luma pixels): the ahead-of-time kernels' by default; GFW_JIT_RB_FAST in the
 // environment scans it for the certified first pass (whose cost per pixel — the lattice's nodes, the queue's resolution — is per tile).
@@ -17,9 +21,9 @@ static int jit_rows(bool fast1) {
 }
 // perframe: the header of the per-frame flavour (GFW_JIT_PERFRAME, gfw_undistort_clip_params) — translation2d and FILL_WITH_BACKGROUND are not literals there (the
 // kernel reads them from each frame's slot), so they are left out: a use that slipped past the flavour would not compile.
-static std::string bake_header(const GfwYuvArgs &Y_in, bool fast1, bool perframe = false) {
+static std::string bake_header(const GfwYuvArgs &Y_in, const FusedShape &S, bool perframe = false) {
     GfwYuvArgs Y = Y_in;
-    { const int rb = jit_rows(fast1); Y.tiles_y = (Y.ch + 4 * rb - 1) / (4 * rb); }          // (the launch's own tiling: the argument block carries the ahead-of-time kernels')
+    Y.tiles_y = tiles_y_of(Y, jit_rows(S.fast1 != 0));                                       // (the launch's own tiling: the argument block carries the ahead-of-time kernels')
     std::string o;
     o.reserve(4096);
     bake_i(o, "nplanes", Y.nplanes); bake_i(o, "width", Y.width); bake_i(o, "height", Y.height); bake_i(o, "out_w", Y.out_w); bake_i(o, "out_h", Y.out_h);
@@ -67,13 +71,14 @@ static std::string bake_header(const GfwYuvArgs &Y_in, bool fast1, bool perframe
 // The generic-model body keeps the rule — the lens-correction blend too, although it spills a few dwords at eight waves (GoPro lens, blend 0.5:
 // 141.5 us at 6 waves, 139.2 at 7, 134.4 at 8; fisheye + blend 140.5 / 137.4 / 135.9) — except with background mode 3 or the Sony mesh (two
 // samples per pixel, f64 splines: up to 80 registers), which get six.
-static int jit_waves(int n0, int matrix_count, int jit_model, int extras, int taps, int bps, int dh, int checksum = 0) {
+static int jit_waves(const FusedShape &S, int matrix_count, int jit_model, int extras, int checksum = 0) {
+    const int n0 = S.n0, taps = S.taps, bps = S.kind;
     static const int forced = getenv("GFW_JIT_WAVES") ? atoi(getenv("GFW_JIT_WAVES")) : 0;      // experiments
     if (forced >= 1 && forced <= 8) return forced;
     // The checksum build (gfw_set_frame_checksums) keeps three more registers alive through the tile walk; at eight waves (64 registers) four dwords go to scratch, and
     // every build of this kernel with a private segment measured 4-10 % slower than its scratch-free twin (all waves resident, same instruction count: not occupancy —
     // profiles/r05_c5_checksum.txt): C5 46.4 us per frame at eight waves, 44.6 at seven — no scratch
-    if (checksum) { const int w = jit_waves(n0, matrix_count, jit_model, extras, taps, bps, dh, 0); return w == 8 ? 7 : w; }
+    if (checksum) { const int w = jit_waves(S, matrix_count, jit_model, extras, 0); return w == 8 ? 7 : w; }
     if (jit_model < 0 && (extras & (16 | 32))) return 6;
     // bicubic / Lanczos4 on single-channel integer planes: registers for the tap rows in flight are worth more than the seventh and eighth wave
     // (gfw_frame.hip GFW_TAP_ROW_UNROLL; profiles/r04_ab_lut_rows.txt).  Round 5: C2's bicubic (16-bit, full-height chroma) too — with the group-first row fetch the
@@ -82,29 +87,6 @@ static int jit_waves(int n0, int matrix_count, int jit_model, int extras, int ta
     if (n0 == 1 && bps <= 2 && taps == 4) return 6;
     if (n0 == 1 && bps <= 2 && taps == 8) return bps == 1 ? 5 : 6;
     return (n0 == 1 && matrix_count > 1) ? 8 : 7;
-}
-// The definition list of a specialised build (with the bake header: everything that names the kernel)
-static std::vector<std::string> jit_defs(const GfwYuvArgs &Y, int bps, int taps, int n0, int dw, int dh, bool interleaved, bool fast1, int jit_model, int waves, bool perframe = false) {
-    (void)Y;
-    char b[64];
-    std::vector<std::string> defs;
-    snprintf(b, sizeof(b), "GFW_FRAME_KIND=%d", bps); defs.push_back(b);
-    snprintf(b, sizeof(b), "GFW_FRAME_TAPS=%d", taps); defs.push_back(b);
-    snprintf(b, sizeof(b), "GFW_JIT_WAVES=%d", waves); defs.push_back(b);
-    snprintf(b, sizeof(b), "GFW_JIT_MODEL=%d", jit_model); defs.push_back(b);
-    defs.push_back(bps == 1 ? "GFW_JIT_T=uint8_t" : bps == 2 ? "GFW_JIT_T=uint16_t" : bps == 3 ? "GFW_JIT_T=_Float16" : "GFW_JIT_T=float");
-    snprintf(b, sizeof(b), "GFW_JIT_N0=%d", n0); defs.push_back(b);
-    snprintf(b, sizeof(b), "GFW_JIT_DW=%d", dw); defs.push_back(b);
-    snprintf(b, sizeof(b), "GFW_JIT_DH=%d", dh); defs.push_back(b);
-    snprintf(b, sizeof(b), "GFW_JIT_IL=%d", interleaved ? 1 : 0); defs.push_back(b);
-    snprintf(b, sizeof(b), "GFW_JIT_RB=%d", jit_rows(fast1)); defs.push_back(b);
-    snprintf(b, sizeof(b), "GFW_JIT_FAST1=%d", fast1 ? 1 : 0); defs.push_back(b);
-    if (perframe) defs.push_back("GFW_JIT_PERFRAME=1");                                   // (absent otherwise: the other flavours' definition lists — their cache names — are unchanged)
-    if (const char *extra = getenv("GFW_JIT_DEFS")) {                                    // experiments: further ';'-separated definitions for the build
-        std::string cur;
-        for (const char *p = extra; ; ++p) { if (*p == ';' || *p == 0) { if (!cur.empty()) defs.push_back(cur); cur.clear(); if (!*p) break; } else cur += *p; }
-    }
-    return defs;
 }
 static int jit_model_of(const GfwYuvArgs &Y) {
     return (Y.model == GFW_MODEL_OPENCV_FISHEYE && (Y.extras & ~2) == 0) ? GFW_MODEL_OPENCV_FISHEYE : ((Y.extras & (16 | 32)) ? -2 : -1);
@@ -115,14 +97,28 @@ static int jit_model_of(const GfwYuvArgs &Y) {
 static bool jit_audit_build(const gfw_ctx *c, const GfwYuvArgs &Y, bool perframe) {
     return Y.audit && (Y.p1_rform || perframe) && (c->kernel_variant == 3 || c->kernel_variant == 4);
 }
-// The definition list jit_for builds these arguments with (also behind gfw_debug_jit_key / gfw_debug_jit_key_clip_params); `waves` receives the budget
-static std::vector<std::string> jit_build_defs(const GfwYuvArgs &Y, int bps, int taps, int n0, int dw, int dh, bool interleaved, bool fast1, bool perframe, bool audit_build, int *waves_out) {
+// The definition list of a specialised build (with the bake header: everything that names the kernel; also behind the gfw_debug_jit_key hooks); `waves_out`: the budget
+static std::vector<std::string> jit_build_defs(const GfwYuvArgs &Y, const FusedShape &S, bool perframe, bool audit_build, int *waves_out) {
     const int jit_model = jit_model_of(Y);
-    int waves = jit_waves(n0, Y.matrix_count, jit_model, Y.extras, taps, bps, dh, Y.checksum);
+    int waves = jit_waves(S, Y.matrix_count, jit_model, Y.extras, Y.checksum);
     // (the per-frame flavour of the lens-correction body keeps one more value of the frame alive through the pixel loop: at eight waves 24 bytes went to scratch
     // on 4K NV12, so it gets seven — as the checksum build does; every other body keeps its constant build's waves: tests/test_kernel_resources_perframe.py)
     if (perframe && (Y.extras & 8) && waves == 8) waves = 7;
-    std::vector<std::string> defs = jit_defs(Y, bps, taps, n0, dw, dh, interleaved, fast1, jit_model, waves, perframe);
+    char b[64];
+    std::vector<std::string> defs;
+    snprintf(b, sizeof(b), "GFW_FRAME_KIND=%d", S.kind); defs.push_back(b);
+    snprintf(b, sizeof(b), "GFW_FRAME_TAPS=%d", S.taps); defs.push_back(b);
+    snprintf(b, sizeof(b), "GFW_JIT_WAVES=%d", waves); defs.push_back(b);
+    snprintf(b, sizeof(b), "GFW_JIT_MODEL=%d", jit_model); defs.push_back(b);
+    defs.push_back(S.kind == 1 ? "GFW_JIT_T=uint8_t" : S.kind == 2 ? "GFW_JIT_T=uint16_t" : S.kind == 3 ? "GFW_JIT_T=_Float16" : "GFW_JIT_T=float");
+    snprintf(b, sizeof(b), "GFW_JIT_N0=%d", S.n0); defs.push_back(b);
+    snprintf(b, sizeof(b), "GFW_JIT_DW=%d", S.dw); defs.push_back(b);
+    snprintf(b, sizeof(b), "GFW_JIT_DH=%d", S.dh); defs.push_back(b);
+    snprintf(b, sizeof(b), "GFW_JIT_IL=%d", S.interleaved ? 1 : 0); defs.push_back(b);
+    snprintf(b, sizeof(b), "GFW_JIT_RB=%d", jit_rows(S.fast1 != 0)); defs.push_back(b);
+    snprintf(b, sizeof(b), "GFW_JIT_FAST1=%d", S.fast1 ? 1 : 0); defs.push_back(b);
+    if (perframe) defs.push_back("GFW_JIT_PERFRAME=1");                                   // (absent otherwise: the other flavours' definition lists — their cache names — are unchanged)
+    if (const char *extra = getenv("GFW_JIT_DEFS")) split_defs(extra, defs);             // experiments: further ';'-separated definitions for the build
     if (audit_build) defs.push_back("GFW_JIT_AUDIT=1");
     if (waves_out) *waves_out = waves;
     return defs;
@@ -131,7 +127,7 @@ static std::vector<std::string> jit_build_defs(const GfwYuvArgs &Y, int bps, int
 // launches the ahead-of-time kernel.  perframe: the per-frame flavour (gfw_undistort_clip_params): its launches take GfwClipArgsPF (gfw_jit_launch_pf), and its
 // key blanks the fields the frames carry in their slots as well — translation2d and the fill flag here, fov / lens-correction amount / margin / feather with `kp` —
 // so that one kernel serves the clip and the kJitAfter count runs on under a moving zoom centre.
-static hipFunction_t jit_for(gfw_ctx *c, const GfwYuvArgs &Y, int bps, int taps, int n0, int dw, int dh, bool interleaved, bool fast1, int *grid, bool perframe = false) {
+static hipFunction_t jit_for(gfw_ctx *c, const GfwYuvArgs &Y, const FusedShape &S, bool perframe, int *grid) {
     // every frame the fused kernel serves can be specialised: the fisheye model alone or under a digital lens (extras 0 / 2) takes the lean
     // projection (MODEL = 1); everything else the generic-model body with the lens model, the digital lens and the feature bits as literals
     // (MODEL = -1, or -2 with background mode 3 / the Sony mesh) — the run-time switch over 14 lens models folds to the one in use
@@ -147,25 +143,24 @@ static hipFunction_t jit_for(gfw_ctx *c, const GfwYuvArgs &Y, int bps, int taps,
     memset(&K.kp, 0, sizeof(K.kp));
     { const int dig = K.common.digital; memset(&K.common, 0, sizeof(K.common)); K.common.digital = dig; }
     if (perframe) { K.t2[0] = K.t2[1] = 0.0f; K.fill_bg = 0; }
-    const int key_misc[9] = {bps, taps, n0, dw, dh, interleaved ? 1 : 0, fast1 ? 1 : 0, c->tune_grid, perframe ? 1 : 0};
-    const bool same = c->jit_key_valid && memcmp(&K, &c->jit_key, sizeof(K)) == 0 && memcmp(key_misc, c->jit_key_misc, sizeof(key_misc)) == 0;
+    const JitKeyMisc misc = {S, c->tune_grid, perframe ? 1 : 0};
+    const bool same = c->jit_key_valid && memcmp(&K, &c->jit_key, sizeof(K)) == 0 && memcmp(&misc, &c->jit_key_misc, sizeof(misc)) == 0;
     if (same) {
         if (c->jit_seen < (1 << 30)) ++c->jit_seen;
         if (c->jit_fn) { *grid = c->jit_grid; return c->jit_fn; }                        // ready and loaded: nothing else to do
         if (c->jit_dead) return nullptr;                                                 // decided: ahead of time for the rest of the clip, no lookup per frame
     } else {
-        c->jit_key = K; memcpy(c->jit_key_misc, key_misc, sizeof(key_misc)); c->jit_key_valid = true;
-        c->jit_header = bake_header(Y, fast1, perframe); c->jit_seen = 1; c->jit_fn = nullptr; c->jit_dead = false;
-        c->jit_info = GfwJitInfo{GFW_JIT_UNAVAILABLE, 0.0, std::string()};
+        jit_reset(c);
+        c->jit_key = K; c->jit_key_misc = misc; c->jit_key_valid = true;
+        c->jit_header = bake_header(Y, S, perframe); c->jit_seen = 1;
     }
     if (c->jit_mode == 1 && c->jit_seen < gfw_ctx::kJitAfter && !audit_build) return nullptr;          // one or two frames are not a clip
     int waves = 0;
-    const std::vector<std::string> defs = jit_build_defs(Y, bps, taps, n0, dw, dh, interleaved, fast1, perframe, audit_build, &waves);
+    const std::vector<std::string> defs = jit_build_defs(Y, S, perframe, audit_build, &waves);
     hipFunction_t fn = gfw_jit_get(c->device, c->arch, defs, c->jit_header, c->jit_mode == 2 || audit_build, &c->jit_info);
     if (!fn) { c->jit_dead = c->jit_info.state == GFW_JIT_FAILED || c->jit_info.state == GFW_JIT_UNAVAILABLE; return nullptr; }
     int g = c->tune_grid > 0 ? c->tune_grid : c->num_cus * waves;
-    const int jrb = jit_rows(fast1);
-    const int per_xcd = (Y.tiles_x * ((Y.ch + 4 * jrb - 1) / (4 * jrb)) + 7) >> 3;
+    const int per_xcd = (Y.tiles_x * tiles_y_of(Y, jit_rows(S.fast1 != 0)) + 7) >> 3;
     if (g > per_xcd * 8) g = per_xcd * 8;
     *grid = (g + 7) & ~7;
     c->jit_fn = fn; c->jit_grid = *grid;

@@ -50,12 +50,23 @@ static P1Derivs p1_s_derivs(double rho, const float *k) {
 }
 // The table lives in one buffer per context, d_p1_table.  Frames held for a clip launch (a ClipBatch: gfw_api_clip.inc) read it when that launch goes out, with the
 // range constants of the table they were set up against: a rebuild sends them on their way first (as ck_table does), and stream order puts the copy behind them.
-// `err` carries the error of that launch out of the functions below that answer with a bool.
+// The functions below return that launch's error — the frame's — or GFW_OK; whether there is a table, and a certified pass, they answer beside it.
 struct ClipBatch;
 static void clip_envelope(const ClipBatch *b, double &hx, double &hy);      // (gfw_api_clip.inc)
 static int clip_flush(gfw_ctx *c, ClipBatch *b);
-static int p1_prepare_table(gfw_ctx *c, const gfw_kernel_params &p, float rho_max, ClipBatch *pending, int &err) {
-    if (c->p1_valid && memcmp(c->p1_k, p.k, sizeof(c->p1_k)) == 0 && rho_max <= c->p1_rho_max && rho_max >= 0.5f * c->p1_rho_max) return GFW_OK;
+// A new table takes the buffer's place.  `moved`: it is there (always on a dry context, where there is no buffer); else the frame takes the exact first pass.
+static int p1_table_upload(gfw_ctx *c, const std::vector<float2> &tab, ClipBatch *pending, bool &moved) {
+    moved = c->dry;
+    if (c->dry) return GFW_OK;
+    { const int frc = clip_flush(c, pending); if (frc != GFW_OK) return frc; }      // (a pending launch names the table that is about to move)
+    const size_t bytes = (GFW_P1_TABLE_N + 1) * sizeof(float2);
+    moved = c->d_p1_table.ensure(bytes) == hipSuccess && hipMemcpyAsync(c->d_p1_table.ptr, tab.data(), bytes, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
+            hipStreamSynchronize(c->stream) == hipSuccess;                         // (`tab` is a stack-lifetime source)
+    return GFW_OK;
+}
+static int p1_prepare_table(gfw_ctx *c, const gfw_kernel_params &p, float rho_max, ClipBatch *pending, bool &ready) {      // ready: the context's table serves these coefficients and this range
+    ready = c->p1_valid && memcmp(c->p1_k, p.k, sizeof(c->p1_k)) == 0 && rho_max <= c->p1_rho_max && rho_max >= 0.5f * c->p1_rho_max;
+    if (ready) return GFW_OK;
     const int N = GFW_P1_TABLE_N;
     std::vector<float2> tab(N + 1);
     const double h = (double)rho_max / N;
@@ -115,16 +126,11 @@ static int p1_prepare_table(gfw_ctx *c, const gfw_kernel_params &p, float rho_ma
     // the entry s_{i+1} - s_i (u h |s'|, times a fraction <= 1); the fma that combines them is counted with the first pass's roundings (section 2c, item 4)
     const double etab = h * h / 8.0 * s2max + (smax + h * slope) / 16777216.0;
     if (!(etab == etab) || !(smax == smax) || !(slope == slope) || !(kappa == kappa) || !(t32 == t32)) { c->p1_valid = false; return GFW_OK; }
-    if (!c->dry) {
-        err = clip_flush(c, pending);                               // (a pending launch names the table that is about to move)
-        if (err != GFW_OK) return err;
-        HIP_TRY(c->d_p1_table.ensure((N + 1) * sizeof(float2)), GFW_ERR_HIP);
-        HIP_TRY(hipMemcpyAsync(c->d_p1_table.ptr, tab.data(), (N + 1) * sizeof(float2), hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
-        HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);      // `tab` is a stack-lifetime source
-    }
+    { bool moved; const int rc = p1_table_upload(c, tab, pending, moved); if (rc != GFW_OK || !moved) return rc; }
     memcpy(c->p1_k, p.k, sizeof(c->p1_k));
     c->p1_rho_max = rho_max; c->p1_etab = etab; c->p1_smax = smax; c->p1_slope = slope; c->p1_kappa = kappa; c->p1_valid = true;
     c->p1_u1 = u1; c->p1_u2 = u2; c->p1_t32 = t32;
+    ready = true;
     return GFW_OK;
 }
 // ---- radial models other than the fisheye (round 6): GoPro's inverted polynomial --------------------------------------------------------------------------------
@@ -192,7 +198,6 @@ static double p1_gopro_q(double theta, const double *k) {             // the roo
     return p;
 }
 static bool p1_prepare_radial_gopro(const gfw_kernel_params &p, double r_max, P1Radial &R, std::vector<float2> *tab_out) {
-    const int N = GFW_P1_TABLE_N;
     R.ok = false;
     double k[7]; for (int i = 0; i < 7; ++i) k[i] = (double)p.k[i];
     if (k[0] != 0.0 || !(k[1] > 1e-3) || !(r_max > 0.0) || r_max > 8.0) return false;          // (k0 != 0: r_norm does not vanish at the centre, T has a pole there)
@@ -302,35 +307,18 @@ static bool p1_model_radial_served(int model) {
     return model == GFW_MODEL_GOPRO || model == GFW_MODEL_SONY || model == GFW_MODEL_GENERIC_POLYNOMIAL || (all && p1_model_radial(model));
 }
 static void p1_radial_free(gfw_ctx *c) { delete c->p1_radial; c->p1_radial = nullptr; }
-// p1_setup for the radial models: the table over r, E = e0 + ew omega + em mu with the r form's coefficients.  With v = f c T(r) + c0, r = |(a, b)|, c = b (a):
-//   |dv/dc| <= f (Tmax + r_max T1), |dv/d(other)| <= f r_max T1, so the two paths' errors in a, b (u D each: DESIGN.md section 2c, items 1-2) move v by at most
-//   u G D, G = f (Tmax + 2 r_max T1);  the key — rho = fma(a, a, b b) (2u), the hardware's square root (1 ulp = 2u), the position's product (1u) — by 6 u f r_max^2 T1;
-//   the table by f r_max e_table per path's share (chord of an interval h under T2, the entries' and the fma's roundings); the last two products and the fma 3 u vmag;
-//   the EXACT path beyond its linear forms and divisions (in D): its r (2u), r_norm = k1 p (1u), the quotient, the product by pos, by f, the sum with c (5u vmag in
-//   all) and the Newton result itself, f nu2 (p1_prepare_radial_gopro).
-static bool p1_setup_radial(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_matrices, int matrix_count, double rho_max, bool hrs, GfwYuvArgs &Y, bool &table_ok,
-                            ClipBatch *pending, int &err) {
-    double r_need = sqrt(rho_max);
-    P1Radial *R = c->p1_radial;
-    if (!(R && R->ok && R->model == c->model && memcmp(R->k, p0.k, sizeof(R->k)) == 0 && r_need <= R->r_max && r_need >= 0.7 * R->r_max)) {
-        r_need = fmin(r_need * 1.08, 8.0);                       // head-room so that frame-to-frame motion does not rebuild the table
-        if (!R) R = c->p1_radial = new P1Radial();
-        std::vector<float2> tab;
-        R->model = c->model;
-        if (!p1_prepare_radial(c->model, p0, r_need, *R, &tab)) { R->ok = false; return false; }
-        if (!c->dry) {
-            err = clip_flush(c, pending);                           // (a pending launch names the table that is about to move)
-            if (err != GFW_OK) { R->ok = false; return false; }
-            if (c->d_p1_table.ensure((GFW_P1_TABLE_N + 1) * sizeof(float2)) != hipSuccess) { R->ok = false; return false; }
-            if (hipMemcpyAsync(c->d_p1_table.ptr, tab.data(), (GFW_P1_TABLE_N + 1) * sizeof(float2), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                hipStreamSynchronize(c->stream) != hipSuccess) { R->ok = false; return false; }      // (`tab` is a stack-lifetime source)
-        }
-    }
-    const double f = fabs((double)(hrs ? p0.f[0] : p0.f[1])), cc = fabs((double)(hrs ? p0.c[0] : p0.c[1]));
-    const double rmax = R->r_max, vmag = f * rmax * R->Tmax + cc, u24 = 1.05 / 16777216.0;
-    const double G = f * (R->Tmax + 2.0 * rmax * R->T1);
-    const double e0 = u24 * (G * 10.0 * rmax + 6.0 * f * rmax * rmax * R->T1 + 11.0 * vmag) + 2.0 * f * rmax * R->etab + 1.05 * f * R->nu2 + 1.0 / 16384.0;
-    const double ew = u24 * G * rmax, em = u24 * G;
+// Audit mode (GFW_OPT_KERNEL_VARIANT 3 / 4): the launch counts certificates and checks each one.  False: no counters, the frame takes the exact pass.
+static bool p1_attach_audit(gfw_ctx *c, GfwYuvArgs &Y) {
+    if (c->kernel_variant != 3 && c->kernel_variant != 4) return true;
+    if (c->dry) { Y.audit = &c->dry_audit; return true; }            // (gfw_debug_jit_key_clip_params: the key of the audit build, no device)
+    if (audit_counters(c) != hipSuccess) return false;
+    Y.audit = (unsigned long long *)c->d_audit.ptr;
+    return true;
+}
+// What p1_setup and p1_setup_radial end on, E = e[0] + e[1] omega + e[2] mu derived: the kernel evaluates omega, mu from the matrix it actually uses; the host's own
+// view of them — from the mid-row matrix, if it has one — only decides whether the certified pass is worth launching (the answer) and is what gfw_get_audit reports
+static bool p1_finish(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_matrices, int matrix_count, double rmax, const double e[3], GfwYuvArgs &Y) {
+    const bool hrs = (p0.flags & GFW_FLAG_HORIZONTAL_RS) != 0;
     double omega = 1.0, mu = 6.0 * (rmax + 1.0);
     if (h_matrices) {
         const float *m = h_matrices + (size_t)(matrix_count >> 1) * 14;
@@ -340,43 +328,60 @@ static bool p1_setup_radial(gfw_ctx *c, const gfw_kernel_params &p0, const float
         const double wden = fmax((double)m[8] - pw, fmax(1.0 / 1024.0, (pw + fabs(m[8])) / 8.0));
         omega = 3.0 * pw / wden; mu = 3.0 * fmax(px, py) / wden;
     }
-    const double eps = e0 + ew * omega + em * mu;
+    const double eps = e[0] + e[1] * omega + e[2] * mu;
     Y.p1_table = (const float2 *)c->d_p1_table.ptr;
+    Y.p1_eps = (float)e[0]; Y.p1_ew = (float)e[1]; Y.p1_em = (float)e[2];
+    c->p1_eps_last = (float)eps;
+    Y.p1_f = hrs ? p0.f[0] : p0.f[1]; Y.p1_c = hrs ? p0.c[0] : p0.c[1];
+    // a single matrix: no first pass to certify (the table still serves the second); a certificate that would reject most pixels: the exact pass
+    return p1_attach_audit(c, Y) && matrix_count > 1 && eps < 0.2;
+}
+// p1_setup for the radial models: the table over r, E = e0 + ew omega + em mu with the r form's coefficients.  With v = f c T(r) + c0, r = |(a, b)|, c = b (a):
+//   |dv/dc| <= f (Tmax + r_max T1), |dv/d(other)| <= f r_max T1, so the two paths' errors in a, b (u D each: DESIGN.md section 2c, items 1-2) move v by at most
+//   u G D, G = f (Tmax + 2 r_max T1);  the key — rho = fma(a, a, b b) (2u), the hardware's square root (1 ulp = 2u), the position's product (1u) — by 6 u f r_max^2 T1;
+//   the table by f r_max e_table per path's share (chord of an interval h under T2, the entries' and the fma's roundings); the last two products and the fma 3 u vmag;
+//   the EXACT path beyond its linear forms and divisions (in D): its r (2u), r_norm = k1 p (1u), the quotient, the product by pos, by f, the sum with c (5u vmag in
+//   all) and the Newton result itself, f nu2 (p1_prepare_radial_gopro).
+static int p1_setup_radial(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_matrices, int matrix_count, double rho_max, ClipBatch *pending, GfwYuvArgs &Y, bool &fast1) {
+    const bool hrs = (p0.flags & GFW_FLAG_HORIZONTAL_RS) != 0;
+    double r_need = sqrt(rho_max);
+    P1Radial *R = c->p1_radial;
+    if (!(R && R->ok && R->model == c->model && memcmp(R->k, p0.k, sizeof(R->k)) == 0 && r_need <= R->r_max && r_need >= 0.7 * R->r_max)) {
+        r_need = fmin(r_need * 1.08, 8.0);                       // head-room so that frame-to-frame motion does not rebuild the table
+        if (!R) R = c->p1_radial = new P1Radial();
+        std::vector<float2> tab;
+        R->model = c->model;
+        if (!p1_prepare_radial(c->model, p0, r_need, *R, &tab)) { R->ok = false; return GFW_OK; }
+        { bool moved; const int rc = p1_table_upload(c, tab, pending, moved); if (rc != GFW_OK || !moved) { R->ok = false; return rc; } }
+    }
+    const double f = fabs((double)(hrs ? p0.f[0] : p0.f[1])), cc = fabs((double)(hrs ? p0.c[0] : p0.c[1]));
+    const double rmax = R->r_max, vmag = f * rmax * R->Tmax + cc, u24 = 1.05 / 16777216.0;
+    const double G = f * (R->Tmax + 2.0 * rmax * R->T1);
+    const double e0 = u24 * (G * 10.0 * rmax + 6.0 * f * rmax * rmax * R->T1 + 11.0 * vmag) + 2.0 * f * rmax * R->etab + 1.05 * f * R->nu2 + 1.0 / 16384.0;
+    const double e[3] = {e0, u24 * G * rmax, u24 * G};
     Y.p1_rho_max = (float)(rmax * rmax * (1.0 - 1e-6)); Y.p1_kmax = (float)rmax; Y.p1_rho_scale = (float)(GFW_P1_TABLE_N / rmax); Y.p1_rform = 1;
-    Y.p1_eps = (float)e0; Y.p1_ew = (float)ew; Y.p1_em = (float)em;
     Y.p1_lat[0] = (float)(R->Tmax * (1.0 + 1e-6)); Y.p1_lat[1] = (float)(0.5 * R->T1 * (1.0 + 1e-6)); Y.p1_lat[2] = (float)(0.5 * rmax * R->T1 * (1.0 + 1e-6));
     Y.p1_lat[3] = (float)(0.25 * (rmax * R->T2 + R->T1) * (1.0 + 1e-6)); Y.p1_lat[4] = (float)(4.0 * u24 * vmag + 1.0 / 131072.0);
     Y.p1_lat[5] = 1.0f;                                          // the per-pixel form (header comment of p1_prepare_radial_gopro)
-    c->p1_eps_last = (float)eps;
-    Y.p1_f = hrs ? p0.f[0] : p0.f[1]; Y.p1_c = hrs ? p0.c[0] : p0.c[1];
-    table_ok = true;
-    if ((c->kernel_variant == 3 || c->kernel_variant == 4) && c->dry) Y.audit = &c->dry_audit;      // (gfw_debug_jit_key_clip_params: the key of the audit build, no device)
-    else if (c->kernel_variant == 3 || c->kernel_variant == 4) {     // audit mode: count certificates and check each one (a specialised audit build: gfw_api_bake.inc)
-        const bool fresh = c->d_audit.cap == 0;
-        if (c->d_audit.ensure(8 * sizeof(unsigned long long)) != hipSuccess) { table_ok = false; return false; }
-        if (fresh) (void)hipMemsetAsync(c->d_audit.ptr, 0, 8 * sizeof(unsigned long long), c->stream);
-        Y.audit = (unsigned long long *)c->d_audit.ptr;
-    }
-    if (matrix_count <= 1) return false;
-    if (!(eps < 0.2)) return false;
-    return true;
+    fast1 = p1_finish(c, p0, h_matrices, matrix_count, rmax, e, Y);      // (its audit is a specialised audit build: gfw_api_bake.inc)
+    return GFW_OK;
 }
-// Fill the first-pass fields of the fused kernel's arguments; returns true when the certified pass may be used.
 // The half-extents of the output frame's corner ray in normalised camera coordinates (new_k = f / fov, frame_transform.rs:37-51; the zoom centre moves it by
 // translation2d) — the first pass's range estimate for device-resident tables
 static void p1_corner_extent(const gfw_kernel_params &p0, double &hx, double &hy) {
     hx = 0.5 * p0.output_width * (double)p0.fov / fmax(fabs((double)p0.f[0]), 1e-6) + fabs((double)p0.translation2d[0]) * (double)p0.fov / fmax(fabs((double)p0.f[0]), 1e-6);
     hy = 0.5 * p0.output_height * (double)p0.fov / fmax(fabs((double)p0.f[1]), 1e-6) + fabs((double)p0.translation2d[1]) * (double)p0.fov / fmax(fabs((double)p0.f[1]), 1e-6);
 }
-static bool p1_setup(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_matrices, int matrix_count, GfwYuvArgs &Y, bool &table_ok, ClipBatch *pending, int &err) {
-    Y.p1_table = nullptr; Y.audit = nullptr; table_ok = false;
-    if (c->kernel_variant == 2) return false;                   // forced exact first pass (tests / A-B benchmarking)
+// Fill the first-pass fields of the fused kernel's arguments.  `fast1`: the certified pass may be used (false on every early return: the exact first pass).
+static int p1_setup(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_matrices, int matrix_count, ClipBatch *pending, GfwYuvArgs &Y, bool &fast1) {
+    Y.p1_table = nullptr; Y.audit = nullptr; fast1 = false;
+    if (c->kernel_variant == 2) return GFW_OK;                  // forced exact first pass (tests / A-B benchmarking)
     const bool radial = p1_model_radial_served(c->model);       // (round 6) GoPro, Sony, generic polynomial: certified through a table over r, in specialised builds only
-    if ((c->model != GFW_MODEL_OPENCV_FISHEYE && !radial) || Y.hstretch_div || Y.vstretch_div) return false;
-    if (radial && c->jit_mode == 0) return false;
+    if ((c->model != GFW_MODEL_OPENCV_FISHEYE && !radial) || Y.hstretch_div || Y.vstretch_div) return GFW_OK;
+    if (radial && c->jit_mode == 0) return GFW_OK;
     if (radial) {                                               // GFW_P1_RADIAL=0 in the environment: the exact first pass for these models (A/B runs)
         static const bool env_off = [] { const char *e = getenv("GFW_P1_RADIAL"); return e && e[0] == '0' && e[1] == 0; }();
-        if (env_off) return false;
+        if (env_off) return GFW_OK;
     }
     const bool hrs = (p0.flags & GFW_FLAG_HORIZONTAL_RS) != 0;
     // rho range over the output frame under the mid-row matrix (corners + edge midpoints), in double
@@ -401,12 +406,12 @@ static bool p1_setup(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_mat
         const double ang = atan(sqrt(hx * hx + hy * hy)) + 0.26;
         rho_max = ang < 1.45 ? tan(ang) * tan(ang) : 64.0;
     }
-    if (!(rho_max == rho_max)) return false;
+    if (!(rho_max == rho_max)) return GFW_OK;
     if (rho_max > 64.0) rho_max = 64.0;
-    if (radial) return p1_setup_radial(c, p0, h_matrices, matrix_count, rho_max, hrs, Y, table_ok, pending, err);
+    if (radial) return p1_setup_radial(c, p0, h_matrices, matrix_count, rho_max, pending, Y, fast1);
     if (!(c->p1_valid && memcmp(c->p1_k, p0.k, sizeof(c->p1_k)) == 0 && rho_max <= c->p1_rho_max && rho_max >= 0.5 * c->p1_rho_max))
         rho_max = fmin(rho_max * 1.15, 64.0);                   // head-room so that frame-to-frame motion does not rebuild the table
-    if (p1_prepare_table(c, p0, (float)rho_max, pending, err) != GFW_OK || !c->p1_valid) return false;
+    { bool ready; const int rc = p1_prepare_table(c, p0, (float)rho_max, pending, ready); if (rc != GFW_OK || !ready) return rc; }
     const double f = fabs((double)(hrs ? p0.f[0] : p0.f[1])), cc = fabs((double)(hrs ? p0.c[0] : p0.c[1]));
     const double rmax = sqrt((double)c->p1_rho_max);
     const double vmag = f * rmax * c->p1_smax + cc;
@@ -419,41 +424,17 @@ static bool p1_setup(gfw_ctx *c, const gfw_kernel_params &p0, const float *h_mat
     const double G = f * c->p1_smax + 2.0 * M_SQRT2 * f * rmax * rmax * c->p1_slope;
     const double e0 = u24 * (G * 10.0 * rmax + 6.0 * f * rmax * (double)c->p1_rho_max * c->p1_slope + f * rmax * c->p1_smax * (c->p1_kappa + 4.0) + 2.0 * vmag)
                     + 2.0 * f * rmax * c->p1_etab + 1.0 / 16384.0;
-    const double ew = u24 * G * rmax, em = u24 * G;
-    // the host's own view of omega, mu (only to decide whether the certified pass is worth launching and to report E; the kernel's value decides)
-    double omega = 1.0, mu = 6.0 * (rmax + 1.0);
-    if (h_matrices) {
-        const float *m = h_matrices + (size_t)(matrix_count >> 1) * 14;
-        const double x0 = p0.translation2d[0], x1 = x0 + p0.output_width, y0 = p0.translation2d[1], y1 = y0 + p0.output_height;
-        const double ax = fmax(fabs(x0), fabs(x1)), ay = fmax(fabs(y0), fabs(y1));
-        const double px = ax * fabs(m[0]) + ay * fabs(m[1]), py = ax * fabs(m[3]) + ay * fabs(m[4]), pw = ax * fabs(m[6]) + ay * fabs(m[7]);
-        const double wden = fmax((double)m[8] - pw, fmax(1.0 / 1024.0, (pw + fabs(m[8])) / 8.0));
-        omega = 3.0 * pw / wden; mu = 3.0 * fmax(px, py) / wden;
-    }
-    const double eps = e0 + ew * omega + em * mu;
-    Y.p1_table = (const float2 *)c->d_p1_table.ptr;
+    const double e[3] = {e0, u24 * G * rmax, u24 * G};
     Y.p1_rho_max = c->p1_rho_max; Y.p1_rho_scale = (float)(GFW_P1_TABLE_N / (double)c->p1_rho_max); Y.p1_kmax = c->p1_rho_max; Y.p1_rform = 0;
-    Y.p1_eps = (float)e0; Y.p1_ew = (float)ew; Y.p1_em = (float)em;
     // the lattice form of the first pass (gfw_frame.hip, phase 1): bounds on s and its derivatives for the curvature of v across a cell, and the roundings of the
     // interpolation itself (node differences, three fmas, the row fraction: < 4 u vmag; 2^-17 px on top)
     Y.p1_lat[0] = (float)(c->p1_smax * (1.0 + 1e-6)); Y.p1_lat[1] = (float)(c->p1_u1 * (1.0 + 1e-6)); Y.p1_lat[2] = (float)(c->p1_u2 * (1.0 + 1e-6));
     Y.p1_lat[3] = (float)(c->p1_t32 * (1.0 + 1e-6)); Y.p1_lat[4] = (float)(4.0 * u24 * vmag + 1.0 / 131072.0); Y.p1_lat[5] = 0.0f;
-    c->p1_eps_last = (float)eps;
-    Y.p1_f = hrs ? p0.f[0] : p0.f[1]; Y.p1_c = hrs ? p0.c[0] : p0.c[1];
-    table_ok = true;
     {   // the per-pixel form of the first pass on request: GFW_OPT_KERNEL_VARIANT = 4 (audit of that form) or GFW_P1_LATTICE=0 in the environment (A/B runs)
         static const bool env_off = [] { const char *e = getenv("GFW_P1_LATTICE"); return e && e[0] == '0' && e[1] == 0; }();
         if (c->kernel_variant == 4 || env_off) Y.p1_lat[5] = 1.0f;
     }
-    if ((c->kernel_variant == 3 || c->kernel_variant == 4) && c->dry) Y.audit = &c->dry_audit;      // (gfw_debug_jit_key_clip_params: the key of the audit build, no device)
-    else if (c->kernel_variant == 3 || c->kernel_variant == 4) {     // audit mode: count certificates and check each one
-        const bool fresh = c->d_audit.cap == 0;
-        if (c->d_audit.ensure(8 * sizeof(unsigned long long)) != hipSuccess) { table_ok = false; return false; }
-        if (fresh) (void)hipMemsetAsync(c->d_audit.ptr, 0, 8 * sizeof(unsigned long long), c->stream);
-        Y.audit = (unsigned long long *)c->d_audit.ptr;
-    }
-    if (matrix_count <= 1) return false;                        // a single matrix: no first pass to certify (the table still serves the second)
-    if (!(eps < 0.2)) return false;                             // certificate would reject most pixels: use the exact pass
-    return true;
+    fast1 = p1_finish(c, p0, h_matrices, matrix_count, rmax, e, Y);
+    return GFW_OK;
 }
 

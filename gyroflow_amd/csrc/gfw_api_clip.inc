@@ -23,6 +23,23 @@ struct ClipBatch {
 static void clip_envelope(const ClipBatch *b, double &hx, double &hy) {
     if (b && b->perframe) { hx = fmax(hx, b->env_hx); hy = fmax(hy, b->env_hy); }
 }
+// The batch of a gfw_undistort_clip_params call (and of gfw_debug_jit_key_clip_params, which answers what that call would launch): the per-frame flavour, and the
+// first-pass table's envelope — the call knows every frame's fov and zoom centre, so the table is sized once for all of them (p1_setup)
+static void clip_params_batch(ClipBatch &b, int n_frames, int nplanes, const gfw_kernel_params *params) {
+    b.n_call = n_frames; b.perframe = true;
+    for (int f = 0; f < n_frames; ++f) {
+        double hx, hy;
+        p1_corner_extent(params[(size_t)f * nplanes], hx, hy);
+        b.env_hx = fmax(b.env_hx, hx); b.env_hy = fmax(b.env_hy, hy);
+    }
+}
+// What a launch takes of each frame — its planes' pointers and its matrix table —, from the frame's own argument block
+static GfwFrameDyn frame_dyn(const GfwYuvArgs &Y) {
+    GfwFrameDyn F;
+    for (int i = 0; i < 4; ++i) { F.src[i] = Y.pl[i].src; F.dst[i] = Y.pl[i].dst; }
+    F.matrices = Y.matrices;
+    return F;
+}
 // A frame's slot of a per-frame launch: what FrameTransform::at_timestamp and the render loop move from frame to frame (DESIGN.md section 3.2a)
 static GfwFramePer frame_slot(const GfwYuvArgs &Y) {
     GfwFramePer F;
@@ -144,22 +161,43 @@ static void timeline_dump(gfw_ctx *c, hipFunction_t fn) {
             if (FILE *f = fopen((std::string(tl_file) + ".blocks").c_str(), "wb")) { fwrite(host.data(), 8, host.size(), f); fclose(f); }
     }
 }
+// One launch of the specialised kernel (the profile bracket is the caller's).  `pf`: the frames' slots (per-frame flavour) or nullptr; `sums`: used under CA.Y.checksum
+static int jit_launch(gfw_ctx *c, hipFunction_t fn, int grid, const GfwClipArgs &CA, const GfwFramePer *pf, unsigned long long *const *sums) {
+    hipError_t e;
+    if (pf) {
+        GfwClipArgsPF PF;
+        PF.C = CA; memset(PF.fr_pf, 0, sizeof(PF.fr_pf)); memcpy(PF.fr_pf, pf, (size_t)CA.n_frames * sizeof(GfwFramePer));
+        e = gfw_jit_launch_pf(fn, PF, grid, c->stream);
+    } else e = gfw_jit_launch(fn, CA, grid, c->stream);
+    int rc = (e == hipSuccess && CA.Y.checksum) ? ck_finish(c, CA, grid, sums) : GFW_OK;
+    if (e != hipSuccess) { set_error("clip launch failed: %s", hipGetErrorString(e)); rc = GFW_ERR_HIP; }
+    timeline_dump(c, fn);
+    return rc;
+}
 static int clip_flush(gfw_ctx *c, ClipBatch *b) {
     if (!b || b->n == 0) return GFW_OK;
     b->CA.n_frames = b->n; b->CA.pad_ = 0;
     prof_begin(c);
-    hipError_t e;
-    if (b->perframe) {
-        GfwClipArgsPF PF;
-        PF.C = b->CA;
-        memcpy(PF.fr_pf, b->pf, sizeof(PF.fr_pf));
-        e = gfw_jit_launch_pf(b->fn, PF, b->grid, c->stream);
-    } else e = gfw_jit_launch(b->fn, b->CA, b->grid, c->stream);
-    int crc = GFW_OK;
-    if (e == hipSuccess && b->CA.Y.checksum) crc = ck_finish(c, b->CA, b->grid, b->sums);
+    const int rc = jit_launch(c, b->fn, b->grid, b->CA, b->perframe ? b->pf : nullptr, b->sums);
     prof_end(c, b->n);
-    timeline_dump(c, b->fn);
     b->n = 0;
-    if (e != hipSuccess) { set_error("clip launch failed: %s", hipGetErrorString(e)); return GFW_ERR_HIP; }
-    return crc;
+    return rc;
+}
+// A frame joins the pending launch (opened by run_planes: join_launch): its pointers, its slot in the per-frame flavour, its checksum word.  A full launch leaves.
+static int clip_append(gfw_ctx *c, ClipBatch *b, const GfwFrameDyn &D, const GfwFramePer *slot, unsigned long long *sum) {
+    b->sums[b->n] = sum;
+    sum_commit(c, sum);                               // the frame is part of the pending launch from here on
+    if (slot) b->pf[b->n] = *slot;
+    b->CA.fr[b->n++] = D;
+    c->last_backend = b->backend;
+    return b->n >= b->limit ? clip_flush(c, b) : GFW_OK;
+}
+// The end of a clip call, after a frame's error (`rc`: reported whatever else happens) or after the last frame: what is pending leaves, and GFW_OPT_SYNCHRONOUS
+// means what it means for gfw_undistort_frame — a frame that joined a clip launch left run_planes before its own synchronisation point (round-3 advisor finding)
+static int clip_end(gfw_ctx *c, ClipBatch *b, int rc) {
+    const int frc = clip_flush(c, b);
+    const hipError_t e = c->synchronous ? hipStreamSynchronize(c->stream) : hipSuccess;
+    if (rc != GFW_OK) return rc;
+    if (e != hipSuccess && frc == GFW_OK) { set_error("hipStreamSynchronize failed: %s", hipGetErrorString(e)); return GFW_ERR_HIP; }
+    return frc;
 }

@@ -136,15 +136,16 @@ static int group_launch(PlaneGroup *g, GroupLock &lk) {
     if (!g->matrices_on_device) { h_matrices.swap(g->h_matrices); mats = h_matrices.data(); }
     g->n = 0;
     g = nullptr;
+    const FrameIn F = {n, planes, params, types, mats, matrix_count, nullptr, 0};
     int rc;
     {
         GroupUnlocked u(lk);
         if (hold_frames) {
-            rc = run_planes(owner, n, planes, params, types, mats, matrix_count, nullptr, 0, owner->held);
+            rc = run_planes(owner, F, owner->held);
             if (rc != GFW_OK || owner->held->n >= owner->coalesce_frames) { const int frc = owner->held->n > 0 ? clip_flush_on(owner) : GFW_OK; if (rc == GFW_OK) rc = frc; }
         } else {
             rc = (owner->held && owner->held->n > 0) ? clip_flush_on(owner) : GFW_OK;      // (frames parked earlier leave first: the calls are ordered)
-            if (rc == GFW_OK) rc = run_planes(owner, n, planes, params, types, mats, matrix_count, nullptr, 0);
+            if (rc == GFW_OK) rc = run_planes(owner, F);
         }
     }
     if (!(owner->held && owner->held->n > 0)) { const int orc = order_members_behind(owner); if (rc == GFW_OK) rc = orc; }

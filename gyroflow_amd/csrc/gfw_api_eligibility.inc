@@ -1,10 +1,12 @@
 // gfw_api_eligibility.inc — which frames the fused kernel serves, and its argument block (included by gfw_api.hip: one translation unit)
 // Decide whether the frame qualifies for the fused YUV kernel and, if so, build its argument block.
 // Anything not proven here runs through the generic per-plane kernel (same results, slower).
-// `pending`: the frames held for a clip launch on this context, sent first if the first pass's table has to be rebuilt; `err` is that launch's error (else GFW_OK).
-static bool build_yuv_args(gfw_ctx *c, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params, const int *pixel_types,
-                           const GfwPlane *launches, const float *h_matrices, int matrix_count, size_t mesh_len,
-                           GfwYuvArgs &Y, int &bytes_per_sample, int &n0, int &dw, int &dh, bool &interleaved, bool &fast1, ClipBatch *pending, int &err) {
+// fused_eligible answers from the frame's description alone (no device work): true with Y and S filled but for the first pass and the tiling.
+static bool fused_eligible(const gfw_ctx *c, const FrameIn &F, const GfwPlane *launches, const float *h_matrices, GfwYuvArgs &Y, FusedShape &S) {
+    const int nplanes = F.nplanes, matrix_count = F.matrix_count, *pixel_types = F.pixel_types; const size_t mesh_len = F.mesh_len;
+    const gfw_buffers *planes = F.planes; const gfw_kernel_params *params = F.params;
+    S = FusedShape();
+    int &bytes_per_sample = S.kind, &n0 = S.n0, &dw = S.dw, &dh = S.dh, &interleaved = S.interleaved;
     if (c->kernel_variant == 1) return false;                       // forced generic (tests / A-B benchmarking)
     if (nplanes < 1 || nplanes > 4) return false;
     const gfw_kernel_params &p0 = params[0];
@@ -26,10 +28,10 @@ static bool build_yuv_args(gfw_ctx *c, int nplanes, const gfw_buffers *planes, c
     default: return false;
     }
     if (n0 > 1 && nplanes != 1) return false;
-    interleaved = false;
+    interleaved = 0;
     if (nplanes >= 2) {
         const int t1 = pixel_types[1];
-        if (bytes_per_sample != 4 && t1 == (bytes_per_sample == 1 ? GFW_PIX_UV8 : GFW_PIX_UV16)) { if (nplanes != 2) return false; interleaved = true; }
+        if (bytes_per_sample != 4 && t1 == (bytes_per_sample == 1 ? GFW_PIX_UV8 : GFW_PIX_UV16)) { if (nplanes != 2) return false; interleaved = 1; }
         else { for (int i = 1; i < nplanes; ++i) if (pixel_types[i] != t0) return false; }
     }
     int extras = 0;
@@ -184,10 +186,22 @@ static bool build_yuv_args(gfw_ctx *c, int nplanes, const gfw_buffers *planes, c
     Y.kp = p0;
     Y.grid_limit = c->tune_grid > 0 ? c->tune_grid : c->num_cus * 6;
     Y.ablate = 0;                                                             // (reserved: the timing ablations live in GFW_TESTING builds of the kernel source only, gfw_frame.hip)
-    bool table_ok = false;
-    fast1 = (extras || p0.output_width > 65535 || p0.output_height > 65535) ? false : p1_setup(c, p0, h_matrices, matrix_count, Y, table_ok, pending, err);   // deferred pixels are parked as (x | y << 16)
-    const int rb = gfw_yuv_rows_per_lane(fast1, Y.audit ? 0 : c->tune_rb);
-    Y.tiles_x = (Y.cw + 63) / 64; Y.tiles_y = (Y.ch + 4 * rb - 1) / (4 * rb);
+    S.taps = p0.interpolation;
     return true;
+}
+static int tiles_y_of(const GfwYuvArgs &Y, int rb) { return (Y.ch + 4 * rb - 1) / (4 * rb); }      // rows of tiles: each 4 x rb rows of the chroma height
+// `pending`: the frames held for a clip launch on this context, sent first if the first pass's table has to be rebuilt (the error returned is that launch's)
+static int build_yuv_args(gfw_ctx *c, const FrameIn &F, const GfwPlane *launches, ClipBatch *pending, GfwYuvArgs &Y, FusedShape &S, bool &served) {
+    const float *h_matrices = c->matrices_on_device ? nullptr : F.matrices;
+    served = fused_eligible(c, F, launches, h_matrices, Y, S);
+    if (!served) return GFW_OK;
+    const gfw_kernel_params &p0 = F.params[0];
+    bool fast1 = false;
+    if (!Y.extras && p0.output_width <= 65535 && p0.output_height <= 65535) {               // deferred pixels are parked as (x | y << 16)
+        const int rc = p1_setup(c, p0, h_matrices, F.matrix_count, pending, Y, fast1); if (rc != GFW_OK) return rc;
+    }
+    S.fast1 = fast1 ? 1 : 0;
+    Y.tiles_x = (Y.cw + 63) / 64; Y.tiles_y = tiles_y_of(Y, gfw_yuv_rows_per_lane(fast1, Y.audit ? 0 : c->tune_rb));
+    return GFW_OK;
 }
 

@@ -2,13 +2,13 @@
 // the specialisation path, the shipped-cache key, gfw_checksum64 / gfw_set_frame_checksums, gfw_pack_matrices).  Split out of gfw_api.hip in round 6.
 
 // ------------------------------------------------------------------------------------------------ test hooks
+struct Release3 { DevBuf &x, &y, &z; ~Release3() { x.release(); y.release(); z.release(); } };      // (released on every path)
 extern "C" {
 int gfw_debug_math(int op, const float *a, const float *b, float *out, size_t n) {
     if (!a || !out || n == 0) { set_error("null/empty arrays"); return GFW_ERR_INVALID_ARGUMENT; }
     if (device_count() == 0) { set_error("no HIP device visible"); return GFW_ERR_NO_DEVICE; }
     HIP_TRY(hipSetDevice(g_current_device), GFW_ERR_HIP);
-    DevBuf da, db, dout;                                   // released on every path
-    struct Release { DevBuf &x, &y, &z; ~Release() { x.release(); y.release(); z.release(); } } release{da, db, dout};
+    DevBuf da, db, dout; Release3 release{da, db, dout};
     HIP_TRY(da.ensure(n * sizeof(float)), GFW_ERR_HIP);
     HIP_TRY(dout.ensure(n * sizeof(float)), GFW_ERR_HIP);
     if (b) HIP_TRY(db.ensure(n * sizeof(float)), GFW_ERR_HIP);
@@ -22,8 +22,7 @@ long long gfw_debug_selftest(int test, unsigned long long n, unsigned long long 
     if (device_count() == 0) { set_error("no HIP device visible"); return GFW_ERR_NO_DEVICE; }
     HIP_TRY(hipSetDevice(g_current_device), GFW_ERR_HIP);
     if (test == 2 && n == 0) n = 1ull << 31;
-    DevBuf dbad, none1, none2;
-    struct Release { DevBuf &x, &y, &z; ~Release() { x.release(); y.release(); z.release(); } } release{dbad, none1, none2};
+    DevBuf dbad, none1, none2; Release3 release{dbad, none1, none2};
     unsigned long long bad = 0;
     HIP_TRY(dbad.ensure(sizeof(bad)), GFW_ERR_HIP);
     HIP_TRY(hipMemset(dbad.ptr, 0, sizeof(bad)), GFW_ERR_HIP);
@@ -33,19 +32,12 @@ long long gfw_debug_selftest(int test, unsigned long long n, unsigned long long 
 }
 }
 
-// Verification helper of the frame-sharded clip run (SURVEY.md section 8e: "8 B checksum per frame"): adds the sum of the
-// buffer's u64 words (mod 2^64) to *d_out, in order on the context's stream.  `bytes` must be a multiple of 8 and the
-// buffer 16-byte aligned; d_out is a device pointer the caller zeroed.
 // Host-side build check of the run-time specialisation path (no device involved): compiles the embedded kernel source for `arch`
 // with the given ';'-separated -D definitions and bake header; returns the code object's size (optionally written to `out_path`).
 extern "C" long gfw_debug_jit_compile(const char *arch, const char *defines, const char *bake_header_text, const char *out_path, char *log, size_t cap) {
     if (!arch || !defines || !bake_header_text) return GFW_ERR_INVALID_ARGUMENT;
     std::vector<std::string> defs;
-    std::string cur;
-    for (const char *p = defines; ; ++p) {
-        if (*p == ';' || *p == 0) { if (!cur.empty()) defs.push_back(cur); cur.clear(); if (!*p) break; }
-        else cur += *p;
-    }
+    split_defs(defines, defs);
     std::string lg;
     std::vector<char> code;
     const long n = gfw_jit_compile_only(arch, defs, bake_header_text, lg, &code);
@@ -83,6 +75,21 @@ static int jit_key_out(const char *arch, const std::vector<std::string> &defs, c
     return GFW_OK;
 }
 
+// What run_planes would derive for frame 0 of the n_frames x F.nplanes planes in F.planes / F.params, each validated first, on a dry context: nothing touches a device
+static int dry_fused_args(gfw_ctx &c, int n_frames, const FrameIn &F, ClipBatch *batch, GfwYuvArgs &Y, FusedShape &S) {
+    { const int rc = check_pixel_types(F.nplanes, F.pixel_types); if (rc != GFW_OK) return rc; }
+    for (int j = 0; j < n_frames * F.nplanes; ++j) { const int rc = validate_plane(&F.planes[j], &F.params[j], F.pixel_types[j % F.nplanes]); if (rc != GFW_OK) return rc; }
+    c.dry = true;
+    GfwPlane launches[4];
+    memset(launches, 0, sizeof(launches));
+    for (int i = 0; i < F.nplanes; ++i) { launches[i].src = (const uint8_t *)F.planes[i].input.data; launches[i].dst = (uint8_t *)F.planes[i].output.data; }
+    bool served = false;
+    { const int rc = build_yuv_args(&c, F, launches, batch, Y, S, served); if (rc != GFW_OK) return rc; }
+    if (!served) { set_error("not a frame the fused kernel serves"); return GFW_ERR_UNSUPPORTED_BUFFER; }
+    fill_common(&c, &F.params[0], nullptr, nullptr, 0, Y.common);
+    return GFW_OK;
+}
+
 // Build-time helper of the shipped kernel cache (tools/build_jit_cache.py; no device involved): what the library WOULD specialise a frame of these planes to —
 // the ';'-separated definition list, the bake header and the cache file name of the kernel (gfw_jit.hip) — exactly as run_planes / jit_for derive them on a
 // device, with `matrices_on_device` as the context option would be set (2: device-resident tables, the first pass's table range from the intrinsics).
@@ -90,23 +97,11 @@ extern "C" int gfw_debug_jit_key(int nplanes, const gfw_buffers *planes, const g
                                  const float *h_matrices, int matrix_count, int matrices_on_device, const char *arch,
                                  char *defs_out, size_t defs_cap, char *header_out, size_t header_cap, char *name_out, size_t name_cap) {
     if (!planes || !params || !pixel_types || !arch || nplanes < 1 || nplanes > 4) { set_error("bad arguments"); return GFW_ERR_INVALID_ARGUMENT; }
-    for (int i = 0; i < nplanes; ++i) {
-        if (pixel_types[i] < 0 || pixel_types[i] >= GFW_PIX_COUNT) { set_error("plane %d: unknown pixel type", i); return GFW_ERR_INVALID_ARGUMENT; }
-        const int rc = validate_plane(&planes[i], &params[i], pixel_types[i]);
-        if (rc != GFW_OK) return rc;
-    }
     gfw_ctx c;
-    c.dry = true; c.model = distortion_model; c.digital = digital_lens; c.matrices_on_device = matrices_on_device; c.arch = arch;
-    GfwPlane launches[4];
-    memset(launches, 0, sizeof(launches));
-    for (int i = 0; i < nplanes; ++i) { launches[i].src = (const uint8_t *)planes[i].input.data; launches[i].dst = (uint8_t *)planes[i].output.data; }
-    GfwYuvArgs Y;
-    int bps = 0, n0 = 1, dw = 1, dh = 1, err = GFW_OK; bool interleaved = false, fast1 = false;
-    if (!build_yuv_args(&c, nplanes, planes, params, pixel_types, launches, matrices_on_device ? nullptr : h_matrices, matrix_count, 0, Y, bps, n0, dw, dh, interleaved, fast1, nullptr, err)) {
-        set_error("not a frame the fused kernel serves"); return GFW_ERR_UNSUPPORTED_BUFFER; }
-    fill_common(&c, &params[0], nullptr, nullptr, 0, Y.common);
-    const std::vector<std::string> defs = jit_build_defs(Y, bps, params[0].interpolation, n0, dw, dh, interleaved, fast1, false, false, nullptr);
-    return jit_key_out(arch, defs, bake_header(Y, fast1), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
+    c.model = distortion_model; c.digital = digital_lens; c.matrices_on_device = matrices_on_device; c.arch = arch;
+    GfwYuvArgs Y; FusedShape S;
+    { const int rc = dry_fused_args(c, 1, FrameIn{nplanes, planes, params, pixel_types, h_matrices, matrix_count, nullptr, 0}, nullptr, Y, S); if (rc != GFW_OK) return rc; }
+    return jit_key_out(arch, jit_build_defs(Y, S, false, false, nullptr), bake_header(Y, S), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
 }
 
 // The same for the first launch of a gfw_undistort_clip_params call (the per-frame flavour): `planes` / `params` hold n_frames x nplanes entries as that call takes
@@ -118,33 +113,16 @@ extern "C" int gfw_debug_jit_key_clip_params(int n_frames, int nplanes, const gf
                                              char *defs_out, size_t defs_cap, char *header_out, size_t header_cap, char *name_out, size_t name_cap) {
     if (!planes || !params || !pixel_types || !arch || n_frames < 1 || nplanes < 1 || nplanes > 4 || (!matrices_on_device && (!host_matrices || !host_matrices[0]))) {
         set_error("bad arguments"); return GFW_ERR_INVALID_ARGUMENT; }
-    for (int f = 0; f < n_frames; ++f)
-        for (int i = 0; i < nplanes; ++i) {
-            if (pixel_types[i] < 0 || pixel_types[i] >= GFW_PIX_COUNT) { set_error("plane %d: unknown pixel type", i); return GFW_ERR_INVALID_ARGUMENT; }
-            const int rc = validate_plane(&planes[(size_t)f * nplanes + i], &params[(size_t)f * nplanes + i], pixel_types[i]);
-            if (rc != GFW_OK) return rc;
-        }
     gfw_ctx c;
-    c.dry = true; c.model = distortion_model; c.digital = digital_lens; c.matrices_on_device = matrices_on_device; c.arch = arch; c.kernel_variant = audit ? 3 : 0;
-    ClipBatch batch;                                               // (as gfw_undistort_clip_params sets it up: the envelope of every frame of the call)
-    batch.n_call = n_frames; batch.perframe = true;
-    for (int f = 0; f < n_frames; ++f) {
-        double hx, hy;
-        p1_corner_extent(params[(size_t)f * nplanes], hx, hy);
-        batch.env_hx = fmax(batch.env_hx, hx); batch.env_hy = fmax(batch.env_hy, hy);
-    }
-    GfwPlane launches[4];
-    memset(launches, 0, sizeof(launches));
-    for (int i = 0; i < nplanes; ++i) { launches[i].src = (const uint8_t *)planes[i].input.data; launches[i].dst = (uint8_t *)planes[i].output.data; }
-    GfwYuvArgs Y;
-    int bps = 0, n0 = 1, dw = 1, dh = 1, err = GFW_OK; bool interleaved = false, fast1 = false;
-    if (!build_yuv_args(&c, nplanes, planes, params, pixel_types, launches, matrices_on_device ? nullptr : host_matrices[0], matrix_count, 0, Y, bps, n0, dw, dh, interleaved, fast1,
-                        &batch, err)) { set_error("not a frame the fused kernel serves"); return GFW_ERR_UNSUPPORTED_BUFFER; }
-    fill_common(&c, &params[0], nullptr, nullptr, 0, Y.common);
+    c.model = distortion_model; c.digital = digital_lens; c.matrices_on_device = matrices_on_device; c.arch = arch; c.kernel_variant = audit ? 3 : 0;
+    ClipBatch batch;
+    clip_params_batch(batch, n_frames, nplanes, params);
+    GfwYuvArgs Y; FusedShape S;
+    { const int rc = dry_fused_args(c, n_frames, FrameIn{nplanes, planes, params, pixel_types, matrices_on_device ? nullptr : host_matrices[0], matrix_count, nullptr, 0}, &batch, Y, S);
+      if (rc != GFW_OK) return rc; }
     const bool audit_build = jit_audit_build(&c, Y, true);
     if ((c.kernel_variant != 0 || Y.audit) && !audit_build) return 1;             // (jit_for: the ahead-of-time kernel)
-    const std::vector<std::string> defs = jit_build_defs(Y, bps, params[0].interpolation, n0, dw, dh, interleaved, fast1, true, audit_build, nullptr);
-    return jit_key_out(arch, defs, bake_header(Y, fast1, true), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
+    return jit_key_out(arch, jit_build_defs(Y, S, true, audit_build, nullptr), bake_header(Y, S, true), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
 }
 
 extern "C" int gfw_checksum64(gfw_ctx *c, const void *d_buf, size_t bytes, unsigned long long *d_out) {
@@ -164,13 +142,7 @@ extern "C" int gfw_set_frame_checksums(gfw_ctx *c, unsigned long long *d_sums, s
 
 extern "C" int gfw_pack_matrices(const float *rows14, int count, float *rows16) {
     if (!rows14 || !rows16 || count < 0) { set_error("null arrays"); return GFW_ERR_INVALID_ARGUMENT; }
-    for (int r = 0; r < count; ++r) {
-        const float *m = rows14 + (size_t)r * 14;
-        float *o = rows16 + (size_t)r * GFW_MAT_STRIDE;
-        memcpy(o, m, 14 * sizeof(float));
-        if (m[9] != 0.0f || m[10] != 0.0f || m[11] != 0.0f || m[12] != 0.0f || m[13] != 0.0f) { o[14] = cosf(-m[11]); o[15] = sinf(-m[11]); }
-        else { o[14] = 1.0f; o[15] = 0.0f; }
-    }
+    for (int r = 0; r < count; ++r) pack_row(rows14 + (size_t)r * 14, rows16 + (size_t)r * GFW_MAT_STRIDE);
     return GFW_OK;
 }
 extern "C" long long gfw_debug_paired_launches(gfw_ctx *c) { return c ? c->paired_launches : -1; }
