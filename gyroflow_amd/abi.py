@@ -173,9 +173,11 @@ def bind(lib):
     lib.gfw_build_matrices_stab.argtypes = [vp, C.POINTER(FrameTiming), C.POINTER(FrameStab), vp, C.POINTER(vp)]; lib.gfw_build_matrices_stab.restype = i32
     lib.gfw_set_sync_offsets.argtypes = [vp, C.c_double, vp, vp, i32]; lib.gfw_set_sync_offsets.restype = i32
     lib.gfw_build_matrices_batch.argtypes = [vp, C.POINTER(FrameTiming), i32, C.POINTER(vp)]; lib.gfw_build_matrices_batch.restype = i32
+    lib.gfw_build_matrices_batch_stab.argtypes = [vp, C.POINTER(FrameTiming), vp, i32, C.POINTER(vp)]; lib.gfw_build_matrices_batch_stab.restype = i32
     lib.gfw_stmap_undistort.argtypes = [vp, C.POINTER(KernelParams), vp, i32, vp, sz, i32, i32, vp, i32]; lib.gfw_stmap_undistort.restype = i32
     lib.gfw_undistort_points.argtypes = [vp, C.POINTER(KernelParams), vp, sz, i32, vp, i32, vp, i32, vp, sz, vp, i32]; lib.gfw_undistort_points.restype = i32
     lib.gfw_zoom_fovs.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(ZoomSearch), vp, i32, vp, vp, vp, i32]; lib.gfw_zoom_fovs.restype = i32
+    lib.gfw_zoom_fovs_stab.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(ZoomSearch), vp, i32, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_zoom_fovs_stab.restype = i32
     lib.gfw_zoom_smooth.argtypes = [vp, i32, C.c_double, C.c_double, i32, vp, i32, vp, vp]; lib.gfw_zoom_smooth.restype = i32
     lib.gfw_pack_matrices.argtypes = [vp, i32, vp]; lib.gfw_pack_matrices.restype = i32
     lib.gfw_checksum64.argtypes = [vp, vp, sz, vp]; lib.gfw_checksum64.restype = i32
@@ -199,7 +201,8 @@ EXPORTS = ["gfw_abi_version", "gfw_list_devices", "gfw_set_device", "gfw_get_inf
            "gfw_create", "gfw_destroy", "gfw_undistort_image", "gfw_undistort_frame", "gfw_set_option",
            "gfw_get_stream", "gfw_set_stream", "gfw_synchronize", "gfw_flush", "gfw_import_external_fd", "gfw_release_external", "gfw_last_backend", "gfw_get_profile", "gfw_last_error", "gfw_debug_math", "gfw_debug_jit_key", "gfw_debug_selftest", "gfw_get_audit", "gfw_pack_matrices", "gfw_checksum64", "gfw_set_frame_checksums", "gfw_set_quaternion_tracks", "gfw_build_matrices", "gfw_build_matrices_stab", "gfw_set_sync_offsets", "gfw_build_matrices_batch", "gfw_stmap_undistort", "gfw_undistort_points",
            "gfw_pixel_type_info", "gfw_undistort_clip", "gfw_undistort_clip_params", "gfw_jit_status", "gfw_get_profile_frames", "gfw_debug_jit_compile", "gfw_debug_source_id", "gfw_debug_p1_radial", "gfw_debug_paired_launches", "gfw_debug_frames_per_launch",
-           "gfw_debug_jit_key_clip_params", "gfw_zoom_fovs", "gfw_zoom_smooth"]
+           "gfw_debug_jit_key_clip_params", "gfw_zoom_fovs", "gfw_zoom_smooth",
+           "gfw_build_matrices_batch_stab", "gfw_zoom_fovs_stab"]
 
 
 def load_library(path=None):

@@ -54,6 +54,50 @@ static int stage_timings(gfw_ctx *c, const gfw_frame_timing *t, int count, hipSt
     return GFW_OK;
 }
 static bool timing_ok(const gfw_frame_timing *t) { return t->rows >= 1 && t->readout_dim >= 1 && t->suppress_rotation >= 0 && t->suppress_rotation <= 2; }
+// gfw_frame_stab as every entry that takes one checks it: counts >= 0 with their arrays, non-zero crop and pitch, ascending spline positions.  `frame` >= 0 is named in the error.
+static bool stab_ok(const gfw_frame_stab *stab, int frame) {
+    char who[32] = "";
+    if (frame >= 0) snprintf(who, sizeof(who), "frame %d: ", frame);
+    if (stab->ibis_count < 0 || stab->ois_count < 0 || (stab->ibis_count && !stab->ibis) || (stab->ois_count && !stab->ois) ||
+        !(stab->crop_area[2] != 0.0) || !(stab->crop_area[3] != 0.0) || !(stab->pixel_pitch[0] != 0.0) || !(stab->pixel_pitch[1] != 0.0)) {
+        set_error("%sbad stabiliser data (counts %d/%d, crop %g x %g, pitch %g x %g)", who, stab->ibis_count, stab->ois_count, stab->crop_area[2], stab->crop_area[3], stab->pixel_pitch[0], stab->pixel_pitch[1]);
+        return false; }
+    for (int i = 1; i < stab->ibis_count; ++i) if (!(stab->ibis[i * 4] >= stab->ibis[(i - 1) * 4])) { set_error("%sIBIS spline positions must ascend", who); return false; }
+    for (int i = 1; i < stab->ois_count; ++i) if (!(stab->ois[i * 4] >= stab->ois[(i - 1) * 4])) { set_error("%sOIS spline positions must ascend", who); return false; }
+    return true;
+}
+static size_t stab_point_bytes(const gfw_frame_stab *stab) { return ((size_t)stab->ibis_count + (size_t)stab->ois_count) * 32; }
+// The device form of a frame's stabiliser data; its control points are copied to `h_points` (pinned), which the caller uploads to `d_points`.  y_sign: the
+// framebuffer sign of the matrix path (frame_transform.rs:234-241), 1.0 for at_timestamp_for_points (:413-416)
+static GfwStab stab_device(const gfw_frame_stab *stab, double y_sign, void *h_points, const void *d_points) {
+    const size_t nb0 = (size_t)stab->ibis_count * 32, nb1 = (size_t)stab->ois_count * 32;
+    if (nb0) memcpy(h_points, stab->ibis, nb0);
+    if (nb1) memcpy((char *)h_points + nb0, stab->ois, nb1);
+    GfwStab S;
+    S.offset = stab->offset; S.sensor_h = stab->sensor_size[1]; S.crop_y = stab->crop_area[1]; S.crop_h = stab->crop_area[3];
+    S.scale_x = stab->width / stab->crop_area[2] / stab->pixel_pitch[0];
+    S.scale_y = stab->height / stab->crop_area[3] / stab->pixel_pitch[1] * y_sign;
+    S.height = stab->height;
+    S.ibis = (const double *)d_points; S.ois = (const double *)((const char *)d_points + nb0); S.ibis_n = stab->ibis_count; S.ois_n = stab->ois_count;
+    return S;
+}
+static const GfwStab kNoStab = {0, 0, 0, 0, 0, 0, 0, nullptr, nullptr, -1, -1};
+// the next (pinned host, device) pair of the stabiliser ring with room for `bytes`; the build that last read it has normally long finished
+static int stab_slot_for(gfw_ctx *c, size_t bytes, gfw_ctx::StabSlot **out) {
+    gfw_ctx::StabSlot &ss = c->sslots[c->sslot_next];
+    c->sslot_next = (c->sslot_next + 1) % gfw_ctx::kStabSlots;
+    if (!ss.done) HIP_TRY(hipEventCreateWithFlags(&ss.done, hipEventDisableTiming), GFW_ERR_HIP);
+    if (ss.used) HIP_TRY(hipEventSynchronize(ss.done), GFW_ERR_HIP);
+    HIP_TRY(ss.d.ensure(bytes), GFW_ERR_HIP);
+    if (ss.hcap < bytes) {
+        if (ss.h) (void)hipHostFree(ss.h);
+        ss.h = nullptr; ss.hcap = 0;
+        HIP_TRY(hipHostMalloc(&ss.h, bytes), GFW_ERR_HIP);
+        ss.hcap = bytes;
+    }
+    *out = &ss;
+    return GFW_OK;
+}
 
 int gfw_build_matrices(gfw_ctx *c, const gfw_frame_timing *t, float *rows16_out, float **out_ptr) {
     return gfw_build_matrices_stab(c, t, nullptr, rows16_out, out_ptr);
@@ -66,36 +110,10 @@ int gfw_build_matrices_stab(gfw_ctx *c, const gfw_frame_timing *t, const gfw_fra
     GfwStab S, *Sp = nullptr;
     gfw_ctx::StabSlot *stab_slot = nullptr; size_t stab_bytes = 0;
     if (stab) {
-        if (stab->ibis_count < 0 || stab->ois_count < 0 || (stab->ibis_count && !stab->ibis) || (stab->ois_count && !stab->ois) ||
-            !(stab->crop_area[2] != 0.0) || !(stab->crop_area[3] != 0.0) || !(stab->pixel_pitch[0] != 0.0) || !(stab->pixel_pitch[1] != 0.0)) {
-            set_error("bad stabiliser data (counts %d/%d, crop %g x %g, pitch %g x %g)", stab->ibis_count, stab->ois_count, stab->crop_area[2], stab->crop_area[3], stab->pixel_pitch[0], stab->pixel_pitch[1]);
-            return GFW_ERR_INVALID_ARGUMENT; }
-        for (int i = 1; i < stab->ibis_count; ++i) if (!(stab->ibis[i * 4] >= stab->ibis[(i - 1) * 4])) { set_error("IBIS spline positions must ascend"); return GFW_ERR_INVALID_ARGUMENT; }
-        for (int i = 1; i < stab->ois_count; ++i) if (!(stab->ois[i * 4] >= stab->ois[(i - 1) * 4])) { set_error("OIS spline positions must ascend"); return GFW_ERR_INVALID_ARGUMENT; }
-        const size_t nb0 = (size_t)stab->ibis_count * 32, nb1 = (size_t)stab->ois_count * 32;
-        // next pair of the ring; the build that last read it (four builds ago) has normally long finished
-        gfw_ctx::StabSlot &ss = c->sslots[c->sslot_next];
-        c->sslot_next = (c->sslot_next + 1) % gfw_ctx::kStabSlots;
-        if (!ss.done) HIP_TRY(hipEventCreateWithFlags(&ss.done, hipEventDisableTiming), GFW_ERR_HIP);
-        if (ss.used) HIP_TRY(hipEventSynchronize(ss.done), GFW_ERR_HIP);
-        HIP_TRY(ss.d.ensure(nb0 + nb1 + 64), GFW_ERR_HIP);
-        if (ss.hcap < nb0 + nb1 + 64) {
-            if (ss.h) (void)hipHostFree(ss.h);
-            ss.h = nullptr; ss.hcap = 0;
-            HIP_TRY(hipHostMalloc(&ss.h, nb0 + nb1 + 64), GFW_ERR_HIP);
-            ss.hcap = nb0 + nb1 + 64;
-        }
-        stab_slot = &ss;
-        char *base = (char *)ss.d.ptr;
-        if (nb0) memcpy(ss.h, stab->ibis, nb0);
-        if (nb1) memcpy((char *)ss.h + nb0, stab->ois, nb1);
-        stab_bytes = nb0 + nb1;
-        const double inv = t->framebuffer_inverted ? -1.0 : 1.0;
-        S.offset = stab->offset; S.sensor_h = stab->sensor_size[1]; S.crop_y = stab->crop_area[1]; S.crop_h = stab->crop_area[3];
-        S.scale_x = stab->width / stab->crop_area[2] / stab->pixel_pitch[0];                       // frame_transform.rs:234-241
-        S.scale_y = stab->height / stab->crop_area[3] / stab->pixel_pitch[1] * inv;
-        S.height = stab->height;
-        S.ibis = (const double *)base; S.ois = (const double *)(base + nb0); S.ibis_n = stab->ibis_count; S.ois_n = stab->ois_count;
+        if (!stab_ok(stab, -1)) return GFW_ERR_INVALID_ARGUMENT;
+        stab_bytes = stab_point_bytes(stab);
+        { const int rc = stab_slot_for(c, stab_bytes + 64, &stab_slot); if (rc != GFW_OK) return rc; }
+        S = stab_device(stab, t->framebuffer_inverted ? -1.0 : 1.0, stab_slot->h, stab_slot->d.ptr);
         Sp = &S;
     }
     const size_t table_floats = (size_t)t->rows * GFW_MAT_STRIDE;
@@ -146,6 +164,45 @@ int gfw_build_matrices_batch(gfw_ctx *c, const gfw_frame_timing *t, int count, f
     const gfw_frame_timing *d_t = nullptr;
     { const int rc = stage_timings(c, t, count, c->stream, &d_t); if (rc != GFW_OK) return rc; }
     HIP_TRY(gfw_launch_build_matrices(c->tracks, d_t, count, max_rows, (double *)((char *)buf.ptr + tables_bytes), (float *)buf.ptr, table_floats, c->stream), GFW_ERR_HIP);
+    for (int i = 0; i < count; ++i) out_ptrs[i] = (float *)buf.ptr + table_floats * i;
+    if (c->synchronous) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);
+    return GFW_OK;
+}
+// The same for a clip with IBIS/OIS splines: frame i's table is gfw_build_matrices_stab(ctx, &t[i], stabs[i], ...)'s, bit for bit.  The descriptors of all frames and their
+// control points go up in ONE pinned copy in front of the launch; the row kernel reads its frame's descriptor from that device table.
+int gfw_build_matrices_batch_stab(gfw_ctx *c, const gfw_frame_timing *t, const gfw_frame_stab *const *stabs, int count, float **out_ptrs) {
+    if (!stabs) return gfw_build_matrices_batch(c, t, count, out_ptrs);
+    if (!c || !t || !out_ptrs || count < 1 || count > gfw_ctx::kMaxBatch) { set_error("bad batch arguments (1 <= count <= %d)", gfw_ctx::kMaxBatch); return GFW_ERR_INVALID_ARGUMENT; }
+    int max_rows = 0;
+    size_t point_bytes = 0;
+    for (int i = 0; i < count; ++i) {
+        if (!timing_ok(&t[i])) { set_error("frame %d: rows %d, readout_dim %d, suppress_rotation %d", i, t[i].rows, t[i].readout_dim, t[i].suppress_rotation); return GFW_ERR_INVALID_ARGUMENT; }
+        if (t[i].rows > max_rows) max_rows = t[i].rows;
+        if (stabs[i]) { if (!stab_ok(stabs[i], i)) return GFW_ERR_INVALID_ARGUMENT; point_bytes += stab_point_bytes(stabs[i]); }
+    }
+    { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
+    HIP_TRY(hipSetDevice(c->device), GFW_ERR_HIP);
+    const size_t table_bytes = sizeof(GfwStab) * (size_t)count;
+    gfw_ctx::StabSlot *ss = nullptr;
+    { const int rc = stab_slot_for(c, table_bytes + point_bytes + 64, &ss); if (rc != GFW_OK) return rc; }
+    GfwStab *h_stabs = (GfwStab *)ss->h;
+    size_t at = table_bytes;
+    for (int i = 0; i < count; ++i) {
+        if (!stabs[i]) { h_stabs[i] = kNoStab; continue; }
+        h_stabs[i] = stab_device(stabs[i], t[i].framebuffer_inverted ? -1.0 : 1.0, (char *)ss->h + at, (const char *)ss->d.ptr + at);
+        at += stab_point_bytes(stabs[i]);
+    }
+    DevBuf &buf = c->d_batch[c->batch_next];
+    c->batch_next ^= 1;
+    const size_t table_floats = (size_t)max_rows * GFW_MAT_STRIDE;
+    const size_t tables_bytes = table_floats * sizeof(float) * count;
+    HIP_TRY(buf.ensure(tables_bytes + 4 * sizeof(double) * count), GFW_ERR_HIP);
+    const gfw_frame_timing *d_t = nullptr;
+    { const int rc = stage_timings(c, t, count, c->stream, &d_t); if (rc != GFW_OK) return rc; }
+    HIP_TRY(hipMemcpyAsync(ss->d.ptr, ss->h, at, hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
+    HIP_TRY(gfw_launch_build_matrices_stab(c->tracks, d_t, count, max_rows, (double *)((char *)buf.ptr + tables_bytes), (float *)buf.ptr, table_floats, c->stream, (const GfwStab *)ss->d.ptr), GFW_ERR_HIP);
+    HIP_TRY(hipEventRecord(ss->done, c->stream), GFW_ERR_HIP);
+    ss->used = true;
     for (int i = 0; i < count; ++i) out_ptrs[i] = (float *)buf.ptr + table_floats * i;
     if (c->synchronous) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);
     return GFW_OK;
@@ -241,44 +298,81 @@ extern "C" int gfw_stmap_undistort(gfw_ctx *c, const gfw_kernel_params *p, const
 }
 
 // Adaptive zoom, first half: FovIterative::find_fov of every frame (fov_iterative.rs:91-134) in one launch, a workgroup per frame (gfw_zoom.hip).
-// See include/gfwarp.h for the argument contract.
-extern "C" int gfw_zoom_fovs(gfw_ctx *c, const gfw_kernel_params *p, const gfw_zoom_search *search, const gfw_zoom_frame *frames, int n_frames,
-                             const float *rotations, double *fov_minimal, double *debug_points, int out_on_device) {
+// See include/gfwarp.h for the argument contract.  `with_data`: gfw_zoom_fovs_stab — per-frame stabiliser data and meshes are taken, the three data flags are not
+// consulted, suppress_rotation 2 is a value.
+static int zoom_fovs_impl(gfw_ctx *c, const gfw_kernel_params *p, const gfw_zoom_search *search, const gfw_zoom_frame *frames, int n_frames, const float *rotations,
+                          const gfw_frame_stab *const *stabs, const double *const *meshes, const size_t *mesh_lens,
+                          double *fov_minimal, double *debug_points, int out_on_device, bool with_data) {
     if (!c || !p || !search || n_frames < 0) { set_error("bad zoom arguments (null context / params / search, or n_frames < 0)"); return GFW_ERR_INVALID_ARGUMENT; }
     if (n_frames == 0) return GFW_OK;                                        // fov_iterative.rs:33 `if timestamps.is_empty() { return Vec::new(); }`
     if (!frames || !fov_minimal) { set_error("bad zoom arguments (null frames / fov_minimal)"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (meshes && !mesh_lens) { set_error("bad zoom arguments (meshes without mesh_lens)"); return GFW_ERR_INVALID_ARGUMENT; }
     if (search->width < 1 || search->height < 1 || search->org_output_width < 1 || search->org_output_height < 1 || !(search->fov_algorithm_margin == search->fov_algorithm_margin) ||
         search->horizontal_readout < 0 || search->horizontal_readout > 1) {
         set_error("bad zoom search: %d x %d, output %d x %d, margin %g, horizontal_readout %d", search->width, search->height, search->org_output_width, search->org_output_height,
                   (double)search->fov_algorithm_margin, search->horizontal_readout);
         return GFW_ERR_INVALID_ARGUMENT; }
-    if (p->flags & (256 | 512 | 1024)) {                                     // HAS_IBIS_DATA | HAS_MESH_DATA | HAS_FPD_DATA
+    if (!with_data && (p->flags & (256 | 512 | 1024))) {                     // HAS_IBIS_DATA | HAS_MESH_DATA | HAS_FPD_DATA
         set_error("the zoom search does not cover per-frame IBIS/OIS shifts, lens meshes or focal-plane distortion data (flags 0x%x): map the outline with gfw_undistort_points", p->flags);
         return GFW_ERR_INVALID_ARGUMENT; }
     if (!rotations && c->tracks.org_n < 1 && c->tracks.sm_n < 1) { set_error("no rotations given and no quaternion tracks set (gfw_set_quaternion_tracks)"); return GFW_ERR_INVALID_ARGUMENT; }
+    size_t point_bytes = 0, mesh_doubles = 0;
     for (int i = 0; i < n_frames; ++i) {
-        if (frames[i].suppress_rotation < 0 || frames[i].suppress_rotation > 1) { set_error("frame %d: suppress_rotation %d", i, frames[i].suppress_rotation); return GFW_ERR_INVALID_ARGUMENT; }
+        if (frames[i].suppress_rotation < 0 || frames[i].suppress_rotation > (with_data ? 2 : 1)) { set_error("frame %d: suppress_rotation %d", i, frames[i].suppress_rotation); return GFW_ERR_INVALID_ARGUMENT; }
         if (rotations && frames[i].frame_readout_time_ms != 0.0) {
             set_error("frame %d: caller-given rotations are one per frame, but frame_readout_time_ms = %g needs one per point", i, frames[i].frame_readout_time_ms);
             return GFW_ERR_INVALID_ARGUMENT; }
+        if (stabs && stabs[i]) { if (!stab_ok(stabs[i], i)) return GFW_ERR_INVALID_ARGUMENT; point_bytes += stab_point_bytes(stabs[i]); }
+        if (meshes && mesh_lens[i]) {
+            if (!meshes[i]) { set_error("frame %d: mesh of %zu values is NULL", i, mesh_lens[i]); return GFW_ERR_INVALID_ARGUMENT; }
+            if (i && meshes[i] == meshes[i - 1] && mesh_lens[i] == mesh_lens[i - 1]) continue;            // the mesh of the frame before: checked and uploaded once
+            if (mesh_lens[i] > GFW_MESH_MAX) { set_error("frame %d: mesh too large (%zu values, at most %d)", i, mesh_lens[i], GFW_MESH_MAX); return GFW_ERR_INVALID_ARGUMENT; }
+            if (validate_mesh(meshes[i], mesh_lens[i]) != GFW_OK) { const std::string why = g_last_error; set_error("frame %d: %s", i, why.c_str()); return GFW_ERR_INVALID_ARGUMENT; }
+            mesh_doubles += mesh_lens[i];
+        }
     }
+    if (mesh_doubles > 0x7fffffffu) { set_error("the clip's distinct meshes hold %zu values: more than a frame's 32-bit mesh reference addresses", mesh_doubles); return GFW_ERR_INVALID_ARGUMENT; }
     { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
     HIP_TRY(hipSetDevice(c->device), GFW_ERR_HIP);
-    // descriptors (and rotations) through pinned memory: the copy is enqueued, the caller's arrays are free on return
-    const size_t fb = sizeof(gfw_zoom_frame) * (size_t)n_frames, rb = rotations ? sizeof(float) * 9 * (size_t)n_frames : 0;
+    // descriptors (rotations, stabiliser tables, control points, meshes) through pinned memory in one copy: it is enqueued, the caller's arrays are free on return
+    const size_t fb = sizeof(gfw_zoom_frame) * (size_t)n_frames, rb = rotations ? (sizeof(float) * 9 * (size_t)n_frames + 7) / 8 * 8 : 0;
+    const size_t sb = stabs ? sizeof(GfwStab) * (size_t)n_frames : 0, mb = meshes ? sizeof(int32_t) * 2 * (size_t)n_frames : 0;
+    const size_t o_stab = fb + rb, o_points = o_stab + sb, o_ref = o_points + point_bytes, o_mesh = o_ref + mb, total = o_mesh + mesh_doubles * sizeof(double);
+    static_assert(sizeof(gfw_zoom_frame) % 8 == 0 && sizeof(GfwStab) % 8 == 0 && GFW_MESH_MAX == GFW_ZOOM_MESH_MAX, "the staged block keeps its doubles aligned; one mesh limit");
     if (!c->zoom_copied) HIP_TRY(hipEventCreateWithFlags(&c->zoom_copied, hipEventDisableTiming), GFW_ERR_HIP);
     HIP_TRY(hipEventSynchronize(c->zoom_copied), GFW_ERR_HIP);              // the copy that last read the pinned block is done
-    if (c->h_zoom_cap < fb + rb) {
+    if (c->h_zoom_cap < total) {
         if (c->h_zoom) (void)hipHostFree(c->h_zoom);
         c->h_zoom = nullptr; c->h_zoom_cap = 0;
-        HIP_TRY(hipHostMalloc(&c->h_zoom, fb + rb), GFW_ERR_HIP);
-        c->h_zoom_cap = fb + rb;
+        HIP_TRY(hipHostMalloc(&c->h_zoom, total), GFW_ERR_HIP);
+        c->h_zoom_cap = total;
     }
-    if (c->d_zoom_in.cap < fb + rb) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);      // a launch in flight may still read the block about to be replaced
-    HIP_TRY(c->d_zoom_in.ensure(fb + rb), GFW_ERR_HIP);
-    memcpy(c->h_zoom, frames, fb);
-    if (rb) memcpy((char *)c->h_zoom + fb, rotations, rb);
-    HIP_TRY(hipMemcpyAsync(c->d_zoom_in.ptr, c->h_zoom, fb + rb, hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
+    if (c->d_zoom_in.cap < total) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);      // a launch in flight may still read the block about to be replaced
+    HIP_TRY(c->d_zoom_in.ensure(total), GFW_ERR_HIP);
+    char *h = (char *)c->h_zoom;
+    const char *d = (const char *)c->d_zoom_in.ptr;
+    memcpy(h, frames, fb);
+    if (rb) memcpy(h + fb, rotations, sizeof(float) * 9 * (size_t)n_frames);
+    if (stabs) {
+        GfwStab *hs = (GfwStab *)(h + o_stab);
+        size_t at = o_points;
+        for (int i = 0; i < n_frames; ++i) {
+            if (!stabs[i]) { hs[i] = kNoStab; continue; }
+            hs[i] = stab_device(stabs[i], 1.0, h + at, d + at);
+            at += stab_point_bytes(stabs[i]);
+        }
+    }
+    if (meshes) {
+        int32_t *ref = (int32_t *)(h + o_ref);
+        double *hm = (double *)(h + o_mesh);
+        size_t at = 0, first = 0;
+        for (int i = 0; i < n_frames; ++i) {
+            if (!mesh_lens[i]) { ref[i * 2] = 0; ref[i * 2 + 1] = 0; continue; }
+            if (!(i && meshes[i] == meshes[i - 1] && mesh_lens[i] == mesh_lens[i - 1])) { first = at; memcpy(hm + at, meshes[i], mesh_lens[i] * sizeof(double)); at += mesh_lens[i]; }
+            ref[i * 2] = (int32_t)first; ref[i * 2 + 1] = (int32_t)mesh_lens[i];
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_zoom_in.ptr, c->h_zoom, total, hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
     HIP_TRY(hipEventRecord(c->zoom_copied, c->stream), GFW_ERR_HIP);
     const size_t ob = sizeof(double) * (size_t)n_frames, db = debug_points ? sizeof(double) * 2 * GFW_ZOOM_RECT * (size_t)n_frames : 0;
     double *d_fov = fov_minimal, *d_dbg = debug_points;
@@ -289,8 +383,10 @@ extern "C" int gfw_zoom_fovs(gfw_ctx *c, const gfw_kernel_params *p, const gfw_z
     GfwZoomArgs A;
     memset(&A, 0, sizeof(A));
     A.T = c->tracks;
-    A.frames = (const gfw_zoom_frame *)c->d_zoom_in.ptr;
-    A.rotations = rotations ? (const float *)((const char *)c->d_zoom_in.ptr + fb) : nullptr;
+    A.frames = (const gfw_zoom_frame *)d;
+    A.rotations = rotations ? (const float *)(d + fb) : nullptr;
+    if (stabs) A.stabs = (const GfwStab *)(d + o_stab);
+    if (meshes) { A.mesh_ref = (const int32_t *)(d + o_ref); A.mesh_data = (const double *)(d + o_mesh); }
     A.fov_minimal = d_fov; A.debug_points = d_dbg;
     A.horizontal = search->horizontal_readout;
     A.w = (float)search->width; A.h = (float)search->height; A.margin = search->fov_algorithm_margin;
@@ -302,13 +398,23 @@ extern "C" int gfw_zoom_fovs(gfw_ctx *c, const gfw_kernel_params *p, const gfw_z
     GfwCommon C;
     fill_common(c, p, nullptr, nullptr, 0, C);
     HIP_TRY(gfw_launch_zoom(*p, C, A, n_frames, c->stream), GFW_ERR_HIP);
-    c->last_backend = "zoom_fovs";
+    c->last_backend = (stabs || meshes) ? "zoom_fovs_stab" : "zoom_fovs";
     if (!out_on_device) {
         HIP_TRY(hipMemcpyAsync(fov_minimal, d_fov, ob, hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
         if (db) HIP_TRY(hipMemcpyAsync(debug_points, d_dbg, db, hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
     }
     if (c->synchronous || !out_on_device) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);
     return GFW_OK;
+}
+extern "C" int gfw_zoom_fovs(gfw_ctx *c, const gfw_kernel_params *p, const gfw_zoom_search *search, const gfw_zoom_frame *frames, int n_frames,
+                             const float *rotations, double *fov_minimal, double *debug_points, int out_on_device) {
+    return zoom_fovs_impl(c, p, search, frames, n_frames, rotations, nullptr, nullptr, nullptr, fov_minimal, debug_points, out_on_device, false);
+}
+// The same for clips with camera_stab_data and a per-frame mesh_correction (frame_transform.rs:370-373, :412-435): NULL tables launch gfw_zoom_fovs's own instantiations.
+extern "C" int gfw_zoom_fovs_stab(gfw_ctx *c, const gfw_kernel_params *p, const gfw_zoom_search *search, const gfw_zoom_frame *frames, int n_frames,
+                                  const float *rotations, const gfw_frame_stab *const *stabs, const double *const *meshes, const size_t *mesh_lens,
+                                  double *fov_minimal, double *debug_points, int out_on_device) {
+    return zoom_fovs_impl(c, p, search, frames, n_frames, rotations, stabs, meshes, mesh_lens, fov_minimal, debug_points, out_on_device, true);
 }
 
 // Adaptive zoom, second half, on the host: zooming/mod.rs:55-68 and zoom_dynamic.rs in f64, the reference's operation order.

@@ -21,3 +21,6 @@ struct GfwStab {              // gfw_frame_stab with device-resident control poi
 // duration of the launch.
 hipError_t gfw_launch_build_matrices(const GfwTracks &T, const gfw_frame_timing *d_timings, int frames, int max_rows, double *prefix_scratch,
                                      float *out, size_t table_floats, hipStream_t s, const GfwStab *stab = nullptr);
+// The same with per-frame stabiliser data: d_stabs[frames] (device; the control points its entries name are device memory as well; counts of -1: the frame has none)
+hipError_t gfw_launch_build_matrices_stab(const GfwTracks &T, const gfw_frame_timing *d_timings, int frames, int max_rows, double *prefix_scratch,
+                                          float *out, size_t table_floats, hipStream_t s, const GfwStab *d_stabs);

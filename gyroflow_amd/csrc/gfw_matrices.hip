@@ -16,6 +16,7 @@
 #include "gfw_matrices.h"
 #include "gfw_math.h"
 #include "gfw_quat.h"
+#include "gfw_spline.h"
 
 namespace {
 
@@ -31,31 +32,8 @@ __global__ void gfw_build_prefix_kernel(const GfwTracks T, const gfw_frame_timin
     const Q pre = quat_prefix(T, ts);
     prefix[0] = pre.w; prefix[1] = pre.x; prefix[2] = pre.y; prefix[3] = pre.z;
 }
-// CatmullRom<Vector3<f64>>::interpolate (gyro_source/splines.rs:22-84) over `n` control points (position, x, y, z);
-// false = None (the caller substitutes the default, zero)
-__device__ bool catmull_rom_at(const double *pts, int n, double t, double out[3]) {
-    if (n < 2 || !(t == t)) return false;
-    // search_lower_cp: binary_search_by(partial_cmp): Ok(i) exact hit, Err(i) insertion point
-    int lo = 0, hi = n;                                           // first index with position >= t
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (pts[mid * 4] < t) lo = mid + 1; else hi = mid; }
-    int lower;
-    if (lo < n && pts[lo * 4] == t) { if (lo == n - 1) return false; lower = lo; }
-    else { if (lo >= n || lo == 0) return false; lower = lo - 1; }
-    if (lower + 1 >= n) return false;
-    const double *pa = pts + (size_t)lower * 4, *pb = pa + 4;
-    const double k = (t - pa[0]) / (pb[0] - pa[0]);               // normalize
-    for (int c = 0; c < 3; ++c) {
-        const double a = pa[1 + c], b = pb[1 + c];
-        const double x = (lower <= 0) ? a * 2.0 - b : pa[1 + c - 4];
-        const double y = (lower + 2 >= n) ? b * 2.0 - a : pb[1 + c + 4];
-        out[c] = ((((a * 3.0 - x) - b * 3.0) + y) * 0.5) * k * k * k + ((b - x) * 0.5) * k + a + (((b * 4.0 + a * -5.0 + x + x) - y) * 0.5) * k * k;
-    }
-    return true;
-}
-__global__ void gfw_build_matrices_kernel(const GfwTracks T, const gfw_frame_timing *Fs, const double *prefix, float *out, size_t table_floats, const GfwStab S) {
-    const gfw_frame_timing &F = Fs[blockIdx.y];
-    prefix += (size_t)blockIdx.y * 4;
-    out += (size_t)blockIdx.y * table_floats;
+// One row of one frame's table (frame_transform.rs:249-308): the body of both row kernels below — `S` by value for a whole launch, or the frame's entry of a device table
+__device__ __forceinline__ void gfw_build_matrices_row(const GfwTracks &T, const gfw_frame_timing &F, const double *prefix, float *out, const GfwStab &S) {
     const int y = blockIdx.x * blockDim.x + threadIdx.x;
     if (y >= F.rows) return;
     const double frt = F.frame_readout_time_ms;
@@ -100,6 +78,13 @@ __global__ void gfw_build_matrices_kernel(const GfwTracks T, const gfw_frame_tim
     if (sx != 0.0f || sy != 0.0f || ra != 0.0f || ox != 0.0f || oy != 0.0f) { o[14] = gfw_cosf(-ra); o[15] = gfw_sinf(-ra); }
     else { o[14] = 1.0f; o[15] = 0.0f; }
 }
+__global__ void gfw_build_matrices_kernel(const GfwTracks T, const gfw_frame_timing *Fs, const double *prefix, float *out, size_t table_floats, const GfwStab S) {
+    gfw_build_matrices_row(T, Fs[blockIdx.y], prefix + (size_t)blockIdx.y * 4, out + (size_t)blockIdx.y * table_floats, S);
+}
+// The same with every frame's own stabiliser data: `Ss[frames]` in device memory (counts of -1: the frame has none), blockIdx.y = frame
+__global__ void gfw_build_matrices_stab_kernel(const GfwTracks T, const gfw_frame_timing *Fs, const double *prefix, float *out, size_t table_floats, const GfwStab *Ss) {
+    gfw_build_matrices_row(T, Fs[blockIdx.y], prefix + (size_t)blockIdx.y * 4, out + (size_t)blockIdx.y * table_floats, Ss[blockIdx.y]);
+}
 
 }  // namespace
 
@@ -110,5 +95,12 @@ hipError_t gfw_launch_build_matrices(const GfwTracks &T, const gfw_frame_timing 
     if (stab) S = *stab; else { S = GfwStab{0, 0, 0, 0, 0, 0, 0, nullptr, nullptr, -1, -1}; }
     hipLaunchKernelGGL(gfw_build_prefix_kernel, dim3((frames + 63) / 64), dim3(64), 0, s, T, d_timings, frames, prefix_scratch);
     hipLaunchKernelGGL(gfw_build_matrices_kernel, dim3((max_rows + 63) / 64, frames), dim3(64), 0, s, T, d_timings, (const double *)prefix_scratch, out, table_floats, S);
+    return hipGetLastError();
+}
+hipError_t gfw_launch_build_matrices_stab(const GfwTracks &T, const gfw_frame_timing *d_timings, int frames, int max_rows, double *prefix_scratch,
+                                          float *out, size_t table_floats, hipStream_t s, const GfwStab *d_stabs) {
+    if (frames <= 0 || max_rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(gfw_build_prefix_kernel, dim3((frames + 63) / 64), dim3(64), 0, s, T, d_timings, frames, prefix_scratch);
+    hipLaunchKernelGGL(gfw_build_matrices_stab_kernel, dim3((max_rows + 63) / 64, frames), dim3(64), 0, s, T, d_timings, (const double *)prefix_scratch, out, table_floats, d_stabs);
     return hipGetLastError();
 }

@@ -96,7 +96,8 @@ class ComputeParams:
                  horizontal_rs=False, background=(0.0, 0.0, 0.0, 0.0), background_mode=0, background_margin=0.0,
                  background_margin_feather=0.0, lens_correction_amount=1.0, light_refraction_coefficient=1.0,
                  adaptive_zoom_center_offset=(0.0, 0.0), scaled_fps=30.0, org_quat_at=None, smoothed_quat_at=None,
-                 video_rotation=0.0, framebuffer_inverted=False, adaptive_zoom_window=0.0, fov_algorithm_margin=2.0, trim_ranges=()):
+                 video_rotation=0.0, framebuffer_inverted=False, adaptive_zoom_window=0.0, fov_algorithm_margin=2.0, trim_ranges=(),
+                 camera_stab_data=None, mesh_correction=None):
         self.lens = lens
         self.distortion_model, self.digital_lens, self.digital_lens_params = distortion_model, digital_lens, digital_lens_params
         self.width, self.height, self.output_width, self.output_height = width, height, output_width, output_height
@@ -115,6 +116,10 @@ class ComputeParams:
         # the adaptive-zoom search (zooming.calculate_fovs): window in seconds (< -0.9 static zoom, 0 disabled), the outline's margin in pixels
         # (compute_params.rs:127), the render ranges as fractions of the clip
         self.adaptive_zoom_window, self.fov_algorithm_margin, self.trim_ranges = adaptive_zoom_window, fov_algorithm_margin, list(trim_ranges)
+        # file_metadata.camera_stab_data / mesh_correction (gyro_source/file_metadata.rs:41-48), indexed by frame: None, or a list whose entry is None or
+        # the dict Backend.build_matrices takes as `stab` / the frame's float64 distorting mesh (mesh_correction[frame].0).  Read by zooming.calculate_fovs
+        self.camera_stab_data = list(camera_stab_data) if camera_stab_data is not None else None
+        self.mesh_correction = list(mesh_correction) if mesh_correction is not None else None
 
 
 class FrameTransform:

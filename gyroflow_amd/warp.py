@@ -51,6 +51,32 @@ def device_buffers(src_ptr, src_len, in_size, dst_ptr, dst_len, out_size, in_rec
 _last_backend = ""
 
 
+def frame_stab(stab):
+    """abi.FrameStab of dict(offset, sensor_size, crop_area, pixel_pitch, width, height, ibis=[n][4], ois=[n][4]) -> (struct, the arrays it points into)"""
+    st = abi.FrameStab()
+    st.offset = stab["offset"]
+    st.sensor_size[0], st.sensor_size[1] = stab["sensor_size"]
+    for i in range(4):
+        st.crop_area[i] = stab["crop_area"][i]
+    st.pixel_pitch[0], st.pixel_pitch[1] = stab["pixel_pitch"]
+    st.width, st.height = stab["width"], stab["height"]
+    ibis = np.ascontiguousarray(stab["ibis"], dtype=np.float64).reshape(-1, 4)
+    ois = np.ascontiguousarray(stab["ois"], dtype=np.float64).reshape(-1, 4)
+    st.ibis_count, st.ois_count = ibis.shape[0], ois.shape[0]
+    st.ibis, st.ois = ibis.ctypes.data, ois.ctypes.data
+    return st, (ibis, ois)
+
+
+def frame_stab_table(stabs):
+    """[dict or None per frame] -> (ctypes array of gfw_frame_stab pointers, NULL where None; what it points into)"""
+    table, keep = (C.c_void_p * max(len(stabs), 1))(), []
+    for k, stab in enumerate(stabs):
+        if stab is not None:
+            keep.append(frame_stab(stab))
+            table[k] = C.addressof(keep[-1][0])
+    return table, keep
+
+
 def last_backend():
     return _last_backend
 
@@ -159,35 +185,34 @@ class Backend:
         if stab is None:
             self._check(self.lib.gfw_build_matrices(self.ctx, C.byref(t), out_ptr, C.byref(ptr)))
             return ptr.value
-        st = abi.FrameStab()
-        st.offset = stab["offset"]
-        st.sensor_size[0], st.sensor_size[1] = stab["sensor_size"]
-        for i in range(4):
-            st.crop_area[i] = stab["crop_area"][i]
-        st.pixel_pitch[0], st.pixel_pitch[1] = stab["pixel_pitch"]
-        st.width, st.height = stab["width"], stab["height"]
-        ibis = np.ascontiguousarray(stab["ibis"], dtype=np.float64).reshape(-1, 4)
-        ois = np.ascontiguousarray(stab["ois"], dtype=np.float64).reshape(-1, 4)
-        st.ibis_count, st.ois_count = ibis.shape[0], ois.shape[0]
-        st.ibis, st.ois = ibis.ctypes.data, ois.ctypes.data
+        st, _keep = frame_stab(stab)
         self._check(self.lib.gfw_build_matrices_stab(self.ctx, C.byref(t), C.byref(st), out_ptr, C.byref(ptr)))
         return ptr.value
 
     def build_matrices_batch(self, nk, timestamps_ms, frame_readout_time_ms, rows, readout_dim, video_rotation_deg=0.0,
-                             framebuffer_inverted=False, per_frame_offset_ms=0.0):
-        """Tables of several upcoming frames in one launch (gfw_build_matrices_batch); returns the device pointers."""
+                             framebuffer_inverted=False, per_frame_offset_ms=0.0, stabs=None, suppress_rotation=0):
+        """Tables of several upcoming frames in one launch (gfw_build_matrices_batch); returns the device pointers.
+        stabs: None, or one entry per frame — None or the dict build_matrices takes — (gfw_build_matrices_batch_stab).
+        framebuffer_inverted / suppress_rotation: one value, or one per frame."""
         n = len(timestamps_ms)
         arr = (abi.FrameTiming * n)()
         nkf = np.asarray(nk, dtype=np.float64).reshape(9)
+        per_frame = lambda v, k: v[k] if isinstance(v, (list, tuple)) else v
         for k, ts in enumerate(timestamps_ms):
             t = arr[k]
             t.timestamp_ms, t.per_frame_time_offset_ms, t.frame_readout_time_ms = ts, per_frame_offset_ms, frame_readout_time_ms
             for i in range(9):
                 t.new_k[i] = nkf[i]
             t.video_rotation_deg, t.rows, t.readout_dim = video_rotation_deg, rows, readout_dim
-            t.framebuffer_inverted = 1 if framebuffer_inverted else 0
+            t.framebuffer_inverted = 1 if per_frame(framebuffer_inverted, k) else 0
+            t.suppress_rotation = int(per_frame(suppress_rotation, k))
         ptrs = (C.c_void_p * n)()
-        self._check(self.lib.gfw_build_matrices_batch(self.ctx, arr, n, ptrs))
+        if stabs is None:
+            self._check(self.lib.gfw_build_matrices_batch(self.ctx, arr, n, ptrs))
+        else:
+            assert len(stabs) == n
+            table, _keep = frame_stab_table(stabs)
+            self._check(self.lib.gfw_build_matrices_batch_stab(self.ctx, arr, table, n, ptrs))
         return [p for p in ptrs]
 
     def stmap_undistort(self, params, matrices, width, height, mesh=None):
@@ -249,6 +274,41 @@ class Backend:
         dbg = np.zeros((n, abi.ZOOM_RECT_POINTS, 2), dtype=np.float64) if debug else None
         self._check(self.lib.gfw_zoom_fovs(self.ctx, C.byref(params), C.byref(search), C.cast(arr, C.c_void_p), n, rp, fov.ctypes.data,
                                            dbg.ctypes.data if debug else None, 0))
+        return (fov, dbg) if debug else fov
+
+    def zoom_fovs_stab(self, params, search, frames, rotations=None, stabs=None, meshes=None, debug=False, out_ptr=None, debug_ptr=None):
+        """zoom_fovs for clips with stabiliser data and lens meshes (gfw_zoom_fovs_stab).  ``stabs``: None, or one entry per frame —
+        None (camera_stab_data has no entry for the frame) or the dict build_matrices takes; ``meshes``: None, or one entry per frame — None
+        or the frame's float64 distorting mesh (frames that name the SAME array object consecutively share one upload).  Everything else as
+        zoom_fovs; with both None the call is gfw_zoom_fovs's."""
+        n = len(frames)
+        arr = frames if isinstance(frames, C.Array) else (abi.ZoomFrame * max(n, 1))(*frames)
+        rp = None
+        if rotations is not None:
+            rot = np.ascontiguousarray(rotations, dtype=np.float32).reshape(-1, 9)
+            assert rot.shape[0] == n
+            rp = rot.ctypes.data
+        sp, _keep = (None, None)
+        if stabs is not None:
+            assert len(stabs) == n
+            sp, _keep = frame_stab_table(stabs)
+        mp = lp = None
+        if meshes is not None:
+            assert len(meshes) == n
+            mp, lp, held = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))(), {}
+            for k, m in enumerate(meshes):
+                if m is None or len(m) == 0:
+                    continue
+                if id(m) not in held:
+                    held[id(m)] = np.ascontiguousarray(m, dtype=np.float64)
+                mp[k], lp[k] = held[id(m)].ctypes.data, held[id(m)].size
+        if out_ptr is not None:
+            self._check(self.lib.gfw_zoom_fovs_stab(self.ctx, C.byref(params), C.byref(search), C.cast(arr, C.c_void_p), n, rp, sp, mp, lp, out_ptr, debug_ptr, 1))
+            return None
+        fov = np.zeros(n, dtype=np.float64)
+        dbg = np.zeros((n, abi.ZOOM_RECT_POINTS, 2), dtype=np.float64) if debug else None
+        self._check(self.lib.gfw_zoom_fovs_stab(self.ctx, C.byref(params), C.byref(search), C.cast(arr, C.c_void_p), n, rp, sp, mp, lp, fov.ctypes.data,
+                                                dbg.ctypes.data if debug else None, 0))
         return (fov, dbg) if debug else fov
 
     def synchronize(self):

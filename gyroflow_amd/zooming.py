@@ -5,11 +5,12 @@
     # ... FrameTransform.at_timestamp per frame, undistort_clip_params: the reference's recompute-then-render sequence
 
 ``calculate_fovs`` (mod.rs:35-70) patches the parameters (fov_scale = 1, no fovs, output size = source size), runs
-``FovIterative::find_fov`` for every frame — here ONE device call, ``Backend.zoom_fovs`` (gfw_zoom_fovs) — and smooths the
+``FovIterative::find_fov`` for every frame — here ONE device call, ``Backend.zoom_fovs`` (gfw_zoom_fovs), or
+``Backend.zoom_fovs_stab`` (gfw_zoom_fovs_stab) when the parameters carry per-frame ``camera_stab_data`` or ``mesh_correction`` — and smooths the
 series (``warp.zoom_smooth``: static / dynamic / disabled zoom).  The rotations come from the quaternion tracks the backend
 holds (``Backend.set_quaternion_tracks`` / ``set_sync_offsets``): they are the clip's, as for the device matrix builder.
 
-Not covered (as gfw_zoom_fovs): clips with IBIS/OIS data or a lens mesh, keyframed zooming speed.
+Not covered: keyframed zooming speed.
 """
 import numpy as np
 
@@ -46,10 +47,23 @@ def search_inputs(compute_params, timestamps):
     return kp, search, frames
 
 
+def frame_tables(compute_params, timestamps):
+    """camera_stab_data.get(frame) and mesh_correction.get(frame) of every searched frame: ([dict or None] or None, [mesh or None] or None)"""
+    def table(src):
+        if src is None:
+            return None
+        return [src[frame] if 0 <= frame < len(src) else None for frame, _ in timestamps]
+    return table(getattr(compute_params, "camera_stab_data", None)), table(getattr(compute_params, "mesh_correction", None))
+
+
 def calculate_fovs(compute_params, timestamps, method, backend):
     """``calculate_fovs`` (zooming/mod.rs:35-70) -> (fovs, minimal_fovs), two float64 arrays of len(timestamps)."""
     if len(timestamps) == 0:
         return np.zeros(0), np.zeros(0)
     kp, search, frames = search_inputs(compute_params, timestamps)
-    minimal = backend.zoom_fovs(kp, search, frames)
+    stabs, meshes = frame_tables(compute_params, timestamps)
+    if stabs is None and meshes is None:
+        minimal = backend.zoom_fovs(kp, search, frames)
+    else:
+        minimal = backend.zoom_fovs_stab(kp, search, frames, stabs=stabs, meshes=meshes)
     return warp.zoom_smooth(minimal, compute_params.adaptive_zoom_window, compute_params.scaled_fps, int(method), compute_params.trim_ranges)

@@ -437,6 +437,12 @@ int   gfw_set_sync_offsets(gfw_ctx *ctx, double duration_ms, const int64_t *time
  * to be passed as `matrices` with GFW_OPT_MATRICES_ON_DEVICE = 2.  Amortises the builder's latency and needs no
  * cross-stream synchronisation: the per-frame cost in a render loop drops to ~1 us of GPU time. */
 int   gfw_build_matrices_batch(gfw_ctx *ctx, const gfw_frame_timing *timings, int count, float **out_ptrs);
+/* The same for a clip with IBIS/OIS splines: stabs[i] is frame i's camera_stab_data entry or NULL (stabs itself may be NULL: no
+ * frame has one).  Frame i's table equals gfw_build_matrices_stab(ctx, &timings[i], stabs[i], ...)'s bit for bit.  The control
+ * points of all frames travel in one pinned staging copy in front of the launch; limits, ordering, the two alternating batches
+ * and the error codes are gfw_build_matrices_batch's, and a rejected frame is named in gfw_last_error(). */
+int   gfw_build_matrices_batch_stab(gfw_ctx *ctx, const gfw_frame_timing *timings, const gfw_frame_stab *const *stabs,
+                                    int count, float **out_ptrs);
 
 /* ---- STMap coordinate export ("next" row: src/core/stmap.rs:87-109, :127-137) ----------------------------
  * The "undist" ST map: for every pixel (x, y) of a width x height map, the rolling-shutter row pick followed by
@@ -492,7 +498,7 @@ int   gfw_undistort_points(gfw_ctx *ctx, const gfw_kernel_params *params, const 
  * One launch, in order on the context's stream; with device outputs an asynchronous context returns without waiting.  n_frames = 0 succeeds and writes nothing.
  * NOT covered, rejected with GFW_ERR_INVALID_ARGUMENT: clips with per-frame IBIS/OIS shifts (frame_transform.rs:412-435) or a
  * lens mesh / focal-plane distortion data (params->flags has HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA): such a clip keeps
- * mapping its outline with gfw_undistort_points. */
+ * mapping its outline with gfw_undistort_points — or calls gfw_zoom_fovs_stab below. */
 typedef struct gfw_zoom_frame {
     double timestamp_ms;               /* frame centre */
     double per_frame_time_offset_ms;   /* file_metadata.per_frame_time_offsets[frame] */
@@ -502,7 +508,8 @@ typedef struct gfw_zoom_frame {
     double video_rotation_deg;
     double zoom_center[2];             /* adaptive_zoom_center_offset, or its keyframed value at the frame (fov_iterative.rs:41-57) */
     double lens_correction_amount;     /* lens_correction_amount, or its keyframed value */
-    int32_t suppress_rotation;         /* 0 or 1 */
+    int32_t suppress_rotation;         /* 0 or 1; gfw_zoom_fovs_stab also takes 2 = 1 with params.frame_readout_time == 0.0: the frame's
+                                          shifts are dropped (frame_transform.rs:433-435), as in gfw_frame_timing */
     int32_t reserved;                  /* 0 */
 } gfw_zoom_frame;
 typedef struct gfw_zoom_search {
@@ -514,6 +521,29 @@ typedef struct gfw_zoom_search {
 int   gfw_zoom_fovs(gfw_ctx *ctx, const gfw_kernel_params *params, const gfw_zoom_search *search,
                     const gfw_zoom_frame *frames, int n_frames, const float *rotations,
                     double *fov_minimal, double *debug_points, int out_on_device);
+/* The search for clips with in-body / optical stabiliser data (file_metadata.camera_stab_data) and a per-frame lens mesh
+ * (file_metadata.mesh_correction): at_timestamp_for_points' shifts (frame_transform.rs:412-435) and undistort_points' mesh and
+ * focal-plane-distortion steps (cpu_undistort.rs:712-760) per outline point, in the same single launch.
+ *   stabs      NULL, or [n_frames] pointers: camera_stab_data.get(frame), NULL = None.  A present entry whose splines cannot be
+ *              evaluated gives a shift of zeros, which is NOT the same as no shift (the shift's arithmetic rounds).  The scale is
+ *              width / crop_w / pitch_x, height / crop_h / pitch_y — no framebuffer sign, no sensor-height flip: those belong to
+ *              the matrix path — the spline position map_coord(y, 0, height, crop_y, crop_y + crop_h) + offset with the
+ *              point's own y (under horizontal readout too), the roll (z / 1000).to_radians() as f32, cos / sin of +angle.
+ *              A frame with rolling shutter shifts every point of the outline and of each refinement; a frame without has ONE
+ *              shift, evaluated at y = 0, and shift_per_point.get(index) hands it to point 0 of each mapped set only — as written.
+ *   meshes / mesh_lens   NULL, or [n_frames]: mesh_correction[frame].0 (the DISTORTING mesh, f64) and its length (0 = none; at
+ *              most 839).  Consecutive frames naming the same pointer and length share one validation and one upload.
+ *   params->flags   HAS_IBIS_DATA / HAS_MESH_DATA / HAS_FPD_DATA are accepted and not consulted: the data decides, as on the
+ *              reference's CPU path.
+ * Everything else — rotations (caller-given ones still require every readout time to be 0), outputs, ordering — is
+ * gfw_zoom_fovs's; with stabs and meshes NULL the call IS gfw_zoom_fovs (same kernels, same bits).  Rejected with
+ * GFW_ERR_INVALID_ARGUMENT and the frame named in gfw_last_error(), outputs untouched: negative counts, a count without its
+ * array, descending spline positions, zero crop or pitch, a mesh that is NULL, longer than 839 values or inconsistent with its
+ * own header, suppress_rotation outside 0..2. */
+int   gfw_zoom_fovs_stab(gfw_ctx *ctx, const gfw_kernel_params *params, const gfw_zoom_search *search,
+                         const gfw_zoom_frame *frames, int n_frames, const float *rotations,
+                         const gfw_frame_stab *const *stabs, const double *const *meshes, const size_t *mesh_lens,
+                         double *fov_minimal, double *debug_points, int out_on_device);
 /* The second half, on the host in f64 with the reference's operation order (zooming/mod.rs:55-68, zoom_dynamic.rs); needs no
  * context and no GPU.  adaptive_zoom_window < -0.9: static zoom (every fov = the minimum); > 0.0001: dynamic zoom over
  * frames = floor(window * scaled_fps) made odd — method 0 Gaussian filter (pad_edge, min_rolling, pad_edge, convolve with the

@@ -304,5 +304,38 @@ inline std::pair<std::vector<double>, std::vector<double>> calculate_fovs(gfw_ct
     if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
     return {fovs, trimmed};
 }
+// The same for a clip with stabiliser data and lens meshes, over gfw_zoom_fovs_stab: `stabs` = file_metadata.camera_stab_data, one pointer per frame (nullptr = no
+// entry) or empty; `meshes` = mesh_correction[frame].0, the distorting mesh, one vector per frame (empty = none) or empty.  Consecutive frames whose meshes are equal
+// share one upload when they are given as the same vector object through `mesh_of_frame` (index into `meshes` per frame; empty = frame f names meshes[f]).
+inline std::pair<std::vector<double>, std::vector<double>> calculate_fovs(gfw_ctx *ctx, const KernelParams &params, const gfw_zoom_search &search,
+                                                                          const std::vector<gfw_zoom_frame> &frames, const std::vector<const gfw_frame_stab *> &stabs,
+                                                                          const std::vector<std::vector<double>> &meshes, double adaptive_zoom_window, double scaled_fps,
+                                                                          ZoomMethod method, const std::vector<std::pair<double, double>> &trim_ranges = {},
+                                                                          const float *rotations = nullptr, const std::vector<int> &mesh_of_frame = {}) {
+    const int n = (int)frames.size();
+    std::vector<double> minimal((size_t)n), fovs((size_t)n), trimmed((size_t)n), ranges;
+    if (n == 0) return {fovs, minimal};
+    if ((!stabs.empty() && (int)stabs.size() != n) || (!mesh_of_frame.empty() && (int)mesh_of_frame.size() != n) || (mesh_of_frame.empty() && !meshes.empty() && (int)meshes.size() != n))
+        throw GyroflowCoreError(GyroflowCoreError::from_code(GFW_ERR_INVALID_ARGUMENT), "calculate_fovs: one stabiliser entry and one mesh per frame");
+    std::vector<const double *> mesh_ptrs;
+    std::vector<size_t> mesh_lens;
+    if (!meshes.empty()) {
+        mesh_ptrs.resize((size_t)n); mesh_lens.resize((size_t)n);
+        for (int f = 0; f < n; ++f) {
+            const int m = mesh_of_frame.empty() ? f : mesh_of_frame[(size_t)f];
+            if (m >= (int)meshes.size()) throw GyroflowCoreError(GyroflowCoreError::from_code(GFW_ERR_INVALID_ARGUMENT), "calculate_fovs: mesh_of_frame names no mesh");
+            mesh_ptrs[(size_t)f] = (m < 0 || meshes[(size_t)m].empty()) ? nullptr : meshes[(size_t)m].data();
+            mesh_lens[(size_t)f] = m < 0 ? 0 : meshes[(size_t)m].size();
+        }
+    }
+    int rc = gfw_zoom_fovs_stab(ctx, &params, &search, frames.data(), n, rotations, stabs.empty() ? nullptr : stabs.data(),
+                                mesh_ptrs.empty() ? nullptr : mesh_ptrs.data(), mesh_lens.empty() ? nullptr : mesh_lens.data(), minimal.data(), nullptr, 0);
+    if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+    for (const auto &r : trim_ranges) { ranges.push_back(r.first); ranges.push_back(r.second); }
+    rc = gfw_zoom_smooth(minimal.data(), n, adaptive_zoom_window, scaled_fps, (int)method, ranges.empty() ? nullptr : ranges.data(), (int)trim_ranges.size(),
+                         fovs.data(), trimmed.data());
+    if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+    return {fovs, trimmed};
+}
 
 }  // namespace gyroflow

@@ -8,6 +8,10 @@ uses — two ways:
   (b) gfw_zoom_fovs for all frames in one call (host outputs: wall time includes the descriptor upload and the result download), and the kernel time alone from
       hipEvents around an asynchronous call with device outputs.
 Prints both, frames per second, and how far the two results differ.  usage: zoom_bench.py [--frames N] [--frames-a M] [--reps R] [--lca A] [--out FILE]
+                                                                             [--stab] [--mesh none|shared|per-frame]
+--stab gives every frame IBIS/OIS splines (19 control points each, another phase per frame), --mesh a 9 x 9 lens mesh with a focal-plane-distortion block —
+one array for the whole clip (uploaded once) or one per frame: route (a) then packs each round's shifts on the host (frame_transform.rs:412-435) and hands them and
+the frame's mesh to gfw_undistort_points, route (b) is gfw_zoom_fovs_stab.  Without either the tool runs exactly what it ran before them.
 (GFW_LIBRARY selects an A/B build of the library.)"""
 import argparse
 import json
@@ -69,6 +73,60 @@ def rotations_for(org, smo, nk, ts, pts):
     return (nk[None, :, :] @ r).reshape(-1, 9).astype(np.float32)
 
 
+def stab_for(k):
+    """camera_stab_data[frame k]: a 6000 x 3376 sensor cropped to 5760 x 3240, a few pixels of shift at 4K"""
+    pos = np.linspace(-200.0, 3900.0, 19)
+    ph = 0.37 * k
+    ibis = np.stack([pos, 40.0 * np.sin(pos * 0.004 + ph), -40.0 * np.cos(pos * 0.003 - ph), 100.0 * np.sin(pos * 0.002 + 0.4 + ph)], axis=1)
+    ois = np.stack([pos, 15.0 * np.cos(pos * 0.005 - ph), 15.0 * np.sin(pos * 0.006 + ph), np.zeros_like(pos)], axis=1)
+    return {"offset": 12.5, "sensor_size": (6000.0, 3376.0), "crop_area": (120.0, 68.0, 5760.0, 3240.0), "pixel_pitch": (3.0, 3.0),
+            "width": float(W), "height": float(H), "ibis": ibis, "ois": ois}
+
+
+def mesh_for(k):
+    """a Sony-style mesh block (header, 9 x 9 grid, cubic coefficients per row for x and y, focal-plane-distortion data), f64; k varies the coefficients"""
+    n = 9
+    m = np.zeros(839, dtype=np.float64)
+    o = 9 + n * n * 2 + n * n * 4 * 2
+    m[0:9] = (o, n, n, W, H, 0.0, 0.0, W, H)
+    base = 9 + n * n * 2
+    i, j = np.meshgrid(np.arange(n), np.arange(n))
+    for comp, (a, b, c, d) in enumerate(((i * W / 8.0 + 6.0 * np.sin(0.7 * i + 0.3 * j + 0.01 * k), 1.0 + 0.01 * np.cos(i + j), 1e-5 * (i - 4), -1e-9 * (j - 3)),
+                                         (j * H / 8.0 + 5.0 * np.cos(0.5 * i - 0.2 * j + 0.01 * k), 0.004 * np.sin(i - j), 2e-6 * (j - 4), 1e-10 * (i - 2)))):
+        for jj in range(n):
+            rb = base + comp * n * n * 4 + jj * n * 4
+            m[rb:rb + n], m[rb + n:rb + 2 * n], m[rb + 2 * n:rb + 3 * n], m[rb + 3 * n:rb + 4 * n] = a[jj], b[jj], c[jj], d[jj]
+    m[o] = 1.0
+    m[o + 4:o + 20:2] = 0.002 * (np.arange(8) - 3)
+    m[o + 5:o + 20:2] = -0.001 * (np.arange(8) - 4)
+    return m
+
+
+def catmull_rom_many(pts, t):
+    """CatmullRom::interpolate (gyro_source/splines.rs:22-84) at an array of positions -> [n][3] (zeros where None)"""
+    pos, n = pts[:, 0], len(pts)
+    lo = np.searchsorted(pos, t, side="left")
+    hit = (lo < n) & (pos[np.minimum(lo, n - 1)] == t)
+    lower = np.where(hit, lo, lo - 1)
+    ok = np.where(hit, lo != n - 1, (lo < n) & (lo != 0)) & (lower + 1 < n) & (lower >= 0)
+    lw = np.clip(lower, 0, n - 2)
+    a, b = pts[lw, 1:], pts[lw + 1, 1:]
+    k = ((t - pos[lw]) / (pos[lw + 1] - pos[lw]))[:, None]
+    x = np.where((lw <= 0)[:, None], a * 2.0 - b, pts[np.maximum(lw - 1, 0), 1:])
+    y = np.where((lw + 2 >= n)[:, None], b * 2.0 - a, pts[np.minimum(lw + 2, n - 1), 1:])
+    v = ((((a * 3.0 - x) - b * 3.0) + y) * 0.5) * k * k * k + ((b - x) * 0.5) * k + a + (((b * 4.0 + a * -5.0 + x + x) - y) * 0.5) * k * k
+    return np.where(ok[:, None], v, 0.0)
+
+
+def shifts_for(stab, pts):
+    """at_timestamp_for_points' shifts (frame_transform.rs:412-432) of one round's points (rolling shutter: one per point) -> [n][5] f32"""
+    ca, pp = stab["crop_area"], stab["pixel_pitch"]
+    sx, sy = W / ca[2] / pp[0], H / ca[3] / pp[1]
+    ys = pts[:, 1].astype(np.float64) * ((ca[1] + ca[3]) - ca[1]) / float(H) + ca[1] + stab["offset"]
+    s, o = catmull_rom_many(stab["ibis"], ys), catmull_rom_many(stab["ois"], ys)
+    return np.stack([s[:, 0] * sx, s[:, 1] * sy, (s[:, 2] / 1000.0) * (np.pi / 180.0), o[:, 0] * sx, o[:, 1] * sy], axis=1).astype(np.float32)
+
+
 def rect_points():
     w, h = f32(W), f32(H)
     ws, hs = f32(w / f32(30)), f32(h / f32(30))
@@ -88,20 +146,23 @@ def fold(poly, m, a):
     return idx, m
 
 
-def route_a(be, kp, org, smo, nk, timestamps, rect):
+def route_a(be, kp, org, smo, nk, timestamps, rect, stabs=None, meshes=None):
     """-> (fovs, seconds inside gfw_undistort_points, calls)"""
     a = f32(f32(H) / f32(W))
     fovs, t_calls, calls = [], 0.0, 0
+    frame = 0
 
     def mapped(ts, pts):
         nonlocal t_calls, calls
         rot = rotations_for(org, smo, nk, ts, pts)
+        sh = shifts_for(stabs[frame], pts) if stabs is not None else None
+        mesh = meshes[frame] if meshes is not None else None
         t0 = time.perf_counter()
-        out = be.undistort_points(kp, rot, points=pts, index_mode=abi.POINT_INDEX_PER_POINT)
+        out = be.undistort_points(kp, rot, points=pts, shifts=sh, index_mode=abi.POINT_INDEX_PER_POINT, mesh=mesh)
         t_calls += time.perf_counter() - t0
         calls += 1
         return out
-    for ts in timestamps:
+    for frame, ts in enumerate(timestamps):
         poly = mapped(ts, rect)
         idx, m = None, (f32(1000000.0), f32(f32(1000000.0) * a))
         for _ in range(1, 5):
@@ -126,6 +187,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--lca", type=float, default=1.0, help="lens_correction_amount of every frame (< 1: the Newton inverse of the blend per point)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--stab", action="store_true", help="every frame has IBIS/OIS splines: per-point shifts")
+    ap.add_argument("--mesh", choices=("none", "shared", "per-frame"), default="none", help="lens mesh + focal-plane distortion: one array for the clip, or one per frame")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     n = args.frames
@@ -148,26 +211,38 @@ def main():
         for i, v in enumerate(nk.reshape(9)):
             f.new_k[i] = v
     rect = rect_points()
-    result = {"frames": n, "frames_a": min(args.frames_a, n), "lens_correction_amount": args.lca, "library": os.environ.get("GFW_LIBRARY", ""), "runs": []}
+    stabs = [stab_for(k) for k in range(n)] if args.stab else None
+    meshes = None
+    if args.mesh == "shared":
+        meshes = [mesh_for(0)] * n
+    elif args.mesh == "per-frame":
+        meshes = [mesh_for(k) for k in range(n)]
+    with_data = stabs is not None or meshes is not None
+
+    def search_all(**kw):
+        if with_data:
+            return be.zoom_fovs_stab(kp, search, frames, stabs=stabs, meshes=meshes, **kw)
+        return be.zoom_fovs(kp, search, frames, **kw)
+    result = {"frames": n, "stab": bool(args.stab), "mesh": args.mesh, "frames_a": min(args.frames_a, n), "lens_correction_amount": args.lca, "library": os.environ.get("GFW_LIBRARY", ""), "runs": []}
     try:
         be.set_quaternion_tracks(org, smo)
-        be.zoom_fovs(kp, search, frames)                                      # warm-up: allocations, code object load
-        route_a(be, kp, org, smo, nk, timestamps[:4], rect)
+        search_all()                                                          # warm-up: allocations, code object load
+        route_a(be, kp, org, smo, nk, timestamps[:4], rect, stabs, meshes)
         d_out = torch.zeros(n, dtype=torch.float64, device=dev)
         for rep in range(args.reps):
             na = min(args.frames_a, n)
             t0 = time.perf_counter()
-            fa, t_calls, calls = route_a(be, kp, org, smo, nk, timestamps[:na], rect)
+            fa, t_calls, calls = route_a(be, kp, org, smo, nk, timestamps[:na], rect, stabs, meshes)
             wall_a = time.perf_counter() - t0
             t0 = time.perf_counter()
-            fb = be.zoom_fovs(kp, search, frames)
+            fb = search_all()
             wall_b = time.perf_counter() - t0
             stream = torch.cuda.current_stream(dev)
             be.set_stream(stream.cuda_stream)
             be.set_option(abi.OPT_SYNCHRONOUS, 0)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
-            be.zoom_fovs(kp, search, frames, out_ptr=d_out.data_ptr())
+            search_all(out_ptr=d_out.data_ptr())
             e1.record(stream)
             e1.synchronize()
             kernel_ms = e0.elapsed_time(e1)
@@ -183,7 +258,7 @@ def main():
     finally:
         be.close()
     ok = all(r["b_wall_s"] < r["a_calls_extrapolated_s"] for r in result["runs"])
-    print("gfw_zoom_fovs for all %d frames takes less wall time than the gfw_undistort_points calls of route (a) alone, extrapolated: %s" % (n, ok))
+    print("%s for all %d frames takes less wall time than the gfw_undistort_points calls of route (a) alone, extrapolated: %s" % ("gfw_zoom_fovs_stab" if with_data else "gfw_zoom_fovs", n, ok))
     print(json.dumps(result))
     if args.out:
         with open(args.out, "w") as fo:
