@@ -215,10 +215,11 @@ class Backend:
             self._check(self.lib.gfw_build_matrices_batch_stab(self.ctx, arr, table, n, ptrs))
         return [p for p in ptrs]
 
-    def stmap_undistort(self, params, matrices, width, height, mesh=None):
-        """STMap 'undist' coordinates (stmap.rs:87-109) as a float32 array [height][width][2] (0 where None)."""
+    def stmap_undistort(self, params, matrices, width, height, mesh=None, fill=None):
+        """STMap 'undist' coordinates (stmap.rs:87-109) as a float32 array [height][width][2].  Where the projection is None an element keeps what the
+        array started from: the 32-bit pattern ``fill`` (default 0, what parallel_exr leaves)."""
         m = np.ascontiguousarray(matrices, dtype=np.float32)
-        coords = np.zeros((height, width, 2), dtype=np.float32)
+        coords = np.full((height, width, 2), fill or 0, dtype=np.uint32).view(np.float32)
         meshp, meshn = None, 0
         if mesh is not None and len(mesh):
             mesh = np.ascontiguousarray(mesh, dtype=np.float32)

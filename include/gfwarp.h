@@ -448,7 +448,10 @@ int   gfw_build_matrices_batch_stab(gfw_ctx *ctx, const gfw_frame_timing *timing
  * The "undist" ST map: for every pixel (x, y) of a width x height map, the rolling-shutter row pick followed by
  * rotate_and_distort, written as two f32 (source x, y in pixels) instead of being sampled.  `params` is the
  * KernelParams stmap.rs builds (width/height/output_* = map size, flags = HAS_DIGITAL_LENS | HORIZONTAL_RS).
- * Pixels whose projection is None are left untouched (parallel_exr leaves them 0).  Bit-exact vs the CPU closure. */
+ * Pixels whose projection is None are left untouched (parallel_exr leaves them 0).  Bit-exact vs the CPU closure.
+ * matrix_count may not exceed the rows of the plane the context was created for (its height; its width under a horizontal
+ * rolling shutter) — GFW_ERR_BUFFER_SIZE_MISMATCH, "Buffer size mismatch matrices!", nothing written — so a per-row map larger
+ * than the source (stmap.rs sizes the undist map new_width x new_height) needs a context created at the map's size. */
 int   gfw_stmap_undistort(gfw_ctx *ctx, const gfw_kernel_params *params, const float *matrices, int matrix_count,
                           const float *mesh, size_t mesh_len, int width, int height, float *coords, int coords_on_device);
 

@@ -583,14 +583,28 @@ class _Lenses:
         self.model, self.digital = model, digital
 
 
-def stmap_undistort(params, model, digital, matrices, width, height):
-    """gfw_stmap_undistort through the host-interpreted gfw_stmap_kernel -> float32 [height][width][2] (0 where the ray is rejected)."""
-    coords = np.zeros((height, width, 2), dtype=np.float32)
+def stmap_undistort(params, model, digital, matrices, width, height, mesh=None, fill=None):
+    """gfw_stmap_undistort through the host-interpreted gfw_stmap_kernel -> float32 [height][width][2]; where the ray is rejected an element keeps the
+    32-bit pattern `fill` it started from (default 0).  `mesh`: None or the f32 lens mesh (run_plane's way: it also picks the <-1> instantiation for a
+    fisheye clip, emu_kernels_driver.inc).  Under GUARD the map, the matrix table and the mesh lie against inaccessible pages."""
+    n = height * width * 2
+    whole = np.full(n + 64, fill or 0, dtype=np.uint32)                       # (64 elements of slack behind the map: a lane past its edge fails the run, not the process)
+    coords = whole[:n].view(np.float32).reshape(height, width, 2)
     com = common_for(_Lenses(model, digital), params)
+    keep = None
+    if mesh is not None and len(mesh):
+        keep = np.ascontiguousarray(mesh, dtype=np.float32)
+        if GUARD:
+            keep = guarded(keep, GUARD == "end").view(np.float32)
+        com.mesh, com.mesh_len = keep.ctypes.data, keep.size
     packed = warp.pack_matrices(matrices)
+    if GUARD:
+        packed = guarded(packed, GUARD == "end").view(np.float32)
+        coords = guarded(coords, GUARD == "end").view(np.float32).reshape(height, width, 2)
     rc = _kernels_lib().gfw_emu_stmap(C.cast(C.byref(params), C.c_void_p), C.cast(C.byref(com), C.c_void_p), packed.ctypes.data, width, height, coords.ctypes.data)
     assert rc == 0
-    return coords
+    assert np.all(whole[n:] == (fill or 0)), "gfw_stmap_kernel wrote behind the map"
+    return np.array(coords)
 
 
 def undistort_points(params, model, digital, rotations, points=None, grid=None, shifts=None, index_mode=0, mesh=None):

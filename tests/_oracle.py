@@ -79,13 +79,13 @@ def undistort_coord(params, model, digital, matrices, x, y, mesh=None):
     return bool(out[0]), float(out[1]), float(out[2])
 
 
-def run_frame(frame, nthreads=0):
-    """Oracle over every plane of a SyntheticFrame; returns list of output arrays (copies)."""
+def run_frame(frame, nthreads=0, mesh=None):
+    """Oracle over every plane of a SyntheticFrame; returns list of output arrays (copies).  ``mesh``: None or the f32 lens mesh."""
     outs = []
     for pl in frame.planes:
         dst = pl["dst"].copy()
         st = undistort_image(pl["src"], pl["size"], dst, pl["out_size"], pl["params"], pl["pixel_type"],
-                             frame.model, frame.digital, frame.matrices, nthreads=nthreads)
+                             frame.model, frame.digital, frame.matrices, mesh=mesh, nthreads=nthreads)
         assert st == 1, "oracle returned %d" % st
         outs.append(dst)
     return outs
@@ -121,11 +121,16 @@ def run_frame_fast(frame, nthreads=0):
     return r.run()
 
 
-def stmap_undistort(params, model, digital, matrices, width, height, nthreads=0):
-    """Oracle restatement of the stmap.rs 'undist' closure; returns float32 [height][width][2] (0 where None)."""
+def stmap_undistort(params, model, digital, matrices, width, height, nthreads=0, mesh=None, fill=None):
+    """Oracle restatement of the stmap.rs 'undist' closure; returns float32 [height][width][2].  Where the projection is None an element keeps what it
+    started from: the 32-bit pattern ``fill`` (default 0, what parallel_exr leaves).  ``mesh``: None or the f32 lens mesh."""
     m = np.ascontiguousarray(matrices, dtype=np.float32)
-    coords = np.zeros((height, width, 2), dtype=np.float32)
-    lib().gfw_oracle_stmap_undistort(C.byref(params), model, digital, m.ctypes.data, None, 0, width, height, coords.ctypes.data, nthreads)
+    coords = np.full((height, width, 2), fill or 0, dtype=np.uint32).view(np.float32)
+    mesh_ptr, mesh_len = None, 0
+    if mesh is not None and len(mesh):
+        mesh = np.ascontiguousarray(mesh, dtype=np.float32)
+        mesh_ptr, mesh_len = mesh.ctypes.data, mesh.size
+    lib().gfw_oracle_stmap_undistort(C.byref(params), model, digital, m.ctypes.data, mesh_ptr, mesh_len, width, height, coords.ctypes.data, nthreads)
     return coords
 
 

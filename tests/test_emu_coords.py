@@ -3,6 +3,7 @@
 and tests/test_gpu_points.py (same inputs, bit-identical results; NaN compares equal to NaN)."""
 import json
 import os
+import subprocess
 import sys
 import zlib
 
@@ -16,6 +17,7 @@ import make_golden as G  # noqa: E402
 from gyroflow_amd import abi, synthetic as S  # noqa: E402
 import _emu  # noqa: E402
 import _oracle as O  # noqa: E402
+import _coordcase as K  # noqa: E402
 from test_gpu_lens_models import PHYSICAL, DIGITAL, synthetic_mesh  # noqa: E402
 from test_gpu_points import wild_points, same_bits  # noqa: E402
 from test_oracle_points import points_params  # noqa: E402
@@ -108,3 +110,48 @@ def test_points_lens_correction_branch(model, lca, digital):
     pts = wild_points(w, h, 3000, 13)
     assert same_bits(O.undistort_points(kp, fr.model, fr.digital, fr.rotations, points=pts, index_mode=abi.POINT_INDEX_SINGLE),
                      _emu.undistort_points(kp, fr.model, fr.digital, fr.rotations, points=pts, index_mode=abi.POINT_INDEX_SINGLE))
+
+
+# ---- the undist export's case table (tests/_coordcase.py): rejected rays, the block edge, meshes, digital lenses, IBIS rows, one matrix ------------------
+
+@pytest.mark.parametrize("name", K.NAMES)
+def test_stmap_case_table_from_a_sentinel(name):
+    """Every element starts from a NaN payload and the maps are compared as uint32: what the kernel rejects must keep those bits, what it writes must be
+    the oracle's value, and nothing may land in another pixel (203 x 117 and the shapes around one workgroup: the x / y guards fire in both directions)."""
+    fr, kp, mesh, w, h = K.case(name)
+    ref = K.reference(name)
+    got = _emu.stmap_undistort(kp, fr.model, fr.digital, fr.matrices, w, h, mesh=mesh, fill=K.SENTINEL)
+    assert np.array_equal(ref.view(np.uint32), got.view(np.uint32))
+
+
+def test_stmap_ignores_the_fields_the_closure_does_not_read():
+    """lens_correction_amount, translation2d, input_rotation and background_mode belong to the render: the map of `unread` is rl_gopro's."""
+    assert np.array_equal(K.reference("unread").view(np.uint32), K.reference("rl_gopro").view(np.uint32))
+
+
+def test_stmap_mesh_reaches_the_oracle():
+    """(the helper's `mesh=` is new: a dropped mesh on both sides would compare equal)"""
+    fr, kp, mesh, w, h = K.case("mesh_fisheye")
+    plain = O.stmap_undistort(kp, fr.model, fr.digital, fr.matrices, w, h, fill=K.SENTINEL)
+    assert np.abs(plain - K.reference("mesh_fisheye")).max() > 0.25
+
+
+@pytest.mark.parametrize("place", ["end", "start"])
+def test_stmap_small_shapes_between_guard_pages(place):
+    """The shapes around one workgroup with the map, the matrix table and the mesh flush against an inaccessible page (tests/emu/guard_coords.py, one process per
+    placement: a store by a lane past the map's edge ends it with SIGSEGV), and the maps still the oracle's."""
+    r = subprocess.run([sys.executable, os.path.join(HERE, "emu", "guard_coords.py"), place] + K.SMALL + ["mesh_fisheye"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, "gfw_stmap_kernel touched memory outside its buffers (%s guard): rc %d\n%s" % (place, r.returncode, r.stderr[-1500:])
+    assert r.stdout.split() == ["OK"] * (len(K.SMALL) + 1), r.stdout[-500:]
+
+
+def test_dist_grid_with_fewer_rotations_than_rows():
+    """rotation_count = 3 under _PER_ROW on a 203 x 117 grid: rows 3 and above take rotation 0 (`rot_per_point.get(index).unwrap_or(&rr)`), not the last one."""
+    fr = K.case("ibis_rs")[0]
+    kp = points_params(fr)
+    rot = fr.rotations[[0, 58, 116]]
+    ref = O.undistort_points(kp, fr.model, 0, rot, grid=(K.W, K.H), index_mode=abi.POINT_INDEX_PER_ROW)
+    assert same_bits(ref, _emu.undistort_points(kp, fr.model, 0, rot, grid=(K.W, K.H), index_mode=abi.POINT_INDEX_PER_ROW))
+    single = O.undistort_points(kp, fr.model, 0, rot[:1], grid=(K.W, K.H), index_mode=abi.POINT_INDEX_SINGLE)
+    assert same_bits(ref[3:], single[3:]) and np.abs(ref[1:3] - single[1:3]).max() > 0.01
+    assert np.abs(ref[3:] - O.undistort_points(kp, fr.model, 0, rot[2:], grid=(K.W, K.H), index_mode=abi.POINT_INDEX_SINGLE)[3:]).max() > 0.01

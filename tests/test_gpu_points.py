@@ -160,3 +160,51 @@ def test_points_argument_errors():
         assert e.value.code == abi.ERR_INVALID_ARGUMENT
     finally:
         be.close()
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257])
+def test_points_into_device_memory(n):
+    """out_on_device = 1 around the 256-lane workgroup: bit-equal to the host-output call and to the oracle, and the 64 elements behind the n results keep
+    the NaN payload they started from (a lane past n must not store)."""
+    import ctypes as C
+    import torch
+    sentinel, tail = 0x7FC0BEEF, 64
+    w, h = 203, 117
+    fr = S.SyntheticFrame("YUV422P16LE", w, h, seed=131, fov=1.3)
+    kp = points_params(fr)
+    pts = np.ascontiguousarray(wild_points(w, h, 264, 17)[:n])
+    rot = np.ascontiguousarray(fr.rotations[np.arange(n) % h])
+    ref = O.undistort_points(kp, fr.model, 0, rot, points=pts, index_mode=abi.POINT_INDEX_PER_POINT)
+    dev = torch.device("cuda", 0)
+    out = torch.full((n * 2 + tail,), sentinel, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)                              # (filled on torch's stream, written on the context's)
+    be = backend_for(fr)
+    try:
+        host = be.undistort_points(kp, rot, points=pts, index_mode=abi.POINT_INDEX_PER_POINT)
+        rc = be.lib.gfw_undistort_points(be.ctx, C.byref(kp), pts.ctypes.data, n, 0, rot.ctypes.data, n, None, abi.POINT_INDEX_PER_POINT, None, 0, out.data_ptr(), 1)
+        assert rc == 0, be.lib.gfw_last_error()
+        got = out.cpu().numpy().view(np.uint32)              # the call is synchronous: nothing to wait for
+        assert warp.Backend.last_backend_of(be) == "points"
+    finally:
+        be.close()
+    dev_out = got[:n * 2].view(np.float32).reshape(n, 2)
+    assert same_bits(ref, host) and np.array_equal(host.view(np.uint32), dev_out.view(np.uint32))
+    assert np.all(got[n * 2:] == sentinel)
+
+
+def test_dist_grid_with_fewer_rotations_than_rows():
+    """rotation_count = 3 under _PER_ROW on a 203 x 117 grid: rows 3 and above take rotation 0 (`rot_per_point.get(index).unwrap_or(&rr)`), not the last one
+    (tests/test_emu_coords.py runs the same through the interpreter)."""
+    w, h = 203, 117
+    fr = S.SyntheticFrame("YUV422P16LE", w, h, seed=108, fov=1.2)
+    kp = points_params(fr)
+    rot = fr.rotations[[0, 58, 116]]
+    ref = O.undistort_points(kp, fr.model, 0, rot, grid=(w, h), index_mode=abi.POINT_INDEX_PER_ROW)
+    single = O.undistort_points(kp, fr.model, 0, rot[:1], grid=(w, h), index_mode=abi.POINT_INDEX_SINGLE)
+    assert same_bits(ref[3:], single[3:]) and np.abs(ref[1:3] - single[1:3]).max() > 0.01
+    be = backend_for(fr)
+    try:
+        got = be.undistort_points(kp, rot, grid=(w, h), index_mode=abi.POINT_INDEX_PER_ROW)
+    finally:
+        be.close()
+    assert same_bits(ref, got)
