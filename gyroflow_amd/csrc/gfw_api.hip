@@ -18,6 +18,7 @@
 #include "../../include/gfwarp.h"
 #include "../../include/gfwarp_testing.h"
 #include "gfw_launch.h"
+#include "gfw_hostmem.h"
 #include "gfw_frame.h"
 #include "gfw_matrices.h"
 #include "gfw_zoom.h"
@@ -55,19 +56,6 @@ static const int   PIX_BPP[GFW_PIX_COUNT]   = {1, 2, 3, 4, 4, 6, 8, 8, 16, 8, 4,
 static const int   PIX_N[GFW_PIX_COUNT]     = {1, 1, 3, 4, 4, 3, 4, 4, 4, 4, 1, 2, 2};
 static const float PIX_MAX[GFW_PIX_COUNT]   = {255.f, 65535.f, 255.f, 255.f, 255.f, 65535.f, 65535.f, 65535.f, 0.f, 0.f, 0.f, 255.f, 65535.f};
 
-struct DevBuf {
-    void *ptr = nullptr; size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr; cap = 0;
-        hipError_t e = hipMalloc(&ptr, n);
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; cap = 0; }
-};
-
 // The fused kernel's instantiation, decided by build_yuv_args: gfw_launch_yuv's template arguments, jit_build_defs' leading definitions (all int: compared as memory)
 struct FusedShape {
     int kind = 0, taps = 2, n0 = 1;              // sample kind (1 = u8, 2 = u16, 3 = f16, 4 = f32), sampler taps (2, 4, 8), channels of plane 0
@@ -91,12 +79,11 @@ struct gfw_ctx {
     size_t src_len = 0, dst_len = 0;              // sizes declared at create (opencl.rs:287-293)
     std::vector<DevBuf> stage_src, stage_dst;      // per-plane staging for HOST buffers
     DevBuf d_mesh;
-    // per-row matrices: ring of (pinned host, device) slots so that an asynchronous caller can enqueue several frames;
-    // uploads run on their own stream and overlap the previous frame's kernel.
-    struct MatSlot { float *h = nullptr; float *d = nullptr; hipEvent_t copied = nullptr, done = nullptr; bool used = false; };
+    // per-row matrices: ring of (pinned host, device) slots so that an asynchronous caller can enqueue several frames; uploads run on their own stream and
+    // overlap the previous frame's kernel: mat_copied[slot] hands the copy over to the context's stream, the slot is free again behind the kernel that read it
     static constexpr int kMatSlots = 4;
-    MatSlot mslots[kMatSlots];
-    int mslot_next = 0, mslot_cur = -1;
+    StagingRing<kMatSlots> mat_ring; Event mat_copied[kMatSlots];
+    int mslot_cur = -1;
     hipStream_t copy_stream = nullptr;
     const char *last_backend = "";
     // certified first pass of the fused kernel: s(rho) table cache
@@ -109,15 +96,15 @@ struct gfw_ctx {
     DevBuf d_pts_in, d_pts_out, d_pts_rot, d_pts_shift, d_pts_mesh;   // gfw_undistort_points staging
     DevBuf d_tracks;                              // quaternion tracks
     // gfw_zoom_fovs: frame descriptors (+ caller-given rotations) staged through pinned memory, results for host outputs
-    DevBuf d_zoom_in, d_zoom_out; void *h_zoom = nullptr; size_t h_zoom_cap = 0; hipEvent_t zoom_copied = nullptr;
+    // (one block, free again behind its COPY: the device side is ordered by the context's stream, and a second asynchronous call does not wait for the first search)
+    StagingRing<1> zoom_ring; DevBuf d_zoom_out;
     // context-owned per-row tables built on the device (gfw_build_matrices): a small ring, built on copy_stream so that
     // frame N+1's table is produced while frame N is being warped; events order builder and consumer both ways
-    struct BuiltSlot { DevBuf buf; hipEvent_t built = nullptr, consumed = nullptr; bool used = false; };   // buf = rows + 4 doubles of builder scratch
+    struct BuiltSlot { DevBuf buf; Event built, consumed; };   // buf = rows + 4 doubles of builder scratch
     DevBuf d_prefix;                              // builder scratch for caller-owned tables
-    // frame descriptors of the builder: pinned host ring + device ring (one entry of up to kMaxBatch descriptors per build)
+    // frame descriptors of the builder: a slot of up to kMaxBatch descriptors per build, free again behind the BUILDER (it is staged on either stream)
     static constexpr int kTimingSlots = 8, kMaxBatch = 64;
-    gfw_frame_timing *h_timings = nullptr; DevBuf d_timings; int timing_next = 0;
-    hipEvent_t timing_copied[kTimingSlots] = {};
+    StagingRing<kTimingSlots> timing_ring;
     // gfw_build_matrices_batch: two context-owned batches of tables, alternated; built in order on the context stream
     DevBuf d_batch[2]; int batch_next = 0;
     static constexpr int kBuiltSlots = 4;
@@ -126,10 +113,9 @@ struct gfw_ctx {
     GfwTracks tracks = {nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, 1.0};
     DevBuf d_offsets;                              // sync offsets of the clip
     // IBIS/OIS control points of the frames being built: a ring of (pinned host, device) pairs, copied on the stream that builds, so that
-    // a clip with stabiliser data keeps the asynchronous table ring (build N+1 while N warps)
-    struct StabSlot { DevBuf d; void *h = nullptr; size_t hcap = 0; hipEvent_t done = nullptr; bool used = false; };
+    // a clip with stabiliser data keeps the asynchronous table ring (build N+1 while N warps); free again behind the builder
     static constexpr int kStabSlots = 4;
-    StabSlot sslots[kStabSlots]; int sslot_next = 0;
+    StagingRing<kStabSlots> stab_ring;
     // run-time specialised kernel (gfw_jit.hip): 0 off; 1 build in the background once the context has seen kJitAfter frames of one
     // clip, warp ahead-of-time meanwhile; 2 build at the first frame and wait for it
     int jit_mode = 1;
@@ -147,8 +133,8 @@ struct gfw_ctx {
     int coalesce_planes = 1;                       // GFW_OPT_COALESCE_PLANES
     long long paired_launches = 0;                 // launches of the per-plane kernel that served two planes (EWA on planar chroma; gfw_debug_paired_launches)
     int coalesce_frames = 1;                       // GFW_OPT_COALESCE_FRAMES: assembled frames held for one clip launch (1 = each frame leaves when complete)
-    hipEvent_t group_done = nullptr;               // orders a member context's stream behind the owner's launch
-    hipEvent_t inputs_ready = nullptr;             // a member context's side of the same frame: what was enqueued on ITS stream before its plane's call (an upload, a decode,
+    Event group_done;                              // orders a member context's stream behind the owner's launch
+    Event inputs_ready;                            // a member context's side of the same frame: what was enqueued on ITS stream before its plane's call (an upload, a decode,
                                                    // a consumer still reading the destination) — the owner's stream waits for it before the fused launch
     std::atomic<int> pending_planes{0};            // planes of this context held in some thread's group (flush_if_pending looks here: the holder may be another thread)
     bool multi_plane = false;                      // this context has been seen as one plane of a multi-plane frame (its calls may be held: GFW_OPT_COALESCE_PLANES = 1)
@@ -160,7 +146,7 @@ struct gfw_ctx {
     gfw_ctx *frame_owner = nullptr; bool needs_order = false;   // a member context: whose stream its planes were launched on, and whether its own stream has been ordered behind that yet
     std::vector<gfw_buffers> held_planes;          // ... and the descriptions those frames were validated with
     bool profile = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;   // recorded, not yet harvested
+    std::vector<std::pair<Event, Event>> ev_pool;  // timed brackets: recorded, not yet harvested
     size_t ev_used = 0;
     double prof_ms = 0.0; int64_t prof_launches = 0, prof_frames = 0;
     std::vector<int> ev_frames;                   // frames covered by each bracketed launch
@@ -186,16 +172,12 @@ static hipError_t audit_counters(gfw_ctx *c) {
 
 static void prof_begin(gfw_ctx *c) {
     if (!c->profile) return;
-    if (c->ev_used == c->ev_pool.size()) {
-        hipEvent_t a, b;
-        (void)hipEventCreate(&a); (void)hipEventCreate(&b);
-        c->ev_pool.emplace_back(a, b);
-    }
-    (void)hipEventRecord(c->ev_pool[c->ev_used].first, c->stream);
+    if (c->ev_used == c->ev_pool.size()) c->ev_pool.emplace_back(Event(hipEventDefault), Event(hipEventDefault));
+    (void)c->ev_pool[c->ev_used].first.record(c->stream);
 }
 static void prof_end(gfw_ctx *c, int frames = 1) {
     if (!c->profile) return;
-    (void)hipEventRecord(c->ev_pool[c->ev_used].second, c->stream);
+    (void)c->ev_pool[c->ev_used].second.record(c->stream);
     if (c->ev_frames.size() <= c->ev_used) c->ev_frames.resize(c->ev_used + 1);
     c->ev_frames[c->ev_used] = frames;
     c->ev_used++;
@@ -203,7 +185,7 @@ static void prof_end(gfw_ctx *c, int frames = 1) {
 static void prof_harvest(gfw_ctx *c) {
     for (size_t i = 0; i < c->ev_used; ++i) {
         float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, c->ev_pool[i].first, c->ev_pool[i].second) == hipSuccess) { c->prof_ms += ms; c->prof_launches++; c->prof_frames += c->ev_frames[i]; }
+        if (hipEventElapsedTime(&ms, c->ev_pool[i].first.ev, c->ev_pool[i].second.ev) == hipSuccess) { c->prof_ms += ms; c->prof_launches++; c->prof_frames += c->ev_frames[i]; }
     }
     c->ev_used = 0;
 }
@@ -307,13 +289,7 @@ gfw_ctx *gfw_create(const gfw_kernel_params *params, int pixel_type, int distort
         ok = ok && hipStreamCreateWithPriority(&c->copy_stream, hipStreamNonBlocking, prio_hi) == hipSuccess;
     }
     ok = ok && c->d_mesh.ensure(GFW_MESH_MAX * sizeof(float)) == hipSuccess;
-    const size_t mat_bytes = (size_t)c->max_matrix_rows * GFW_MAT_STRIDE * sizeof(float);
-    for (int i = 0; i < gfw_ctx::kMatSlots && ok; ++i) {
-        gfw_ctx::MatSlot &s = c->mslots[i];
-        ok = hipHostMalloc((void **)&s.h, mat_bytes) == hipSuccess && hipMalloc((void **)&s.d, mat_bytes) == hipSuccess &&
-             hipEventCreateWithFlags(&s.copied, hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
-    }
+    ok = ok && c->mat_ring.reserve((size_t)c->max_matrix_rows * GFW_MAT_STRIDE * sizeof(float)) == hipSuccess;
     c->stage_src.resize(1); c->stage_dst.resize(1);
     if (ok && buffers->input.kind == GFW_BUF_HOST) ok = c->stage_src[0].ensure(c->src_len) == hipSuccess;
     if (ok && buffers->output.kind == GFW_BUF_HOST) ok = c->stage_dst[0].ensure(c->dst_len) == hipSuccess;
@@ -327,28 +303,12 @@ void gfw_destroy(gfw_ctx *c) {
     (void)hipSetDevice(c->device);
     (void)gfw_flush(c);
     gfw_forget_context(c);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->group_done) (void)hipEventDestroy(c->group_done);
-    if (c->inputs_ready) (void)hipEventDestroy(c->inputs_ready);
-    for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (auto &b : c->stage_src) b.release();
-    for (auto &b : c->stage_dst) b.release();
-    c->d_mesh.release(); c->d_ck_part.release(); c->d_p1_table.release(); c->d_audit.release(); c->d_tracks.release(); c->d_offsets.release(); for (auto &ss : c->sslots) { ss.d.release(); if (ss.h) (void)hipHostFree(ss.h); if (ss.done) (void)hipEventDestroy(ss.done); } c->d_prefix.release(); c->d_timings.release(); c->d_batch[0].release(); c->d_batch[1].release();
+    if (c->stream) (void)hipStreamSynchronize(c->stream);                   // both streams drained: nothing enqueued reads what the members below release
+    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     p1_radial_free(c);
-    if (c->h_timings) (void)hipHostFree(c->h_timings);
-    for (auto &e : c->timing_copied) if (e) (void)hipEventDestroy(e);
-    for (auto &b : c->bslots) { b.buf.release(); if (b.built) (void)hipEventDestroy(b.built); if (b.consumed) (void)hipEventDestroy(b.consumed); }
-    c->d_pts_in.release(); c->d_pts_out.release(); c->d_pts_rot.release(); c->d_pts_shift.release(); c->d_pts_mesh.release();
-    c->d_zoom_in.release(); c->d_zoom_out.release(); if (c->h_zoom) (void)hipHostFree(c->h_zoom); if (c->zoom_copied) (void)hipEventDestroy(c->zoom_copied);
-    if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-    for (auto &s : c->mslots) {
-        if (s.h) (void)hipHostFree(s.h);
-        if (s.d) (void)hipFree(s.d);
-        if (s.copied) (void)hipEventDestroy(s.copied);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
+    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                                                // buffers, pinned memory and events release themselves (gfw_hostmem.h)
 }
 
 int gfw_set_option(gfw_ctx *c, int option, int64_t value) {
@@ -510,38 +470,33 @@ static int upload_matrices(gfw_ctx *c, const float *matrices, int matrix_count, 
     if (c->matrices_on_device == 2) {                                                          // device-resident, already packed
         c->mslot_cur = -1; c->bslot_cur = -1; *d_out = matrices;
         for (int i = 0; i < gfw_ctx::kBuiltSlots; ++i)
-            if (c->bslots[i].buf.ptr == (const void *)matrices && c->bslots[i].built) {         // a table gfw_build_matrices produced
-                HIP_TRY(hipStreamWaitEvent(c->stream, c->bslots[i].built, 0), GFW_ERR_HIP);
+            if (c->bslots[i].buf.ptr == (const void *)matrices && c->bslots[i].built.recorded()) {         // a table gfw_build_matrices produced
+                HIP_TRY(c->bslots[i].built.wait_on(c->stream), GFW_ERR_HIP);
                 c->bslot_cur = i;
             }
         return GFW_OK;
     }
     c->bslot_cur = -1;
-    c->mslot_cur = c->mslot_next;
-    c->mslot_next = (c->mslot_next + 1) % gfw_ctx::kMatSlots;
-    gfw_ctx::MatSlot &s = c->mslots[c->mslot_cur];
-    if (s.used) HIP_TRY(hipEventSynchronize(s.done), GFW_ERR_HIP);          // the kernel that read this slot has finished
+    const size_t bytes = (size_t)matrix_count * GFW_MAT_STRIDE * sizeof(float);
+    StagingSlot *s = nullptr;
+    c->mslot_cur = c->mat_ring.next;
+    HIP_TRY(c->mat_ring.acquire(bytes, c->stream, &s), GFW_ERR_HIP);        // the kernel that read this slot has finished
+    float *h = (float *)s->h.ptr, *d = (float *)s->d.ptr;
     if (c->matrices_on_device) {
-        HIP_TRY(gfw_launch_repack(matrices, s.d, matrix_count, c->stream), GFW_ERR_HIP);
+        HIP_TRY(gfw_launch_repack(matrices, d, matrix_count, c->stream), GFW_ERR_HIP);
     } else {
-        for (int r = 0; r < matrix_count; ++r) pack_row(matrices + (size_t)r * 14, s.h + (size_t)r * GFW_MAT_STRIDE);      // into pinned memory
-        HIP_TRY(hipMemcpyAsync(s.d, s.h, (size_t)matrix_count * GFW_MAT_STRIDE * sizeof(float), hipMemcpyHostToDevice, c->copy_stream), GFW_ERR_HIP);
-        HIP_TRY(hipEventRecord(s.copied, c->copy_stream), GFW_ERR_HIP);
-        HIP_TRY(hipStreamWaitEvent(c->stream, s.copied, 0), GFW_ERR_HIP);
+        Event &copied = c->mat_copied[c->mslot_cur];
+        for (int r = 0; r < matrix_count; ++r) pack_row(matrices + (size_t)r * 14, h + (size_t)r * GFW_MAT_STRIDE);      // into pinned memory
+        HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->copy_stream), GFW_ERR_HIP);
+        HIP_TRY(copied.record(c->copy_stream), GFW_ERR_HIP);
+        HIP_TRY(copied.wait_on(c->stream), GFW_ERR_HIP);
     }
-    *d_out = s.d;
+    *d_out = d;
     return GFW_OK;
 }
 static int matrices_consumed(gfw_ctx *c) {          // call after the kernels that read the current slot are enqueued
-    if (c->bslot_cur >= 0) {
-        gfw_ctx::BuiltSlot &b = c->bslots[c->bslot_cur];
-        HIP_TRY(hipEventRecord(b.consumed, c->stream), GFW_ERR_HIP);
-        b.used = true;
-    }
-    if (c->mslot_cur < 0) return GFW_OK;
-    gfw_ctx::MatSlot &s = c->mslots[c->mslot_cur];
-    HIP_TRY(hipEventRecord(s.done, c->stream), GFW_ERR_HIP);
-    s.used = true;
+    if (c->bslot_cur >= 0) HIP_TRY(c->bslots[c->bslot_cur].consumed.record(c->stream), GFW_ERR_HIP);
+    if (c->mslot_cur >= 0) HIP_TRY(c->mat_ring.slots[c->mslot_cur].free_again.record(c->stream), GFW_ERR_HIP);
     return GFW_OK;
 }
 

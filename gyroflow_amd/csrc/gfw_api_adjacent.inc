@@ -35,22 +35,14 @@ int gfw_set_sync_offsets(gfw_ctx *c, double duration_ms, const int64_t *ts_us, c
     }
     return GFW_OK;
 }
-// Copies `count` frame descriptors into the next slot of the pinned/device rings on `stream`; returns the device pointer.
-static int stage_timings(gfw_ctx *c, const gfw_frame_timing *t, int count, hipStream_t stream, const gfw_frame_timing **d_out) {
-    if (!c->h_timings) {
-        HIP_TRY(hipHostMalloc((void **)&c->h_timings, sizeof(gfw_frame_timing) * gfw_ctx::kTimingSlots * gfw_ctx::kMaxBatch), GFW_ERR_HIP);
-        HIP_TRY(c->d_timings.ensure(sizeof(gfw_frame_timing) * gfw_ctx::kTimingSlots * gfw_ctx::kMaxBatch), GFW_ERR_HIP);
-        for (auto &e : c->timing_copied) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming), GFW_ERR_HIP);
-    }
-    const int slot = c->timing_next;
-    c->timing_next = (slot + 1) % gfw_ctx::kTimingSlots;
-    HIP_TRY(hipEventSynchronize(c->timing_copied[slot]), GFW_ERR_HIP);         // the copy that last read this pinned slot is done
-    gfw_frame_timing *h = c->h_timings + (size_t)slot * gfw_ctx::kMaxBatch;
-    gfw_frame_timing *d = (gfw_frame_timing *)c->d_timings.ptr + (size_t)slot * gfw_ctx::kMaxBatch;
-    memcpy(h, t, sizeof(gfw_frame_timing) * count);
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof(gfw_frame_timing) * count, hipMemcpyHostToDevice, stream), GFW_ERR_HIP);
-    HIP_TRY(hipEventRecord(c->timing_copied[slot], stream), GFW_ERR_HIP);
-    *d_out = d;
+// Copies `count` frame descriptors through the next slot of the timings ring on `stream`; the caller records the slot's free_again behind the builder it launches
+// (the builder reads the device side, on whichever of the context's two streams this build runs: the slot is not free while it may)
+static int stage_timings(gfw_ctx *c, const gfw_frame_timing *t, int count, hipStream_t stream, StagingSlot **out) {
+    const size_t slot_bytes = sizeof(gfw_frame_timing) * gfw_ctx::kMaxBatch;
+    if (!c->timing_ring.slots[0].d.ptr) HIP_TRY(c->timing_ring.reserve(slot_bytes), GFW_ERR_HIP);
+    HIP_TRY(c->timing_ring.acquire(slot_bytes, stream, out), GFW_ERR_HIP);
+    memcpy((*out)->h.ptr, t, sizeof(gfw_frame_timing) * count);
+    HIP_TRY(hipMemcpyAsync((*out)->d.ptr, (*out)->h.ptr, sizeof(gfw_frame_timing) * count, hipMemcpyHostToDevice, stream), GFW_ERR_HIP);
     return GFW_OK;
 }
 static bool timing_ok(const gfw_frame_timing *t) { return t->rows >= 1 && t->readout_dim >= 1 && t->suppress_rotation >= 0 && t->suppress_rotation <= 2; }
@@ -82,22 +74,6 @@ static GfwStab stab_device(const gfw_frame_stab *stab, double y_sign, void *h_po
     return S;
 }
 static const GfwStab kNoStab = {0, 0, 0, 0, 0, 0, 0, nullptr, nullptr, -1, -1};
-// the next (pinned host, device) pair of the stabiliser ring with room for `bytes`; the build that last read it has normally long finished
-static int stab_slot_for(gfw_ctx *c, size_t bytes, gfw_ctx::StabSlot **out) {
-    gfw_ctx::StabSlot &ss = c->sslots[c->sslot_next];
-    c->sslot_next = (c->sslot_next + 1) % gfw_ctx::kStabSlots;
-    if (!ss.done) HIP_TRY(hipEventCreateWithFlags(&ss.done, hipEventDisableTiming), GFW_ERR_HIP);
-    if (ss.used) HIP_TRY(hipEventSynchronize(ss.done), GFW_ERR_HIP);
-    HIP_TRY(ss.d.ensure(bytes), GFW_ERR_HIP);
-    if (ss.hcap < bytes) {
-        if (ss.h) (void)hipHostFree(ss.h);
-        ss.h = nullptr; ss.hcap = 0;
-        HIP_TRY(hipHostMalloc(&ss.h, bytes), GFW_ERR_HIP);
-        ss.hcap = bytes;
-    }
-    *out = &ss;
-    return GFW_OK;
-}
 
 int gfw_build_matrices(gfw_ctx *c, const gfw_frame_timing *t, float *rows16_out, float **out_ptr) {
     return gfw_build_matrices_stab(c, t, nullptr, rows16_out, out_ptr);
@@ -107,41 +83,38 @@ int gfw_build_matrices_stab(gfw_ctx *c, const gfw_frame_timing *t, const gfw_fra
     if (!timing_ok(t)) { set_error("rows %d, readout_dim %d, suppress_rotation %d", t->rows, t->readout_dim, t->suppress_rotation); return GFW_ERR_INVALID_ARGUMENT; }
     { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
     HIP_TRY(hipSetDevice(c->device), GFW_ERR_HIP);
+    // a caller-owned table is built in order on the context's stream; a context-owned one in the next slot of the ring, on the auxiliary stream (overlaps the warp in flight)
+    const hipStream_t stream = rows16_out ? c->stream : c->copy_stream;
     GfwStab S, *Sp = nullptr;
-    gfw_ctx::StabSlot *stab_slot = nullptr; size_t stab_bytes = 0;
+    StagingSlot *stab_slot = nullptr, *t_slot = nullptr; size_t stab_bytes = 0;
     if (stab) {
         if (!stab_ok(stab, -1)) return GFW_ERR_INVALID_ARGUMENT;
         stab_bytes = stab_point_bytes(stab);
-        { const int rc = stab_slot_for(c, stab_bytes + 64, &stab_slot); if (rc != GFW_OK) return rc; }
-        S = stab_device(stab, t->framebuffer_inverted ? -1.0 : 1.0, stab_slot->h, stab_slot->d.ptr);
+        HIP_TRY(c->stab_ring.acquire(stab_bytes + 64, stream, &stab_slot), GFW_ERR_HIP);
+        S = stab_device(stab, t->framebuffer_inverted ? -1.0 : 1.0, stab_slot->h.ptr, stab_slot->d.ptr);
         Sp = &S;
     }
-    const size_t table_floats = (size_t)t->rows * GFW_MAT_STRIDE;
-    const gfw_frame_timing *d_t = nullptr;
-    if (rows16_out) {                                        // caller-owned table: built in order on the context's stream
+    const size_t table_floats = (size_t)t->rows * GFW_MAT_STRIDE, table_bytes = table_floats * sizeof(float);
+    float *table = rows16_out; double *prefix = nullptr;
+    gfw_ctx::BuiltSlot *b = nullptr;
+    if (rows16_out) {
         HIP_TRY(c->d_prefix.ensure(4 * sizeof(double)), GFW_ERR_HIP);
-        { const int rc = stage_timings(c, t, 1, c->stream, &d_t); if (rc != GFW_OK) return rc; }
-        if (stab_slot && stab_bytes) HIP_TRY(hipMemcpyAsync(stab_slot->d.ptr, stab_slot->h, stab_bytes, hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
-        HIP_TRY(gfw_launch_build_matrices(c->tracks, d_t, 1, t->rows, (double *)c->d_prefix.ptr, rows16_out, table_floats, c->stream, Sp), GFW_ERR_HIP);
-        if (stab_slot) { HIP_TRY(hipEventRecord(stab_slot->done, c->stream), GFW_ERR_HIP); stab_slot->used = true; }
-        if (out_ptr) *out_ptr = rows16_out;
-        if (c->synchronous) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);
-        return GFW_OK;
+        prefix = (double *)c->d_prefix.ptr;
+    } else {
+        b = &c->bslots[c->bslot_next];
+        c->bslot_next = (c->bslot_next + 1) % gfw_ctx::kBuiltSlots;
+        HIP_TRY(b->buf.ensure(table_bytes + 4 * sizeof(double)), GFW_ERR_HIP);
+        HIP_TRY(b->consumed.wait_on(stream), GFW_ERR_HIP);                   // the warp that read this slot is done
+        table = (float *)b->buf.ptr; prefix = (double *)((char *)b->buf.ptr + table_bytes);
     }
-    // context-owned table: next slot of the ring, built on the auxiliary stream (overlaps the warp in flight)
-    gfw_ctx::BuiltSlot &b = c->bslots[c->bslot_next];
-    c->bslot_next = (c->bslot_next + 1) % gfw_ctx::kBuiltSlots;
-    const size_t table_bytes = table_floats * sizeof(float);
-    HIP_TRY(b.buf.ensure(table_bytes + 4 * sizeof(double)), GFW_ERR_HIP);
-    if (!b.built) { HIP_TRY(hipEventCreateWithFlags(&b.built, hipEventDisableTiming), GFW_ERR_HIP); HIP_TRY(hipEventCreateWithFlags(&b.consumed, hipEventDisableTiming), GFW_ERR_HIP); }
-    if (b.used) HIP_TRY(hipStreamWaitEvent(c->copy_stream, b.consumed, 0), GFW_ERR_HIP);   // the warp that read this slot is done
-    { const int rc = stage_timings(c, t, 1, c->copy_stream, &d_t); if (rc != GFW_OK) return rc; }
-    if (stab_slot && stab_bytes) HIP_TRY(hipMemcpyAsync(stab_slot->d.ptr, stab_slot->h, stab_bytes, hipMemcpyHostToDevice, c->copy_stream), GFW_ERR_HIP);
-    HIP_TRY(gfw_launch_build_matrices(c->tracks, d_t, 1, t->rows, (double *)((char *)b.buf.ptr + table_bytes), (float *)b.buf.ptr, table_floats, c->copy_stream, Sp), GFW_ERR_HIP);
-    HIP_TRY(hipEventRecord(b.built, c->copy_stream), GFW_ERR_HIP);
-    if (stab_slot) { HIP_TRY(hipEventRecord(stab_slot->done, c->copy_stream), GFW_ERR_HIP); stab_slot->used = true; }
-    if (out_ptr) *out_ptr = (float *)b.buf.ptr;
-    if (c->synchronous) HIP_TRY(hipStreamSynchronize(c->copy_stream), GFW_ERR_HIP);
+    { const int rc = stage_timings(c, t, 1, stream, &t_slot); if (rc != GFW_OK) return rc; }
+    if (stab_slot && stab_bytes) HIP_TRY(hipMemcpyAsync(stab_slot->d.ptr, stab_slot->h.ptr, stab_bytes, hipMemcpyHostToDevice, stream), GFW_ERR_HIP);
+    HIP_TRY(gfw_launch_build_matrices(c->tracks, (const gfw_frame_timing *)t_slot->d.ptr, 1, t->rows, prefix, table, table_floats, stream, Sp), GFW_ERR_HIP);
+    if (b) HIP_TRY(b->built.record(stream), GFW_ERR_HIP);
+    HIP_TRY(t_slot->free_again.record(stream), GFW_ERR_HIP);
+    if (stab_slot) HIP_TRY(stab_slot->free_again.record(stream), GFW_ERR_HIP);
+    if (out_ptr) *out_ptr = table;
+    if (c->synchronous) HIP_TRY(hipStreamSynchronize(stream), GFW_ERR_HIP);
     return GFW_OK;
 }
 // The tables of `count` upcoming frames in one launch, in order on the context's stream: no cross-stream events, and the
@@ -161,9 +134,10 @@ int gfw_build_matrices_batch(gfw_ctx *c, const gfw_frame_timing *t, int count, f
     const size_t table_floats = (size_t)max_rows * GFW_MAT_STRIDE;
     const size_t tables_bytes = table_floats * sizeof(float) * count;
     HIP_TRY(buf.ensure(tables_bytes + 4 * sizeof(double) * count), GFW_ERR_HIP);
-    const gfw_frame_timing *d_t = nullptr;
-    { const int rc = stage_timings(c, t, count, c->stream, &d_t); if (rc != GFW_OK) return rc; }
-    HIP_TRY(gfw_launch_build_matrices(c->tracks, d_t, count, max_rows, (double *)((char *)buf.ptr + tables_bytes), (float *)buf.ptr, table_floats, c->stream), GFW_ERR_HIP);
+    StagingSlot *t_slot = nullptr;
+    { const int rc = stage_timings(c, t, count, c->stream, &t_slot); if (rc != GFW_OK) return rc; }
+    HIP_TRY(gfw_launch_build_matrices(c->tracks, (const gfw_frame_timing *)t_slot->d.ptr, count, max_rows, (double *)((char *)buf.ptr + tables_bytes), (float *)buf.ptr, table_floats, c->stream), GFW_ERR_HIP);
+    HIP_TRY(t_slot->free_again.record(c->stream), GFW_ERR_HIP);
     for (int i = 0; i < count; ++i) out_ptrs[i] = (float *)buf.ptr + table_floats * i;
     if (c->synchronous) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);
     return GFW_OK;
@@ -183,13 +157,13 @@ int gfw_build_matrices_batch_stab(gfw_ctx *c, const gfw_frame_timing *t, const g
     { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
     HIP_TRY(hipSetDevice(c->device), GFW_ERR_HIP);
     const size_t table_bytes = sizeof(GfwStab) * (size_t)count;
-    gfw_ctx::StabSlot *ss = nullptr;
-    { const int rc = stab_slot_for(c, table_bytes + point_bytes + 64, &ss); if (rc != GFW_OK) return rc; }
-    GfwStab *h_stabs = (GfwStab *)ss->h;
+    StagingSlot *ss = nullptr, *t_slot = nullptr;
+    HIP_TRY(c->stab_ring.acquire(table_bytes + point_bytes + 64, c->stream, &ss), GFW_ERR_HIP);
+    GfwStab *h_stabs = (GfwStab *)ss->h.ptr;
     size_t at = table_bytes;
     for (int i = 0; i < count; ++i) {
         if (!stabs[i]) { h_stabs[i] = kNoStab; continue; }
-        h_stabs[i] = stab_device(stabs[i], t[i].framebuffer_inverted ? -1.0 : 1.0, (char *)ss->h + at, (const char *)ss->d.ptr + at);
+        h_stabs[i] = stab_device(stabs[i], t[i].framebuffer_inverted ? -1.0 : 1.0, (char *)ss->h.ptr + at, (const char *)ss->d.ptr + at);
         at += stab_point_bytes(stabs[i]);
     }
     DevBuf &buf = c->d_batch[c->batch_next];
@@ -197,12 +171,11 @@ int gfw_build_matrices_batch_stab(gfw_ctx *c, const gfw_frame_timing *t, const g
     const size_t table_floats = (size_t)max_rows * GFW_MAT_STRIDE;
     const size_t tables_bytes = table_floats * sizeof(float) * count;
     HIP_TRY(buf.ensure(tables_bytes + 4 * sizeof(double) * count), GFW_ERR_HIP);
-    const gfw_frame_timing *d_t = nullptr;
-    { const int rc = stage_timings(c, t, count, c->stream, &d_t); if (rc != GFW_OK) return rc; }
-    HIP_TRY(hipMemcpyAsync(ss->d.ptr, ss->h, at, hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
-    HIP_TRY(gfw_launch_build_matrices_stab(c->tracks, d_t, count, max_rows, (double *)((char *)buf.ptr + tables_bytes), (float *)buf.ptr, table_floats, c->stream, (const GfwStab *)ss->d.ptr), GFW_ERR_HIP);
-    HIP_TRY(hipEventRecord(ss->done, c->stream), GFW_ERR_HIP);
-    ss->used = true;
+    { const int rc = stage_timings(c, t, count, c->stream, &t_slot); if (rc != GFW_OK) return rc; }
+    HIP_TRY(hipMemcpyAsync(ss->d.ptr, ss->h.ptr, at, hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
+    HIP_TRY(gfw_launch_build_matrices_stab(c->tracks, (const gfw_frame_timing *)t_slot->d.ptr, count, max_rows, (double *)((char *)buf.ptr + tables_bytes), (float *)buf.ptr, table_floats, c->stream, (const GfwStab *)ss->d.ptr), GFW_ERR_HIP);
+    HIP_TRY(t_slot->free_again.record(c->stream), GFW_ERR_HIP);
+    HIP_TRY(ss->free_again.record(c->stream), GFW_ERR_HIP);
     for (int i = 0; i < count; ++i) out_ptrs[i] = (float *)buf.ptr + table_floats * i;
     if (c->synchronous) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);
     return GFW_OK;
@@ -339,18 +312,10 @@ static int zoom_fovs_impl(gfw_ctx *c, const gfw_kernel_params *p, const gfw_zoom
     const size_t sb = stabs ? sizeof(GfwStab) * (size_t)n_frames : 0, mb = meshes ? sizeof(int32_t) * 2 * (size_t)n_frames : 0;
     const size_t o_stab = fb + rb, o_points = o_stab + sb, o_ref = o_points + point_bytes, o_mesh = o_ref + mb, total = o_mesh + mesh_doubles * sizeof(double);
     static_assert(sizeof(gfw_zoom_frame) % 8 == 0 && sizeof(GfwStab) % 8 == 0 && GFW_MESH_MAX == GFW_ZOOM_MESH_MAX, "the staged block keeps its doubles aligned; one mesh limit");
-    if (!c->zoom_copied) HIP_TRY(hipEventCreateWithFlags(&c->zoom_copied, hipEventDisableTiming), GFW_ERR_HIP);
-    HIP_TRY(hipEventSynchronize(c->zoom_copied), GFW_ERR_HIP);              // the copy that last read the pinned block is done
-    if (c->h_zoom_cap < total) {
-        if (c->h_zoom) (void)hipHostFree(c->h_zoom);
-        c->h_zoom = nullptr; c->h_zoom_cap = 0;
-        HIP_TRY(hipHostMalloc(&c->h_zoom, total), GFW_ERR_HIP);
-        c->h_zoom_cap = total;
-    }
-    if (c->d_zoom_in.cap < total) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);      // a launch in flight may still read the block about to be replaced
-    HIP_TRY(c->d_zoom_in.ensure(total), GFW_ERR_HIP);
-    char *h = (char *)c->h_zoom;
-    const char *d = (const char *)c->d_zoom_in.ptr;
+    StagingSlot *zs = nullptr;                                               // (free when the copy that last read the pinned block is done; a launch in flight that still
+    HIP_TRY(c->zoom_ring.acquire(total, c->stream, &zs), GFW_ERR_HIP);       //  reads a device block about to be replaced is waited for)
+    char *h = (char *)zs->h.ptr;
+    const char *d = (const char *)zs->d.ptr;
     memcpy(h, frames, fb);
     if (rb) memcpy(h + fb, rotations, sizeof(float) * 9 * (size_t)n_frames);
     if (stabs) {
@@ -372,8 +337,8 @@ static int zoom_fovs_impl(gfw_ctx *c, const gfw_kernel_params *p, const gfw_zoom
             ref[i * 2] = (int32_t)first; ref[i * 2 + 1] = (int32_t)mesh_lens[i];
         }
     }
-    HIP_TRY(hipMemcpyAsync(c->d_zoom_in.ptr, c->h_zoom, total, hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
-    HIP_TRY(hipEventRecord(c->zoom_copied, c->stream), GFW_ERR_HIP);
+    HIP_TRY(hipMemcpyAsync(zs->d.ptr, zs->h.ptr, total, hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
+    HIP_TRY(zs->free_again.record(c->stream), GFW_ERR_HIP);
     const size_t ob = sizeof(double) * (size_t)n_frames, db = debug_points ? sizeof(double) * 2 * GFW_ZOOM_RECT * (size_t)n_frames : 0;
     double *d_fov = fov_minimal, *d_dbg = debug_points;
     if (!out_on_device) {

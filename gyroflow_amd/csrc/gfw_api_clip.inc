@@ -103,7 +103,7 @@ static bool clip_same_shape(const gfw_buffers *a, const gfw_buffers *b, int npla
     return true;
 }
 static bool clip_ring_table(gfw_ctx *c, const float *m) {          // a table of gfw_build_matrices' cross-stream ring (ordered by events)
-    for (int i = 0; i < gfw_ctx::kBuiltSlots; ++i) if (c->bslots[i].buf.ptr == (const void *)m && c->bslots[i].built) return true;
+    for (int i = 0; i < gfw_ctx::kBuiltSlots; ++i) if (c->bslots[i].buf.ptr == (const void *)m && c->bslots[i].built.recorded()) return true;
     return false;
 }
 // The frames of one launch are in flight together, the calls they stand for are ordered: a frame whose planes overlap a pending frame's

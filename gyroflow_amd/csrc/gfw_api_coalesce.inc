@@ -60,12 +60,8 @@ static int order_members_behind(gfw_ctx *owner) {
         m->needs_order = false;
         m->last_backend = owner->last_backend;
         if (m->stream == owner->stream) continue;
-        if (!recorded) {
-            if (!owner->group_done && hipEventCreateWithFlags(&owner->group_done, hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); return GFW_ERR_HIP; }
-            HIP_TRY(hipEventRecord(owner->group_done, owner->stream), GFW_ERR_HIP);
-            recorded = true;
-        }
-        HIP_TRY(hipStreamWaitEvent(m->stream, owner->group_done, 0), GFW_ERR_HIP);
+        if (!recorded) { HIP_TRY(owner->group_done.record(owner->stream), GFW_ERR_HIP); recorded = true; }
+        HIP_TRY(owner->group_done.wait_on(m->stream), GFW_ERR_HIP);
     }
     return GFW_OK;
 }
@@ -123,8 +119,7 @@ static int group_launch(PlaneGroup *g, GroupLock &lk) {
         if (seen) continue;
         // (the earlier planes' calls have returned GFW_OK: an event that cannot be created, recorded or waited for must not lose their frame — the host waits for
         //  the member's stream instead and the launch goes on; ADVICE r5)
-        const bool ordered = (m->inputs_ready || hipEventCreateWithFlags(&m->inputs_ready, hipEventDisableTiming) == hipSuccess) &&
-                             hipEventRecord(m->inputs_ready, m->stream) == hipSuccess && hipStreamWaitEvent(owner->stream, m->inputs_ready, 0) == hipSuccess;
+        const bool ordered = m->inputs_ready.record(m->stream) == hipSuccess && m->inputs_ready.wait_on(owner->stream) == hipSuccess;
         if (!ordered) { (void)hipGetLastError(); (void)hipStreamSynchronize(m->stream); }
     }
     for (int i = 1; i < n; ++i) { g->pl[i].c->frame_owner = owner; g->pl[i].c->needs_order = true; }

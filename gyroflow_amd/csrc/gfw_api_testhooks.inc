@@ -2,13 +2,12 @@
 // the specialisation path, the shipped-cache key, gfw_checksum64 / gfw_set_frame_checksums, gfw_pack_matrices).  Split out of gfw_api.hip in round 6.
 
 // ------------------------------------------------------------------------------------------------ test hooks
-struct Release3 { DevBuf &x, &y, &z; ~Release3() { x.release(); y.release(); z.release(); } };      // (released on every path)
 extern "C" {
 int gfw_debug_math(int op, const float *a, const float *b, float *out, size_t n) {
     if (!a || !out || n == 0) { set_error("null/empty arrays"); return GFW_ERR_INVALID_ARGUMENT; }
     if (device_count() == 0) { set_error("no HIP device visible"); return GFW_ERR_NO_DEVICE; }
     HIP_TRY(hipSetDevice(g_current_device), GFW_ERR_HIP);
-    DevBuf da, db, dout; Release3 release{da, db, dout};
+    DevBuf da, db, dout;                                     // (released on every path)
     HIP_TRY(da.ensure(n * sizeof(float)), GFW_ERR_HIP);
     HIP_TRY(dout.ensure(n * sizeof(float)), GFW_ERR_HIP);
     if (b) HIP_TRY(db.ensure(n * sizeof(float)), GFW_ERR_HIP);
@@ -22,7 +21,7 @@ long long gfw_debug_selftest(int test, unsigned long long n, unsigned long long 
     if (device_count() == 0) { set_error("no HIP device visible"); return GFW_ERR_NO_DEVICE; }
     HIP_TRY(hipSetDevice(g_current_device), GFW_ERR_HIP);
     if (test == 2 && n == 0) n = 1ull << 31;
-    DevBuf dbad, none1, none2; Release3 release{dbad, none1, none2};
+    DevBuf dbad;
     unsigned long long bad = 0;
     HIP_TRY(dbad.ensure(sizeof(bad)), GFW_ERR_HIP);
     HIP_TRY(hipMemset(dbad.ptr, 0, sizeof(bad)), GFW_ERR_HIP);

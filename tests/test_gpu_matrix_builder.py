@@ -3,6 +3,8 @@ FrameTransform::at_timestamp (frame_transform.rs:221-308).  Tolerance-based by c
 libm on the host vs closed-form inverse and ocml on the device; the bar is <= 2 ULP of f32 on every entry (relative to
 the row's largest entry for values that cancel to ~0)."""
 import ctypes as C
+import os
+import re
 
 import numpy as np
 import pytest
@@ -273,16 +275,25 @@ def test_suppress_rotation_outside_its_values_is_rejected():
     _rows(fr, run)
 
 
+def ring_size(name):
+    """a ring's length as gyroflow_amd/csrc/gfw_api.hip names it (`kStabSlots = 4`)"""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gyroflow_amd", "csrc", "gfw_api.hip")).read()
+    return int(re.search(r"\b%s\s*=\s*(\d+)\s*[;,]" % name, src).group(1))
+
+
 def test_stabiliser_builds_stay_asynchronous_and_ordered():
-    """Six consecutive frames with different IBIS/OIS control points on one context: each table must carry ITS frame's terms (the
-    control points travel through a ring of pinned / device buffers on the building stream, no stream-wide synchronisation)."""
+    """Twice kStabSlots consecutive frames with different IBIS/OIS control points on one context, kStabSlots at a time (the ring of context-owned tables holds
+    that many; the second lot follows a synchronize and the read-back of the first, and takes every slot of the stabiliser ring a second time): each table must
+    carry ITS frame's terms (the control points travel through a ring of pinned / device buffers on the building stream, no stream-wide synchronisation)."""
     w, h = 640, 360
     fr = S.SyntheticFrame("YUV422P16LE", w, h, seed=3)
     org = S.sampled_track(11, 0.0, 2000.0, 1000.0)
     sm = S.sampled_track(12, 0.0, 2000.0, 200.0, scale=0.25)
     nk = S.new_k(fr.lens, 1.0, w, h)
+    n = ring_size("kStabSlots")
+    assert n == ring_size("kBuiltSlots") >= 2
     stabs = []
-    for j in range(6):
+    for j in range(2 * n):
         st = _stab(w, h)
         st["ibis"] = np.asarray(st["ibis"], dtype=np.float64).copy()
         st["ibis"][:, 1:] *= (1.0 + 0.37 * j)
@@ -291,13 +302,65 @@ def test_stabiliser_builds_stay_asynchronous_and_ordered():
     def run(be):
         be.set_quaternion_tracks(org, sm)
         be.set_option(abi.OPT_SYNCHRONOUS, 0)
-        ptrs = [be.build_matrices(nk, 1000.3 + 33.3 * j, 16.0, h, h, stab=stabs[j]) for j in range(4)]      # the ring holds four tables
-        be.synchronize()
-        return [fetch_rows(p, h) for p in ptrs]
+        out = []
+        for lot in (range(n), range(n, 2 * n)):
+            ptrs = [be.build_matrices(nk, 1000.3 + 33.3 * j, 16.0, h, h, stab=stabs[j]) for j in lot]       # the ring holds n tables
+            be.synchronize()
+            out += [fetch_rows(p, h) for p in ptrs]
+        return out
     devs = _rows(fr, run)
+    assert len(devs) == 2 * n
     for j, dev in enumerate(devs):
         host = HS.row_matrices_from_tracks(org, sm, nk, 1000.3 + 33.3 * j, 16.0, h, h, stab=stabs[j])
         assert ulps(dev[:, 9:14], host[:, 9:14], np.full((h, 1), 1e-6)).max() <= 1.0, j
+
+
+def test_stabiliser_and_timings_rings_wrap_and_regrow_into_caller_owned_tables():
+    """kTimingSlots + 1 asynchronous builds into the caller's device tables, 8 rows each on a 64 x 8 context, one synchronize at the end: the timings ring wraps
+    once and the stabiliser ring twice, and as each call brings more control points than the one before, a slot taken again regrows both of its sides.  Table j is
+    the table of the same call made alone on a fresh synchronous context, bit for bit, and its m[9..13] the host statement's within 1 ULP (two equally wrong
+    device results cannot agree); the statements differ pairwise, so a stale slot would show."""
+    import torch
+    w, h = 64, 8
+    fr = S.SyntheticFrame("YUV422P16LE", w, h, seed=3)
+    org = S.sampled_track(11, 0.0, 2000.0, 1000.0)
+    sm = S.sampled_track(12, 0.0, 2000.0, 200.0, scale=0.25)
+    nk = S.new_k(fr.lens, 1.0, w, h)
+    n = ring_size("kTimingSlots") + 1
+    assert n > 2 * ring_size("kStabSlots")
+    stamps = [1000.3 + 33.3 * j for j in range(n)]
+    stabs = []
+    for j in range(n):
+        pos = np.linspace(-200.0, 3400.0, 19 + 5 * j)                  # more control points call by call
+        amp = 1.0 + 0.37 * j
+        ibis = np.stack([pos, amp * 14.0 * np.sin(pos * 0.004), -amp * 9.0 * np.cos(pos * 0.003), amp * 350.0 * np.sin(pos * 0.002 + 0.4)], axis=1)
+        ois = np.stack([pos, 3.0 * np.cos(pos * 0.005 + 0.2 * j), 2.0 * np.sin(pos * 0.006 - 0.2 * j), np.zeros_like(pos)], axis=1)
+        stabs.append(dict(_stab(w, h), ibis=ibis, ois=ois))
+    hosts = [HS.row_matrices_from_tracks(org, sm, nk, stamps[j], 16.0, h, h, stab=stabs[j]) for j in range(n)]
+    for i in range(n):
+        assert np.abs(hosts[i][:, 9:14]).max() > 0.01
+        for j in range(i + 1, n):
+            assert not np.array_equal(hosts[i][:, 9:14], hosts[j][:, 9:14]) and not np.array_equal(hosts[i][:, :9], hosts[j][:, :9]), (i, j)
+    dev = torch.device("cuda", 0)
+
+    def build(calls, asynchronous):
+        tables = [torch.zeros((h, 16), dtype=torch.float32, device=dev) for _ in calls]
+        torch.cuda.synchronize(dev)                              # (zeroed on torch's stream, written on the context's)
+
+        def run(be):
+            be.set_quaternion_tracks(org, sm)
+            be.set_option(abi.OPT_SYNCHRONOUS, 0 if asynchronous else 1)
+            for j, tab in zip(calls, tables):
+                assert be.build_matrices(nk, stamps[j], 16.0, h, h, stab=stabs[j], out_ptr=tab.data_ptr()) == tab.data_ptr()
+            be.synchronize()
+            return [t.cpu().numpy() for t in tables]
+        return _rows(fr, run)
+    alone = [build([j], False)[0] for j in range(n)]
+    together = build(range(n), True)
+    for j in range(n):
+        assert np.array_equal(together[j].view(np.uint32), alone[j].view(np.uint32)), j
+        t = ulps(together[j][:, 9:14], hosts[j][:, 9:14], np.full((h, 1), 1e-6))
+        assert t.max() <= 1.0, "call %d: IBIS/OIS terms differ by %.2f ULP" % (j, t.max())
 
 
 def test_warp_with_device_built_ibis_rows_is_bit_exact_against_the_oracle():

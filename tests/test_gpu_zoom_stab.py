@@ -10,7 +10,7 @@ import os
 import numpy as np
 import pytest
 
-from gyroflow_amd import abi, warp
+from gyroflow_amd import abi, synthetic as S, warp
 import _zoomstmt as Z
 import _zoomstab as ZS
 from test_gpu_zoom import backend_for, same_f64
@@ -157,6 +157,93 @@ def test_device_outputs_on_an_asynchronous_context_and_empty_clip():
     finally:
         be.close()
     torch.cuda.synchronize()
+
+
+def small_backend(clip):
+    """a context for the smallest plane gfw_create takes, 64 x 8, with the clip's lens ids: the zoom search brings its own KernelParams"""
+    fr = S.SyntheticFrame("NV12", 64, 8, seed=3, lens=clip.lens, pixels=True)
+    pl = fr.planes[0]
+    return warp.Backend(pl["params"], pl["pixel_type"], fr.model, fr.digital, warp.host_buffers(pl["src"], pl["size"], pl["dst"].copy(), pl["out_size"]))
+
+
+def test_the_staging_block_regrows_between_asynchronous_calls():
+    """Three calls back to back on an asynchronous context, 2, 24 and 5 frames of a clip with stabiliser data and meshes, each into its own device tensors: the
+    second call grows both sides of the one staging block while the first search may still read it, the third takes it smaller.  After one synchronize every
+    result is the same call's on a synchronous context, bit for bit."""
+    import torch
+    dev = torch.device("cuda", 0)
+    clip = CLIPS["all-r12-sony"].with_mode(1)
+    kp, search, frames, _, stabs, meshes = ZS.inputs(clip)
+    counts = (2, 24, 5)
+
+    def call(be, k, **kw):
+        return be.zoom_fovs_stab(kp, search, (abi.ZoomFrame * k).from_buffer(frames), stabs=stabs[:k], meshes=meshes[:k], **kw)
+    be = small_backend(clip)
+    try:
+        be.set_quaternion_tracks(*clip.tracks)
+        refs = [call(be, k, debug=True) for k in counts]
+    finally:
+        be.close()
+    assert not same_f64(refs[0][0], refs[1][0][3:5])                                 # frames differ: another call's block would show
+    d_f = [torch.full((k,), -1.0, dtype=torch.float64, device=dev) for k in counts]
+    d_d = [torch.full((k, 120, 2), -1.0, dtype=torch.float64, device=dev) for k in counts]
+    torch.cuda.synchronize(dev)
+    be = small_backend(clip)
+    try:
+        be.set_quaternion_tracks(*clip.tracks)
+        be.set_option(abi.OPT_SYNCHRONOUS, 0)
+        for k, f, d in zip(counts, d_f, d_d):
+            assert call(be, k, out_ptr=f.data_ptr(), debug_ptr=d.data_ptr()) is None
+        be.synchronize()
+        got = [(f.cpu().numpy(), d.cpu().numpy()) for f, d in zip(d_f, d_d)]
+    finally:
+        be.close()
+    for k, (f, d), (rf, rd) in zip(counts, got, refs):
+        assert same_f64(f, rf) and same_f64(d, rd), k
+
+
+def test_a_context_closed_with_work_enqueued_completes_it():
+    """gfw_destroy drains both of the context's streams before anything is released: an asynchronous context takes one coordinate map into the caller's tensor
+    (the matrix ring, copied on the auxiliary stream), one table build with stabiliser data into the caller's table and one zoom search into the caller's tensor,
+    and is closed without a synchronize.  The three outputs are those of a synchronous context; a context created afterwards repeats a call correctly."""
+    import torch
+    import _coordcase as K
+    from test_gpu_matrix_builder import _stab
+    from test_gpu_stmap import sentinel_tensor, split, stmap_call
+    dev = torch.device("cuda", 0)
+    clip = CLIPS["shifts-r12"]
+    assert clip.lens["model"] == "opencv_fisheye"
+    w, h, n = 64, 8, 5
+    fr = K._frame(w, h, "opencv_fisheye", 1.2, 120)
+    skp = K.stmap_params(fr)
+    nk = S.new_k(fr.lens, 1.0, w, h)
+    kp, search, frames, _, stabs, _ = ZS.inputs(clip)
+    frames = (abi.ZoomFrame * n).from_buffer(frames)
+
+    def run(asynchronous, only_build=False):
+        coords, table = sentinel_tensor(w, h, dev), torch.zeros((h, 16), dtype=torch.float32, device=dev)
+        d_f = torch.full((n,), -1.0, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        be = small_backend(clip)
+        try:
+            be.set_quaternion_tracks(*clip.tracks)
+            be.set_option(abi.OPT_SYNCHRONOUS, 0 if asynchronous else 1)
+            if not only_build:
+                assert stmap_call(be, skp, fr.matrices, None, None, w, h, coords.data_ptr(), True) == 0, be.lib.gfw_last_error()
+            be.build_matrices(nk, 1000.3, 16.0, h, h, stab=_stab(w, h), out_ptr=table.data_ptr())
+            if not only_build:
+                be.zoom_fovs_stab(kp, search, frames, stabs=stabs[:n], out_ptr=d_f.data_ptr())
+        finally:
+            be.close()                                       # no synchronize before it
+        torch.cuda.synchronize(dev)
+        return split(coords, w, h), table.cpu().numpy().view(np.uint32), d_f.cpu().numpy()
+    (ref_map, ref_tail), ref_table, ref_f = run(False)
+    assert np.any(ref_map != K.SENTINEL) and np.all(ref_tail == K.SENTINEL) and np.abs(ref_table.view(np.float32)[:, 9:14]).max() > 0.01 and np.all(ref_f > 0.0)
+    (got_map, got_tail), got_table, got_f = run(True)
+    assert np.array_equal(got_map, ref_map) and np.array_equal(got_tail, ref_tail)
+    assert np.array_equal(got_table, ref_table)
+    assert same_f64(got_f, ref_f)
+    assert np.array_equal(run(False, only_build=True)[1], ref_table)
 
 
 def test_arguments():
