@@ -103,6 +103,20 @@ class ZoomSearch(C.Structure):
                 ("fov_algorithm_margin", C.c_float), ("horizontal_readout", C.c_int32)]
 
 
+class SyncSearch(C.Structure):
+    """``gfw_sync_search``: what every candidate of a visual-features sync search shares."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("horizontal_readout", C.c_int32), ("use_sync_offsets", C.c_int32),
+                ("new_k", C.c_double * 9), ("video_rotation_deg", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
+class SyncResult(C.Structure):
+    """``gfw_sync_result``: the two-stage search of one range."""
+    _fields_ = [("found", C.c_int32), ("n_coarse", C.c_int32), ("coarse_value", C.c_double), ("coarse_cost", C.c_double),
+                ("value", C.c_double), ("cost", C.c_double)]
+
+
+SYNC_FINE_CANDIDATES = 200       # the second stage's candidates
+SYNC_PAIR_POINTS_MAX = 4096
 ZOOM_RECT_POINTS = 120           # points_around_rect(w, h, 31, 31)
 
 
@@ -179,6 +193,9 @@ def bind(lib):
     lib.gfw_zoom_fovs.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(ZoomSearch), vp, i32, vp, vp, vp, i32]; lib.gfw_zoom_fovs.restype = i32
     lib.gfw_zoom_fovs_stab.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(ZoomSearch), vp, i32, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_zoom_fovs_stab.restype = i32
     lib.gfw_zoom_smooth.argtypes = [vp, i32, C.c_double, C.c_double, i32, vp, i32, vp, vp]; lib.gfw_zoom_smooth.restype = i32
+    lib.gfw_sync_visual_costs.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(SyncSearch), vp, vp, vp, vp, i32, vp, i32, vp, vp, i32]; lib.gfw_sync_visual_costs.restype = i32
+    lib.gfw_sync_visual_search.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(SyncSearch), vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp, i32]
+    lib.gfw_sync_visual_search.restype = i32
     lib.gfw_pack_matrices.argtypes = [vp, i32, vp]; lib.gfw_pack_matrices.restype = i32
     lib.gfw_checksum64.argtypes = [vp, vp, sz, vp]; lib.gfw_checksum64.restype = i32
     lib.gfw_set_frame_checksums.argtypes = [vp, vp, sz]; lib.gfw_set_frame_checksums.restype = i32
@@ -202,7 +219,7 @@ EXPORTS = ["gfw_abi_version", "gfw_list_devices", "gfw_set_device", "gfw_get_inf
            "gfw_get_stream", "gfw_set_stream", "gfw_synchronize", "gfw_flush", "gfw_import_external_fd", "gfw_release_external", "gfw_last_backend", "gfw_get_profile", "gfw_last_error", "gfw_debug_math", "gfw_debug_jit_key", "gfw_debug_selftest", "gfw_get_audit", "gfw_pack_matrices", "gfw_checksum64", "gfw_set_frame_checksums", "gfw_set_quaternion_tracks", "gfw_build_matrices", "gfw_build_matrices_stab", "gfw_set_sync_offsets", "gfw_build_matrices_batch", "gfw_stmap_undistort", "gfw_undistort_points",
            "gfw_pixel_type_info", "gfw_undistort_clip", "gfw_undistort_clip_params", "gfw_jit_status", "gfw_get_profile_frames", "gfw_debug_jit_compile", "gfw_debug_source_id", "gfw_debug_p1_radial", "gfw_debug_paired_launches", "gfw_debug_frames_per_launch",
            "gfw_debug_jit_key_clip_params", "gfw_zoom_fovs", "gfw_zoom_smooth",
-           "gfw_build_matrices_batch_stab", "gfw_zoom_fovs_stab"]
+           "gfw_build_matrices_batch_stab", "gfw_zoom_fovs_stab", "gfw_sync_visual_costs", "gfw_sync_visual_search"]
 
 
 def load_library(path=None):

@@ -22,6 +22,7 @@
 #include "gfw_frame.h"
 #include "gfw_matrices.h"
 #include "gfw_zoom.h"
+#include "gfw_sync.h"
 #include "gfw_jit.h"
 #include <stdlib.h>
 #include <map>
@@ -98,6 +99,8 @@ struct gfw_ctx {
     // gfw_zoom_fovs: frame descriptors (+ caller-given rotations) staged through pinned memory, results for host outputs
     // (one block, free again behind its COPY: the device side is ordered by the context's stream, and a second asynchronous call does not wait for the first search)
     StagingRing<1> zoom_ring; DevBuf d_zoom_out;
+    // gfw_sync_visual_*: pairs, points and candidates staged the same way; rays / partial sums / fine candidates; results for host outputs
+    StagingRing<1> sync_ring; DevBuf d_sync_work, d_sync_out;
     // context-owned per-row tables built on the device (gfw_build_matrices): a small ring, built on copy_stream so that
     // frame N+1's table is produced while frame N is being warped; events order builder and consumer both ways
     struct BuiltSlot { DevBuf buf; Event built, consumed; };   // buf = rows + 4 doubles of builder scratch

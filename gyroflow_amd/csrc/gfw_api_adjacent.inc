@@ -1,5 +1,5 @@
 // gfw_api_adjacent.inc — part of gfw_api.hip (textually included): the entry points of the rows next to the warp (SURVEY.md section 8f) — the per-row matrix
-// builder (gfw_set_quaternion_tracks, gfw_build_matrices*), gfw_undistort_points, the STMap export.  Split out of gfw_api.hip in round 6.
+// builder (gfw_set_quaternion_tracks, gfw_build_matrices*), gfw_undistort_points, the STMap export, the zoom search, the sync search.  Split out of gfw_api.hip in round 6.
 
 
 extern "C" {
@@ -458,4 +458,138 @@ extern "C" int gfw_zoom_smooth(const double *fov_minimal, int n, double adaptive
         for (int i = 0; i < n; ++i) fovs_out[i] = 1.0;                       // disabled
     }
     return GFW_OK;
+}
+
+// The visual-features sync search (find_offset/visual_features.rs:10-147; gfw_sync.hip).  See include/gfwarp.h for the argument contract.  One body serves both entries:
+// `search_mode` < 0 = gfw_sync_visual_costs (the caller's candidates), 0 / 1 = gfw_sync_visual_search (the coarse candidates are made here, the fine ones on the device).
+struct SyncOut { double *costs; float *mapped; gfw_sync_result *result; double *coarse_costs, *fine_costs; };
+static int sync_visual_impl(gfw_ctx *c, const gfw_kernel_params *p, const gfw_sync_search *search, const int64_t *pair_ts_us, const int32_t *pair_first,
+                            const float *points_a, const float *points_b, int n_pairs, const double *candidates, int n_candidates, int search_mode,
+                            double initial_offset_ms, double search_size_ms, double frame_readout_time_ms, double scaled_fps, const SyncOut &out, int out_on_device) {
+    if (!c || !p || !search || n_pairs < 0 || n_candidates < 0) { set_error("bad sync arguments (null context / params / search, or a negative count)"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (search->reserved[0] || search->reserved[1]) { set_error("bad sync search: reserved slots must be 0"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (search->width < 1 || search->height < 1 || search->horizontal_readout < 0 || search->horizontal_readout > 1 || search->use_sync_offsets < 0 || search->use_sync_offsets > 1) {
+        set_error("bad sync search: %d x %d, horizontal_readout %d, use_sync_offsets %d", search->width, search->height, search->horizontal_readout, search->use_sync_offsets);
+        return GFW_ERR_INVALID_ARGUMENT; }
+    if ((unsigned long long)search->width * (unsigned long long)search->width + (unsigned long long)search->height * (unsigned long long)search->height >= (1ull << 32)) {
+        set_error("bad sync search: %d x %d — width^2 + height^2 must stay below 2^32 (a squared distance is folded as 32 bits)", search->width, search->height);
+        return GFW_ERR_INVALID_ARGUMENT; }
+    if (p->flags & (256 | 512 | 1024)) {                                     // HAS_IBIS_DATA | HAS_MESH_DATA | HAS_FPD_DATA
+        set_error("the sync search does not cover per-frame IBIS/OIS shifts, lens meshes or focal-plane distortion data (flags 0x%x)", p->flags);
+        return GFW_ERR_INVALID_ARGUMENT; }
+    if (n_pairs > GFW_SYNC_PAIRS_MAX) { set_error("%d pairs: at most %d in a call", n_pairs, GFW_SYNC_PAIRS_MAX); return GFW_ERR_INVALID_ARGUMENT; }
+    if (n_pairs && (!pair_ts_us || !pair_first)) { set_error("bad sync arguments (pairs without pair_ts_us / pair_first)"); return GFW_ERR_INVALID_ARGUMENT; }
+    int total = 0, max_pair = 0;
+    if (n_pairs) {
+        if (pair_first[0] < 0) { set_error("pair 0: pair_first %d is negative", pair_first[0]); return GFW_ERR_INVALID_ARGUMENT; }
+        for (int i = 0; i < n_pairs; ++i) {
+            if (pair_first[i + 1] < pair_first[i]) { set_error("pair %d: pair_first descends (%d after %d)", i, pair_first[i + 1], pair_first[i]); return GFW_ERR_INVALID_ARGUMENT; }
+            const int n = pair_first[i + 1] - pair_first[i];
+            if (n > GFW_SYNC_PAIR_MAX) { set_error("pair %d: %d points, at most %d", i, n, GFW_SYNC_PAIR_MAX); return GFW_ERR_INVALID_ARGUMENT; }
+            if (n > max_pair) max_pair = n;
+        }
+        total = pair_first[n_pairs];
+        if (total && (!points_a || !points_b)) { set_error("bad sync arguments (%d points without points_a / points_b)", total); return GFW_ERR_INVALID_ARGUMENT; }
+    }
+    int n_coarse = n_candidates;
+    if (search_mode < 0) {
+        if (n_candidates && (!candidates || !out.costs)) { set_error("bad sync arguments (candidates without their array / costs)"); return GFW_ERR_INVALID_ARGUMENT; }
+    } else {
+        if (search_mode > 1 || !out.result) { set_error("bad sync arguments (mode %d, or a null result)", search_mode); return GFW_ERR_INVALID_ARGUMENT; }
+        // `search_size as usize` (:113) / `(1000.0 / fps) as isize`, `-steps..steps` (:89-91): saturating casts, NaN -> 0
+        const double v = search_mode == 0 ? search_size_ms : 1000.0 / scaled_fps;
+        const double steps = !(v == v) || v <= 0.0 ? 0.0 : trunc(v);
+        if (steps > 1000000.0) { set_error("a search of %g candidates (search_size_ms %g, scaled_fps %g)", steps * (search_mode ? 2.0 : 1.0), search_size_ms, scaled_fps); return GFW_ERR_INVALID_ARGUMENT; }
+        n_coarse = (int)steps * (search_mode ? 2 : 1);
+    }
+    if (c->tracks.org_n < 1 && c->tracks.sm_n < 1) { set_error("no quaternion tracks set (gfw_set_quaternion_tracks)"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (search_mode < 0 && n_candidates == 0) return GFW_OK;
+    { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
+    HIP_TRY(hipSetDevice(c->device), GFW_ERR_HIP);
+    // pairs, points and candidates through pinned memory in one copy: it is enqueued, the caller's arrays are free on return
+    const size_t tb = sizeof(int64_t) * 2 * (size_t)n_pairs, fb = (sizeof(int32_t) * ((size_t)n_pairs + 1) + 7) / 8 * 8, pb = sizeof(float) * 2 * (size_t)total;
+    const size_t cb = sizeof(double) * 2 * (size_t)n_coarse;
+    const size_t o_first = tb, o_pts = o_first + fb, o_cand = o_pts + pb * 2, staged = o_cand + cb;
+    StagingSlot *ss = nullptr;
+    HIP_TRY(c->sync_ring.acquire(staged + 8, c->stream, &ss), GFW_ERR_HIP);
+    char *h = (char *)ss->h.ptr;
+    const char *d = (const char *)ss->d.ptr;
+    if (n_pairs) { memcpy(h, pair_ts_us, tb); memcpy(h + o_first, pair_first, sizeof(int32_t) * ((size_t)n_pairs + 1)); }
+    else *(int32_t *)(h + o_first) = 0;
+    if (total) { memcpy(h + o_pts, points_a, pb); memcpy(h + o_pts + pb, points_b, pb); }
+    double *hc = (double *)(h + o_cand);
+    if (search_mode < 0) memcpy(hc, candidates, cb);
+    else for (int i = 0; i < n_coarse; ++i) {
+        if (search_mode == 0) { hc[i * 2] = initial_offset_ms + (-(search_size_ms / 2.0) + (double)i); hc[i * 2 + 1] = frame_readout_time_ms; }
+        else { hc[i * 2] = 0.0; hc[i * 2 + 1] = (double)(i - n_coarse / 2); }
+    }
+    HIP_TRY(hipMemcpyAsync(ss->d.ptr, ss->h.ptr, staged + 8, hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
+    HIP_TRY(ss->free_again.record(c->stream), GFW_ERR_HIP);
+    // device work space: rays, partials of the larger stage, the fine candidates
+    const int n_wide = search_mode < 0 ? n_coarse : (n_coarse > GFW_SYNC_FINE ? n_coarse : GFW_SYNC_FINE);
+    const size_t rb = sizeof(float4) * 2 * (size_t)total, qb = sizeof(unsigned long long) * (size_t)n_wide * (size_t)(n_pairs ? n_pairs : 1), eb = sizeof(double) * 2 * GFW_SYNC_FINE;
+    HIP_TRY(c->d_sync_work.ensure(rb + qb + eb + 16), GFW_ERR_HIP);
+    char *wk = (char *)c->d_sync_work.ptr;
+    // outputs: the caller's device memory, or the context's to be copied back
+    const size_t res_b = 48, cc_b = sizeof(double) * (size_t)n_coarse, fc_b = sizeof(double) * GFW_SYNC_FINE;
+    const size_t map_b = out.mapped ? sizeof(float) * 4 * (size_t)total * (size_t)n_coarse : 0;
+    double *d_costs = search_mode < 0 ? out.costs : out.coarse_costs, *d_fine_costs = out.fine_costs;
+    float *d_mapped = out.mapped; gfw_sync_result *d_result = out.result;
+    if (!out_on_device) {
+        HIP_TRY(c->d_sync_out.ensure(res_b + cc_b + fc_b + map_b + 16), GFW_ERR_HIP);
+        char *ob = (char *)c->d_sync_out.ptr;
+        d_result = out.result ? (gfw_sync_result *)ob : nullptr;
+        d_costs = d_costs ? (double *)(ob + res_b) : nullptr;
+        d_fine_costs = d_fine_costs ? (double *)(ob + res_b + cc_b) : nullptr;
+        d_mapped = out.mapped ? (float *)(ob + res_b + cc_b + fc_b) : nullptr;
+    }
+    GfwSyncArgs A;
+    memset(&A, 0, sizeof(A));
+    A.T = c->tracks;
+    if (!search->use_sync_offsets) { A.T.off_ts = nullptr; A.T.off_ms = nullptr; A.T.off_n = 0; }      // clear_offsets()
+    for (int i = 0; i < 9; ++i) A.F.new_k[i] = search->new_k[i];
+    A.F.video_rotation_deg = search->video_rotation_deg;
+    A.pair_ts = (const int64_t *)d; A.pair_first = (const int32_t *)(d + o_first); A.points = (const float *)(d + o_pts);
+    A.rays = (float4 *)wk; A.partial = (unsigned long long *)(wk + rb);
+    A.candidates = (const double *)(d + o_cand); A.mapped = d_mapped;
+    A.w = (float)search->width; A.h = (float)search->height;
+    A.horizontal = search->horizontal_readout; A.readout_dim = search->horizontal_readout ? search->width : search->height;
+    A.n_pairs = n_pairs; A.total = total;
+    GfwCommon C;
+    fill_common(c, p, nullptr, nullptr, 0, C);
+    GfwSyncReduceArgs R;
+    memset(&R, 0, sizeof(R));
+    R.partial = A.partial; R.candidates = A.candidates; R.costs = d_costs; R.result = d_result; R.fine = (double *)(wk + rb + qb);
+    R.n = n_coarse; R.n_pairs = n_pairs; R.column = search_mode == 1 ? 1 : 0; R.stage = 0;
+    HIP_TRY(gfw_launch_sync_rays(*p, C, A, c->stream), GFW_ERR_HIP);
+    HIP_TRY(gfw_launch_sync_costs(A, n_coarse, max_pair, c->stream), GFW_ERR_HIP);
+    HIP_TRY(gfw_launch_sync_reduce(R, c->stream), GFW_ERR_HIP);
+    if (search_mode >= 0) {
+        A.candidates = R.fine; A.gate = d_result; A.mapped = nullptr;
+        HIP_TRY(gfw_launch_sync_costs(A, GFW_SYNC_FINE, max_pair, c->stream), GFW_ERR_HIP);
+        R.candidates = R.fine; R.costs = d_fine_costs; R.n = GFW_SYNC_FINE; R.stage = 1;
+        HIP_TRY(gfw_launch_sync_reduce(R, c->stream), GFW_ERR_HIP);
+    }
+    c->last_backend = search_mode < 0 ? "sync_visual_costs" : "sync_visual_search";
+    if (!out_on_device) {
+        if (out.result) HIP_TRY(hipMemcpyAsync(out.result, d_result, sizeof(gfw_sync_result), hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
+        if (d_costs && cc_b) HIP_TRY(hipMemcpyAsync(search_mode < 0 ? out.costs : out.coarse_costs, d_costs, cc_b, hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
+        if (d_fine_costs) HIP_TRY(hipMemcpyAsync(out.fine_costs, d_fine_costs, fc_b, hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
+        if (map_b) HIP_TRY(hipMemcpyAsync(out.mapped, d_mapped, map_b, hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
+    }
+    if (c->synchronous || !out_on_device) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);
+    return GFW_OK;
+}
+extern "C" int gfw_sync_visual_costs(gfw_ctx *c, const gfw_kernel_params *p, const gfw_sync_search *search, const int64_t *pair_ts_us, const int32_t *pair_first,
+                                     const float *points_a, const float *points_b, int n_pairs, const double *candidates, int n_candidates,
+                                     double *costs, float *mapped, int out_on_device) {
+    const SyncOut out = {costs, mapped, nullptr, nullptr, nullptr};
+    return sync_visual_impl(c, p, search, pair_ts_us, pair_first, points_a, points_b, n_pairs, candidates, n_candidates, -1, 0.0, 0.0, 0.0, 0.0, out, out_on_device);
+}
+extern "C" int gfw_sync_visual_search(gfw_ctx *c, const gfw_kernel_params *p, const gfw_sync_search *search, const int64_t *pair_ts_us, const int32_t *pair_first,
+                                      const float *points_a, const float *points_b, int n_pairs, int mode, double initial_offset_ms, double search_size_ms,
+                                      double frame_readout_time_ms, double scaled_fps, gfw_sync_result *result, double *coarse_costs, double *fine_costs, int out_on_device) {
+    const SyncOut out = {nullptr, nullptr, result, coarse_costs, fine_costs};
+    return sync_visual_impl(c, p, search, pair_ts_us, pair_first, points_a, points_b, n_pairs, nullptr, 0, mode < 0 ? 2 : mode, initial_offset_ms, search_size_ms,
+                            frame_readout_time_ms, scaled_fps, out, out_on_device);
 }

@@ -150,3 +150,39 @@ __device__ __forceinline__ float2 gfw_point_map(const gfw_kernel_params &P, cons
     }
     return o;
 }
+
+// gfw_point_map without shifts, without a mesh and with lens_correction_amount 1.0, in two halves — the same operations in the same order, so the halves composed
+// equal it to the bit: the sync search (gfw_sync.hip) runs the first once per point and the second once per candidate.  (gfw_point_map itself is not built from
+// them: its callers' register allocation moves when it is.)
+// First half — everything in front of the rotation (:704-712, :765-779): the stretches, the digital lens, (x - c) / f, the lens inverse, the refraction -> the
+// ray (ptx, pty); false where the lens inverse is None.
+template <int MODEL>
+__device__ __forceinline__ bool gfw_point_ray(const gfw_kernel_params &P, const GfwCommon &C, float x, float y, float &ptx, float &pty) {
+    if (P.input_horizontal_stretch > 0.001f) x *= P.input_horizontal_stretch;
+    if (P.input_vertical_stretch   > 0.001f) y *= P.input_vertical_stretch;
+    if (C.digital != GFW_MODEL_NONE) {
+        const GfwPt d = gfw_lens::digital_undistort(C.digital, x, y, P);
+        if (d.ok) { x = d.x; y = d.y; }
+    }
+    const float pwx = (x - P.c[0]) / P.f[0], pwy = (y - P.c[1]) / P.f[1];
+    const GfwPt pt = gfw_lens::undistort<MODEL>(C.model, pwx, pwy, P, C);
+    ptx = pt.x; pty = pt.y;
+    if (pt.ok && P.light_refraction_coefficient != 1.0f && P.light_refraction_coefficient > 0.0f) {
+        const float rr = sqrtf(ptx * ptx + pty * pty);
+        if (rr != 0.0f) {
+            const float sin_theta_d = (rr / sqrtf(1.0f + rr * rr)) / P.light_refraction_coefficient;
+            const float r_d = sin_theta_d / sqrtf(1.0f - sin_theta_d * sin_theta_d);
+            const float factor = r_d / rr;
+            ptx *= factor; pty *= factor;
+        }
+    }
+    return pt.ok;
+}
+// Second half — the ray through the point's `new_k * R` (rot: 9 f32, row-major; :782-783, nalgebra gemv: column axpy)
+__device__ __forceinline__ float2 gfw_point_project(float ptx, float pty, const float *rot) {
+    const float *r = rot;
+    const float pr0 = ((r[0] * ptx) + r[1] * pty) + r[2];
+    const float pr1 = ((r[3] * ptx) + r[4] * pty) + r[5];
+    const float pr2 = ((r[6] * ptx) + r[7] * pty) + r[8];
+    return float2{pr0 / pr2, pr1 / pr2};
+}

@@ -1,5 +1,5 @@
-// gfw_quat.h — the f64 quaternion-track device functions shared by the per-row matrix builder (gfw_matrices.hip) and the zoom search
-// (gfw_zoom.hip): GyroSource::quat_at_timestamp / offset_at_timestamp with the reference's rounding and clamping, nalgebra's slerp, and
+// gfw_quat.h — the f64 quaternion-track device functions shared by the per-row matrix builder (gfw_matrices.hip), the zoom search
+// (gfw_zoom.hip) and the sync search (gfw_sync.hip): GyroSource::quat_at_timestamp / offset_at_timestamp with the reference's rounding and clamping, nalgebra's slerp, and
 // the rotation matrix of FrameTransform (image_rotation * R(quat)).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -85,3 +85,15 @@ __device__ __forceinline__ Q quat_prefix(const GfwTracks &T, double ts) {
 }
 
 }  // namespace
+
+// at_timestamp_for_points' rotation of one point, shared by the zoom search and the sync search (gfw_sync.hip) (frame_transform.rs:391-409): new_k * (image_rotation * R(prefix * org(quat_time))) with the four sign flips of
+// :402-403 — always these, whatever framebuffer_inverted says — or new_k alone under suppress_rotation; -> f32, row-major
+__device__ inline void gfw_zoom_rotation(const GfwTracks &T, const gfw_zoom_frame &F, const Q &pre, double quat_time, float out[9]) {
+    double r[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    if (!F.suppress_rotation) {
+        quat_rotation(qmul(pre, quat_at(T, T.org_ts, T.org_q, T.org_n, quat_time)), F.video_rotation_deg, r);
+        r[0][1] *= -1.0; r[0][2] *= -1.0; r[1][0] *= -1.0; r[2][0] *= -1.0;
+    }
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j)
+        out[i * 3 + j] = (float)(F.new_k[i * 3 + 0] * r[0][j] + F.new_k[i * 3 + 1] * r[1][j] + F.new_k[i * 3 + 2] * r[2][j]);
+}

@@ -92,18 +92,6 @@ __device__ __forceinline__ float gfw_zoom_rounds(const Map &map, int t, float w,
     return m0;
 }
 
-// at_timestamp_for_points' rotation of one point (frame_transform.rs:391-409): new_k * (image_rotation * R(prefix * org(quat_time))) with the four sign flips of
-// :402-403 — always these, whatever framebuffer_inverted says — or new_k alone under suppress_rotation; -> f32, row-major
-__device__ inline void gfw_zoom_rotation(const GfwTracks &T, const gfw_zoom_frame &F, const Q &pre, double quat_time, float out[9]) {
-    double r[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-    if (!F.suppress_rotation) {
-        quat_rotation(qmul(pre, quat_at(T, T.org_ts, T.org_q, T.org_n, quat_time)), F.video_rotation_deg, r);
-        r[0][1] *= -1.0; r[0][2] *= -1.0; r[1][0] *= -1.0; r[2][0] *= -1.0;
-    }
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j)
-        out[i * 3 + j] = (float)(F.new_k[i * 3 + 0] * r[0][j] + F.new_k[i * 3 + 1] * r[1][j] + F.new_k[i * 3 + 2] * r[2][j]);
-}
-
 // at_timestamp_for_points' shift of one point (frame_transform.rs:412-429) in the 6-float form gfw_point_map takes (sx, sy, cos, sin, ox, oy).  `y`: the point's own y as
 // given (0 for the single point of a frame without rolling shutter), under horizontal readout too.  Neither the framebuffer sign nor the sensor-height flip of the matrix
 // path (frame_transform.rs:270-289) exists here; cos / sin of +angle, the host libm's (cpu_undistort.rs:753-755)

@@ -312,6 +312,54 @@ class Backend:
                                                 dbg.ctypes.data if debug else None, 0))
         return (fov, dbg) if debug else fov
 
+    @staticmethod
+    def _sync_pairs(pairs):
+        """[(ts_us, next_ts_us, points_a [n][2], points_b [n][2])] -> the flat arrays gfw_sync_visual_* take (kept alive by the caller)"""
+        ts = np.array([[int(a), int(b)] for a, b, _, _ in pairs], dtype=np.int64).reshape(-1, 2)
+        pa = [np.asarray(x, dtype=np.float32).reshape(-1, 2) for _, _, x, _ in pairs]
+        pb = [np.asarray(x, dtype=np.float32).reshape(-1, 2) for _, _, _, x in pairs]
+        assert all(a.shape == b.shape for a, b in zip(pa, pb)), "a pair's two point sets have one length"
+        first = np.zeros(len(pairs) + 1, dtype=np.int32)
+        if pairs:
+            first[1:] = np.cumsum([len(a) for a in pa])
+        cat = lambda v: np.ascontiguousarray(np.concatenate(v), dtype=np.float32) if v else np.zeros((0, 2), dtype=np.float32)
+        return ts, first, cat(pa), cat(pb)
+
+    def sync_visual_costs(self, params, search, pairs, candidates, mapped=False, out_ptr=None, mapped_ptr=None):
+        """calculate_distance (find_offset/visual_features.rs:49-83) of every candidate in one device call (gfw_sync_visual_costs).
+
+        ``params``: the KernelParams `undistort_points` builds; ``search``: abi.SyncSearch; ``pairs``: [(ts_us, next_ts_us, points [n][2], points [n][2])];
+        ``candidates``: [n][2] (offset_ms, frame_readout_time_ms).  Returns float64 [n] — with ``mapped`` also float32 [n][total][2][2], p1 and p2 as
+        mapped — or, with ``out_ptr`` (a device pointer to n doubles; ``mapped_ptr``: None or a device pointer), None: in order on the stream."""
+        ts, first, pa, pb = self._sync_pairs(pairs)
+        cand = np.ascontiguousarray(candidates, dtype=np.float64).reshape(-1, 2)
+        n, total = cand.shape[0], int(first[-1])
+        args = (self.ctx, C.byref(params), C.byref(search), ts.ctypes.data, first.ctypes.data, pa.ctypes.data, pb.ctypes.data, len(pairs), cand.ctypes.data, n)
+        if out_ptr is not None:
+            self._check(self.lib.gfw_sync_visual_costs(*args, out_ptr, mapped_ptr, 1))
+            return None
+        costs = np.zeros(n, dtype=np.float64)
+        pts = np.zeros((n, total, 2, 2), dtype=np.float32) if mapped else None
+        self._check(self.lib.gfw_sync_visual_costs(*args, costs.ctypes.data, pts.ctypes.data if mapped else None, 0))
+        return (costs, pts) if mapped else costs
+
+    def sync_visual_search(self, params, search, pairs, mode, initial_offset_ms=0.0, search_size_ms=0.0, frame_readout_time_ms=0.0, scaled_fps=30.0,
+                           costs=False, result_ptr=None, coarse_ptr=None, fine_ptr=None):
+        """The two-stage search of one range (visual_features.rs:87-131) in one device call (gfw_sync_visual_search): ``mode`` 0 the offset, 1 the readout time.
+        Returns abi.SyncResult — with ``costs`` also the coarse [n_coarse] and fine [200] float64 costs — or, with ``result_ptr`` (a device pointer to a
+        gfw_sync_result; ``coarse_ptr`` / ``fine_ptr``: None or device pointers), None: in order on the stream."""
+        ts, first, pa, pb = self._sync_pairs(pairs)
+        args = (self.ctx, C.byref(params), C.byref(search), ts.ctypes.data, first.ctypes.data, pa.ctypes.data, pb.ctypes.data, len(pairs), int(mode),
+                float(initial_offset_ms), float(search_size_ms), float(frame_readout_time_ms), float(scaled_fps))
+        if result_ptr is not None:
+            self._check(self.lib.gfw_sync_visual_search(*args, result_ptr, coarse_ptr, fine_ptr, 1))
+            return None
+        res = abi.SyncResult()
+        n_coarse = sync_coarse_count(mode, search_size_ms, scaled_fps)
+        coarse, fine = np.zeros(max(n_coarse, 1), dtype=np.float64), np.zeros(abi.SYNC_FINE_CANDIDATES, dtype=np.float64)
+        self._check(self.lib.gfw_sync_visual_search(*args, C.cast(C.byref(res), C.c_void_p), coarse.ctypes.data if costs else None, fine.ctypes.data if costs else None, 0))
+        return (res, coarse[:n_coarse], fine) if costs else res
+
     def synchronize(self):
         self._check(self.lib.gfw_synchronize(self.ctx))
 
@@ -348,6 +396,13 @@ class Backend:
             mesh = np.ascontiguousarray(mesh, dtype=np.float32)
             meshp, meshn = mesh.ctypes.data, mesh.size
         self._check(self.lib.gfw_undistort_frame(self.ctx, n, barr, parr, tarr, mp, mc, meshp, meshn))
+
+
+def sync_coarse_count(mode, search_size_ms, scaled_fps):
+    """candidates of the first stage: `search_size as usize` (visual_features.rs:113), or `-steps..steps` with steps = (1000.0 / fps) as isize (:89-91)"""
+    v = float(search_size_ms) if int(mode) == 0 else (1000.0 / float(scaled_fps) if scaled_fps else float("inf"))
+    steps = 0 if v != v or v <= 0.0 else int(min(v, 2.0 ** 62))
+    return steps if int(mode) == 0 else 2 * steps
 
 
 def zoom_smooth(fov_minimal, adaptive_zoom_window, scaled_fps, method=0, trim_ranges=()):

@@ -558,6 +558,59 @@ int   gfw_zoom_fovs_stab(gfw_ctx *ctx, const gfw_kernel_params *params, const gf
 int   gfw_zoom_smooth(const double *fov_minimal, int n, double adaptive_zoom_window, double scaled_fps, int method,
                       const double *trim_ranges, int n_ranges, double *fovs_out, double *fov_minimal_out);
 
+/* ---- synchronization: the visual-features offset / readout-time search of a range in one device call ----
+ * find_offset/visual_features.rs:10-147.  A range has matched frame pairs ((ts, points), (next_ts, points)); calculate_distance
+ * (:49-83) of a candidate (offset_ms, frame_readout_time_ms) maps both point sets of every pair through
+ * undistort_points_with_rolling_shutter at `ts_us as f64 / 1000.0 - offset` (per point the rotation of at_timestamp_for_points,
+ * frame_transform.rs:376-410, with per_frame_time_offset 0 and the readout time of the candidate — negative and zero included:
+ * |readout| > 0 decides rolling, otherwise ONE rotation at ts - readout / 2 serves every point — and the inverse point map of
+ * gfw_undistort_points with lens_correction_amount 1.0), keeps a point pair when both mapped points lie strictly inside
+ * (0, w) x (0, h), takes `dist as u64` of the f32 squared distance, and adds the k = (n_valid as f64 * 0.9) as usize smallest of
+ * each pair.  Costs are sums of integers, far below 2^53: the device adds them as u64 and converts once, which equals the
+ * reference's sequential f64 adds; given the mapped points a cost is exact.
+ *   params     the KernelParams undistort_points builds, as for gfw_undistort_points; lens_correction_amount and fov are not read
+ *   search     what the candidates share (below); rotations come from the tracks of gfw_set_quaternion_tracks, and with
+ *              use_sync_offsets = 1 from gfw_set_sync_offsets as well (for_rs keeps the offsets, the offset search clears them)
+ *   pair_ts_us [n_pairs][2] the two timestamps of a pair; pair_first [n_pairs + 1] ascending: pair p owns the points
+ *              pair_first[p] .. pair_first[p + 1] - 1 of points_a (first frame) and points_b (second frame), [total][2] f32,
+ *              source-image pixels; at most 4096 points in a pair, at most 65535 pairs; a pair of 0 points contributes 0
+ *   candidates [n_candidates][2] f64 (offset_ms, frame_readout_time_ms), host memory
+ *   costs      [n_candidates] f64; mapped NULL or [n_candidates][total][2][2] f32: p1 and p2 of every point pair as mapped
+ *              ((-1e6, -1e6) where the lens inverse is None); both host or both device memory (out_on_device)
+ * n_pairs = 0: every cost is 0.  n_candidates = 0 succeeds and writes nothing.
+ * gfw_sync_visual_search is the two-stage search of one range (:87-131) without a host round trip — lens stage, coarse costs,
+ * reduce + pick, fine costs of the 200 candidates `lowest.0 - 1.0 + i * 0.01` generated on the device, reduce + pick:
+ *   mode 0     offset: search_size_ms as usize candidates initial_offset + (-(search_size / 2.0) + i), the given readout time
+ *   mode 1     readout time (for_rs): steps = (1000.0 / scaled_fps) as isize, candidates i in -steps..steps, offset 0
+ * `reduce_with(find_min)` with `if a.1 < b.1 { a } else { b }`: of equal minimal costs the LAST candidate wins, in both stages.
+ *   result     found = 0 when the coarse stage has no candidates (then nothing else is meaningful); n_coarse; the coarse pick
+ *              and its cost; value / cost: the fine pick (an offset_ms or a readout time in ms)
+ *   coarse_costs / fine_costs   NULL or [n_coarse] / [200] f64; with result host or device memory (out_on_device)
+ * The 90 %-of-range acceptance rule (:137) and the range's middle timestamp are the caller's (gyroflow::find_offsets_visual,
+ * gyroflow_amd.synchronization).  Both calls run in order on the context's stream; with device outputs an asynchronous context
+ * returns without waiting.  Rejected with GFW_ERR_INVALID_ARGUMENT, the pair named in gfw_last_error(), outputs untouched:
+ * negative counts, a descending pair_first, more than 4096 points in a pair, width^2 + height^2 >= 2^32, params->flags with
+ * HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA, a non-zero reserved slot, no tracks.
+ * NOT covered: clips with per_frame_time_offsets, camera_stab_data or mesh_correction (in the reference the frame index, and so
+ * the mesh, follows `timestamp - offs`); lens data or a video rotation keyframed inside a range; suppress_rotation; optical
+ * flow, pose estimation, rs_sync, essential_matrix, optimsync. */
+typedef struct gfw_sync_search {
+    int32_t width, height;            /* params.width / height: the bounds test (`w as f32`) and the readout divisor */
+    int32_t horizontal_readout;
+    int32_t use_sync_offsets;         /* 0 = clear_offsets() (visual_features.rs:13-15: the offset search); 1 = keep the context's (for_rs) */
+    double  new_k[9];                 /* get_new_k(params, camera_matrix, get_fov(use_fovs = false)), row-major */
+    double  video_rotation_deg;
+    int32_t reserved[2];              /* 0 */
+} gfw_sync_search;
+typedef struct gfw_sync_result { int32_t found, n_coarse; double coarse_value, coarse_cost, value, cost; } gfw_sync_result;
+int   gfw_sync_visual_costs(gfw_ctx *ctx, const gfw_kernel_params *params, const gfw_sync_search *search,
+                            const int64_t *pair_ts_us, const int32_t *pair_first, const float *points_a, const float *points_b, int n_pairs,
+                            const double *candidates, int n_candidates, double *costs, float *mapped, int out_on_device);
+int   gfw_sync_visual_search(gfw_ctx *ctx, const gfw_kernel_params *params, const gfw_sync_search *search,
+                             const int64_t *pair_ts_us, const int32_t *pair_first, const float *points_a, const float *points_b, int n_pairs,
+                             int mode, double initial_offset_ms, double search_size_ms, double frame_readout_time_ms, double scaled_fps,
+                             gfw_sync_result *result, double *coarse_costs, double *fine_costs, int out_on_device);
+
 /* First-pass audit of the fused kernel (GFW_OPT_KERNEL_VARIANT = 3): counters8 = {certified pixels,
  * certified-but-different-from-exact (must stay 0), queued to the exact path, queue overflows,
  * max |approximate - exact| coordinate over certified pixels as f32 bits, addresses outside their buffer (audit mode range-checks),

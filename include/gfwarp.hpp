@@ -338,4 +338,42 @@ inline std::pair<std::vector<double>, std::vector<double>> calculate_fovs(gfw_ct
     return {fovs, trimmed};
 }
 
+// ---- synchronization/find_offset/visual_features.rs:10-147 `find_offsets` over gfw_sync_visual_search: the offset (or, with for_rs, the frame readout time) of
+// every range, one device call per range.  `ctx`: a context of the clip's lens models whose tracks are set (gfw_set_quaternion_tracks; with for_rs the sync offsets
+// too: the offset search clears them, :13-15 — `search.use_sync_offsets` is set from for_rs here).  `matched`: what get_of_lines_for_timestamp returns for the keys of
+// the estimator's sync results, ascending by timestamp; entries whose point sets are empty or of different lengths are skipped (:36-40).
+// -> (timestamp, offset, cost) per range that has candidates and, for the offset search, passes the 90 %-of-range rule (:137).
+struct SyncParams { double initial_offset = 0.0, search_size = 0.0; };                              // ms (synchronization/mod.rs)
+struct MatchedPoints { int64_t timestamp_us = 0, next_timestamp_us = 0; std::vector<std::pair<float, float>> points, next_points; };
+inline std::vector<std::tuple<double, double, double>> find_offsets_visual(gfw_ctx *ctx, const KernelParams &params, gfw_sync_search search,
+                                                                           const std::vector<std::pair<int64_t, int64_t>> &ranges, const std::vector<MatchedPoints> &matched,
+                                                                           const SyncParams &sync_params, double frame_readout_time_ms, double scaled_fps, bool for_rs = false) {
+    std::vector<std::tuple<double, double, double>> final_offsets;
+    search.use_sync_offsets = for_rs ? 1 : 0;
+    for (const auto &range : ranges) {
+        std::vector<int64_t> ts;
+        std::vector<int32_t> first{0};
+        std::vector<float> a, b;
+        for (const MatchedPoints &m : matched) {
+            if (m.timestamp_us < range.first || m.timestamp_us >= range.second) continue;             // (*from_ts..*to_ts).contains(ts)
+            if (m.points.empty() || m.points.size() != m.next_points.size()) continue;
+            ts.push_back(m.timestamp_us); ts.push_back(m.next_timestamp_us);
+            for (const auto &pt : m.points) { a.push_back(pt.first); a.push_back(pt.second); }
+            for (const auto &pt : m.next_points) { b.push_back(pt.first); b.push_back(pt.second); }
+            first.push_back((int32_t)(a.size() / 2));
+        }
+        gfw_sync_result r;
+        std::memset(&r, 0, sizeof(r));
+        const int rc = gfw_sync_visual_search(ctx, &params, &search, ts.data(), first.data(), a.data(), b.data(), (int)(ts.size() / 2), for_rs ? 1 : 0,
+                                              sync_params.initial_offset, sync_params.search_size, frame_readout_time_ms, scaled_fps, &r, nullptr, nullptr, 0);
+        if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+        if (!r.found) continue;
+        if (for_rs) { final_offsets.emplace_back(0.0, r.value, r.cost); continue; }                 // :109
+        const double middle_timestamp = ((double)range.first + (double)(range.second - range.first) / 2.0) / 1000.0;
+        const double d = r.value - sync_params.initial_offset;
+        if ((d < 0.0 ? -d : d) < sync_params.search_size * 0.9) final_offsets.emplace_back(middle_timestamp, r.value, r.cost);       // :137
+    }
+    return final_offsets;
+}
+
 }  // namespace gyroflow
