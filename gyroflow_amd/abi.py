@@ -117,6 +117,9 @@ class SyncResult(C.Structure):
 
 SYNC_FINE_CANDIDATES = 200       # the second stage's candidates
 SYNC_PAIR_POINTS_MAX = 4096
+SYNC_GYRO_RANGES_MAX, SYNC_GYRO_EST_MAX, SYNC_GYRO_SAMPLES_MAX, SYNC_GYRO_CANDIDATES_MAX = 65535, 65536, 1 << 22, 2000000      # gfw_sync_gyro_*: per call / per range
+SYNC_GYRO_RING_SLOTS = 2         # staging slots of gfw_sync_gyro_*: calls an asynchronous context takes before one waits for an earlier copy
+FILTER_NOT_APPLIED = 1           # gfw_lowpass_gyro: the reference's from_params would fail; the data is untouched
 ZOOM_RECT_POINTS = 120           # points_around_rect(w, h, 31, 31)
 
 
@@ -196,6 +199,9 @@ def bind(lib):
     lib.gfw_sync_visual_costs.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(SyncSearch), vp, vp, vp, vp, i32, vp, i32, vp, vp, i32]; lib.gfw_sync_visual_costs.restype = i32
     lib.gfw_sync_visual_search.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(SyncSearch), vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp, i32]
     lib.gfw_sync_visual_search.restype = i32
+    lib.gfw_lowpass_gyro.argtypes = [C.c_double, C.c_double, vp, vp, i32]; lib.gfw_lowpass_gyro.restype = i32
+    lib.gfw_sync_gyro_costs.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, i32, vp, i32]; lib.gfw_sync_gyro_costs.restype = i32
+    lib.gfw_sync_gyro_search.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, i32]; lib.gfw_sync_gyro_search.restype = i32
     lib.gfw_pack_matrices.argtypes = [vp, i32, vp]; lib.gfw_pack_matrices.restype = i32
     lib.gfw_checksum64.argtypes = [vp, vp, sz, vp]; lib.gfw_checksum64.restype = i32
     lib.gfw_set_frame_checksums.argtypes = [vp, vp, sz]; lib.gfw_set_frame_checksums.restype = i32
@@ -219,7 +225,8 @@ EXPORTS = ["gfw_abi_version", "gfw_list_devices", "gfw_set_device", "gfw_get_inf
            "gfw_get_stream", "gfw_set_stream", "gfw_synchronize", "gfw_flush", "gfw_import_external_fd", "gfw_release_external", "gfw_last_backend", "gfw_get_profile", "gfw_last_error", "gfw_debug_math", "gfw_debug_jit_key", "gfw_debug_selftest", "gfw_get_audit", "gfw_pack_matrices", "gfw_checksum64", "gfw_set_frame_checksums", "gfw_set_quaternion_tracks", "gfw_build_matrices", "gfw_build_matrices_stab", "gfw_set_sync_offsets", "gfw_build_matrices_batch", "gfw_stmap_undistort", "gfw_undistort_points",
            "gfw_pixel_type_info", "gfw_undistort_clip", "gfw_undistort_clip_params", "gfw_jit_status", "gfw_get_profile_frames", "gfw_debug_jit_compile", "gfw_debug_source_id", "gfw_debug_p1_radial", "gfw_debug_paired_launches", "gfw_debug_frames_per_launch",
            "gfw_debug_jit_key_clip_params", "gfw_zoom_fovs", "gfw_zoom_smooth",
-           "gfw_build_matrices_batch_stab", "gfw_zoom_fovs_stab", "gfw_sync_visual_costs", "gfw_sync_visual_search"]
+           "gfw_build_matrices_batch_stab", "gfw_zoom_fovs_stab", "gfw_sync_visual_costs", "gfw_sync_visual_search",
+           "gfw_lowpass_gyro", "gfw_sync_gyro_costs", "gfw_sync_gyro_search"]
 
 
 def load_library(path=None):

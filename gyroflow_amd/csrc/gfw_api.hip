@@ -14,6 +14,7 @@
 #include <string>
 #include <utility>
 #include <vector>
+#include <algorithm>
 
 #include "../../include/gfwarp.h"
 #include "../../include/gfwarp_testing.h"
@@ -23,6 +24,8 @@
 #include "gfw_matrices.h"
 #include "gfw_zoom.h"
 #include "gfw_sync.h"
+#include "gfw_sync_gyro.h"
+#include "gfw_sync_gyro_host.h"
 #include "gfw_jit.h"
 #include <stdlib.h>
 #include <map>
@@ -101,6 +104,9 @@ struct gfw_ctx {
     StagingRing<1> zoom_ring; DevBuf d_zoom_out;
     // gfw_sync_visual_*: pairs, points and candidates staged the same way; rays / partial sums / fine candidates; results for host outputs
     StagingRing<1> sync_ring; DevBuf d_sync_work, d_sync_out;
+    // gfw_sync_gyro_*: ranges, estimated samples, gyro keys and values, candidates staged the same way (work space and host-output space: the visual search's)
+    static constexpr int kGyroSlots = 2;
+    StagingRing<kGyroSlots> gyro_ring;
     // context-owned per-row tables built on the device (gfw_build_matrices): a small ring, built on copy_stream so that
     // frame N+1's table is produced while frame N is being warped; events order builder and consumer both ways
     struct BuiltSlot { DevBuf buf; Event built, consumed; };   // buf = rows + 4 doubles of builder scratch

@@ -593,3 +593,136 @@ extern "C" int gfw_sync_visual_search(gfw_ctx *c, const gfw_kernel_params *p, co
     return sync_visual_impl(c, p, search, pair_ts_us, pair_first, points_a, points_b, n_pairs, nullptr, 0, mode < 0 ? 2 : mode, initial_offset_ms, search_size_ms,
                             frame_readout_time_ms, scaled_fps, out, out_on_device);
 }
+
+// Lowpass::filter_gyro_forward_backward (filtering.rs:46-74) of a gyro triple series, in place: biquad's second-order Butterworth low-pass (Q = FRAC_1_SQRT_2) in
+// transposed direct form II, forward then backward, one filter per axis and direction; entries without a gyro do not advance the state.  See include/gfwarp.h.
+extern "C" int gfw_lowpass_gyro(double freq, double sample_rate, double *xyz, const uint8_t *has, int n) {
+    if (n < 0 || (n && !xyz)) { set_error("bad lowpass arguments (n %d)", n); return GFW_ERR_INVALID_ARGUMENT; }
+    // Coefficients::from_params fails for 2 f0 > fs (and the reference ignores the failure: essential_matrix.rs:47-48)
+    if (!std::isfinite(freq) || !std::isfinite(sample_rate) || !(freq > 0.0) || !(sample_rate > 0.0) || 2.0 * freq > sample_rate) return GFW_FILTER_NOT_APPLIED;
+    const double omega = 2.0 * 3.14159265358979323846 * freq / sample_rate;
+    const double omega_s = sin(omega), omega_c = cos(omega);
+    const double alpha = omega_s / (2.0 * 0.70710678118654752440);
+    const double b0 = (1.0 - omega_c) * 0.5, b1 = 1.0 - omega_c, b2 = (1.0 - omega_c) * 0.5;
+    const double a0 = 1.0 + alpha, a1 = -2.0 * omega_c, a2 = 1.0 - alpha;
+    const double cb0 = b0 / a0, cb1 = b1 / a0, cb2 = b2 / a0, ca1 = a1 / a0, ca2 = a2 / a0;
+    for (int pass = 0; pass < 2; ++pass) {
+        double s1[3] = {0.0, 0.0, 0.0}, s2[3] = {0.0, 0.0, 0.0};
+        for (int k = 0; k < n; ++k) {
+            const int i = pass ? n - 1 - k : k;
+            if (has && !has[i]) continue;
+            for (int a = 0; a < 3; ++a) {
+                const double x = xyz[(size_t)i * 3 + a];
+                const double out = s1[a] + cb0 * x;
+                s1[a] = s2[a] + cb1 * x - ca1 * out;
+                s2[a] = cb2 * x - ca2 * out;
+                xyz[(size_t)i * 3 + a] = out;
+            }
+        }
+    }
+    return GFW_OK;
+}
+
+// The gyro-match sync search (find_offset/essential_matrix.rs:52-75, :109-131; gfw_sync_gyro.hip).  See include/gfwarp.h for the argument contract.  One body serves
+// both entries: `search` false = gfw_sync_gyro_costs (the caller's candidates), true = gfw_sync_gyro_search (the coarse candidates are made here, the fine ones on the device).
+struct GyroSeries { const int32_t *first; const double *data; const uint8_t *has; int total; const char *what; int limit; };
+static bool gyro_series_ok(const GyroSeries &s, int n_ranges, bool needs_data = true) {
+    if (!s.first || s.total < 0) { set_error("bad sync arguments (%s: a null first array, or a negative length %d)", s.what, s.total); return false; }
+    if (s.first[0] < 0) { set_error("range 0: %s first %d is negative", s.what, s.first[0]); return false; }
+    for (int r = 0; r < n_ranges; ++r) {
+        if (s.first[r + 1] < s.first[r]) { set_error("range %d: %s first descends (%d after %d)", r, s.what, s.first[r + 1], s.first[r]); return false; }
+        if (s.first[r + 1] > s.total) { set_error("range %d: %s slice %d .. %d lies outside its array of %d", r, s.what, s.first[r], s.first[r + 1], s.total); return false; }
+        if (s.first[r + 1] - s.first[r] > s.limit) { set_error("range %d: %d %s, at most %d", r, s.first[r + 1] - s.first[r], s.what, s.limit); return false; }
+    }
+    if (needs_data && s.first[n_ranges] > 0 && !s.data) { set_error("bad sync arguments (%d %s without their array)", s.first[n_ranges], s.what); return false; }
+    return true;
+}
+static int sync_gyro_impl(gfw_ctx *c, const GyroSeries &est, const GyroSeries &gyro, int n_ranges, const GyroSeries &cand, bool search,
+                          double initial_offset_ms, double search_size_ms, double *costs, gfw_sync_result *results, double *coarse_costs, double *fine_costs, int out_on_device) {
+    if (!c || n_ranges < 0) { set_error("bad sync arguments (null context, or a negative range count)"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (n_ranges > GFW_GYRO_RANGES_MAX) { set_error("%d ranges: at most %d in a call", n_ranges, GFW_GYRO_RANGES_MAX); return GFW_ERR_INVALID_ARGUMENT; }
+    size_t n_coarse = 0;
+    if (search) {
+        if (!std::isfinite(initial_offset_ms) || !std::isfinite(search_size_ms) || search_size_ms < 0.0) {
+            set_error("bad sync search: initial_offset_ms %g, search_size_ms %g", initial_offset_ms, search_size_ms); return GFW_ERR_INVALID_ARGUMENT; }
+        if (search_size_ms * 2.0 > (double)GFW_GYRO_COARSE_MAX) { set_error("a search of %g candidates a range (search_size_ms %g), at most %d", trunc(search_size_ms) * 2.0, search_size_ms, GFW_GYRO_COARSE_MAX); return GFW_ERR_INVALID_ARGUMENT; }
+        n_coarse = (size_t)search_size_ms * 2;                              // `search_size as usize * 2` (:55): the cast comes first
+        if (n_ranges && !results) { set_error("bad sync arguments (a null result array)"); return GFW_ERR_INVALID_ARGUMENT; }
+    } else if (n_ranges && !costs) { set_error("bad sync arguments (a null cost array)"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (n_ranges == 0) return GFW_OK;
+    if (!gyro_series_ok(est, n_ranges) || !gyro_series_ok(gyro, n_ranges) || (!search && !gyro_series_ok(cand, n_ranges))) return GFW_ERR_INVALID_ARGUMENT;
+    const size_t tot_est = (size_t)est.first[n_ranges] - (size_t)est.first[0], tot_gyro = (size_t)gyro.first[n_ranges] - (size_t)gyro.first[0];
+    const size_t tot_cand = search ? n_coarse * (size_t)n_ranges : (size_t)cand.first[n_ranges] - (size_t)cand.first[0];
+    const size_t o_est = sizeof(GfwGyroRange) * (size_t)n_ranges, o_has = o_est + 32 * tot_est, o_keys = o_has + (tot_est + 7) / 8 * 8, o_val = o_keys + 8 * tot_gyro;
+    const size_t o_cand = o_val + 32 * tot_gyro, staged = o_cand + 8 * tot_cand + 8;
+    if (staged > ((size_t)1 << 31)) { set_error("the call stages %zu bytes (%zu estimated samples, %zu gyro samples, %zu candidates): at most 2 GiB", staged, tot_est, tot_gyro, tot_cand); return GFW_ERR_INVALID_ARGUMENT; }
+    if (!search && tot_cand == 0) return GFW_OK;
+    { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
+    HIP_TRY(hipSetDevice(c->device), GFW_ERR_HIP);
+    // everything through pinned memory in one copy: it is enqueued, the caller's arrays are free on return
+    StagingSlot *ss = nullptr;
+    HIP_TRY(c->gyro_ring.acquire(staged, c->stream, &ss), GFW_ERR_HIP);
+    char *h = (char *)ss->h.ptr;
+    const char *d = (const char *)ss->d.ptr;
+    GfwGyroRange *hr = (GfwGyroRange *)h;
+    double *h_est = (double *)(h + o_est), *h_val = (double *)(h + o_val), *h_cand = (double *)(h + o_cand);
+    uint8_t *h_has = (uint8_t *)(h + o_has);
+    unsigned long long *h_keys = (unsigned long long *)(h + o_keys);
+    const GfwGyroSeries se = {est.first, est.data, est.has}, sg = {gyro.first, gyro.data, gyro.has};
+    const int max_cand = gfw_gyro_stage(se, sg, n_ranges, search ? nullptr : cand.first, cand.data, n_coarse, initial_offset_ms, search_size_ms, hr, h_est, h_has, h_keys, h_val, h_cand);
+    HIP_TRY(hipMemcpyAsync(ss->d.ptr, ss->h.ptr, staged, hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
+    // outputs: the caller's device memory, or the context's to be copied back; what the caller does not ask for lives in the work space
+    const size_t res_b = (sizeof(gfw_sync_result) * (size_t)n_ranges + 7) / 8 * 8, cc_b = 8 * tot_cand, fc_b = 8 * GFW_GYRO_FINE * (size_t)n_ranges;
+    // caller-given candidates: range r's costs are the caller's entries cand_first[r] ..; the staged ranges count from 0, so the base moves by cand_first[0]
+    double *const costs_out = search ? coarse_costs : costs + cand.first[0];
+    double *d_costs = costs_out, *d_fine_costs = fine_costs;
+    gfw_sync_result *d_results = results;
+    if (!out_on_device) {
+        HIP_TRY(c->d_sync_out.ensure(res_b + cc_b + fc_b + 16), GFW_ERR_HIP);
+        char *ob = (char *)c->d_sync_out.ptr;
+        d_results = (gfw_sync_result *)ob;
+        d_costs = d_costs ? (double *)(ob + res_b) : nullptr;
+        d_fine_costs = d_fine_costs ? (double *)(ob + res_b + cc_b) : nullptr;
+    }
+    HIP_TRY(c->d_sync_work.ensure(fc_b * 2 + cc_b + 16), GFW_ERR_HIP);
+    double *wk = (double *)c->d_sync_work.ptr;
+    GfwGyroArgs A;
+    memset(&A, 0, sizeof(A));
+    A.ranges = (const GfwGyroRange *)d; A.est = (const double *)(d + o_est); A.est_has = (const uint8_t *)(d + o_has);
+    A.keys = (const unsigned long long *)(d + o_keys); A.gyro = (const double *)(d + o_val);
+    A.candidates = (const double *)(d + o_cand); A.costs = d_costs ? d_costs : wk + 2 * GFW_GYRO_FINE * (size_t)n_ranges; A.stage = 0;
+    HIP_TRY(gfw_launch_gyro_costs(A, n_ranges, max_cand, c->stream), GFW_ERR_HIP);
+    if (search) {
+        GfwGyroPickArgs R;
+        memset(&R, 0, sizeof(R));
+        R.ranges = A.ranges; R.candidates = A.candidates; R.costs = A.costs; R.results = d_results; R.fine = wk; R.stage = 0;
+        HIP_TRY(gfw_launch_gyro_pick(R, n_ranges, c->stream), GFW_ERR_HIP);
+        A.candidates = wk; A.costs = d_fine_costs ? d_fine_costs : wk + GFW_GYRO_FINE * (size_t)n_ranges; A.gate = d_results; A.stage = 1;
+        HIP_TRY(gfw_launch_gyro_costs(A, n_ranges, GFW_GYRO_FINE, c->stream), GFW_ERR_HIP);
+        R.candidates = wk; R.costs = A.costs; R.fine_costs = d_fine_costs; R.stage = 1;
+        HIP_TRY(gfw_launch_gyro_pick(R, n_ranges, c->stream), GFW_ERR_HIP);
+    }
+    HIP_TRY(ss->free_again.record(c->stream), GFW_ERR_HIP);                 // behind the last launch that reads the slot's device side
+    c->last_backend = search ? "sync_gyro_search" : "sync_gyro_costs";
+    if (!out_on_device) {
+        if (search) HIP_TRY(hipMemcpyAsync(results, d_results, sizeof(gfw_sync_result) * (size_t)n_ranges, hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
+        if (d_costs && cc_b) HIP_TRY(hipMemcpyAsync(costs_out, d_costs, cc_b, hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
+        if (d_fine_costs) HIP_TRY(hipMemcpyAsync(fine_costs, d_fine_costs, fc_b, hipMemcpyDeviceToHost, c->stream), GFW_ERR_HIP);
+    }
+    if (c->synchronous || !out_on_device) HIP_TRY(hipStreamSynchronize(c->stream), GFW_ERR_HIP);
+    return GFW_OK;
+}
+extern "C" int gfw_sync_gyro_costs(gfw_ctx *c, const int32_t *est_first, const double *est, const uint8_t *est_has, int n_est,
+                                   const int32_t *gyro_first, const double *gyro, const uint8_t *gyro_has, int n_gyro, int n_ranges,
+                                   const int32_t *cand_first, const double *candidates, int n_candidates, double *costs, int out_on_device) {
+    const GyroSeries e = {est_first, est, est_has, n_est, "estimated samples", GFW_GYRO_EST_MAX}, g = {gyro_first, gyro, gyro_has, n_gyro, "gyro samples", GFW_GYRO_SAMPLES_MAX};
+    const GyroSeries k = {cand_first, candidates, nullptr, n_candidates, "candidates", GFW_GYRO_COARSE_MAX};
+    return sync_gyro_impl(c, e, g, n_ranges, k, false, 0.0, 0.0, costs, nullptr, nullptr, nullptr, out_on_device);
+}
+extern "C" int gfw_sync_gyro_search(gfw_ctx *c, const int32_t *est_first, const double *est, const uint8_t *est_has, int n_est,
+                                    const int32_t *gyro_first, const double *gyro, const uint8_t *gyro_has, int n_gyro, int n_ranges,
+                                    double initial_offset_ms, double search_size_ms, gfw_sync_result *results, double *coarse_costs, double *fine_costs, int out_on_device) {
+    const GyroSeries e = {est_first, est, est_has, n_est, "estimated samples", GFW_GYRO_EST_MAX}, g = {gyro_first, gyro, gyro_has, n_gyro, "gyro samples", GFW_GYRO_SAMPLES_MAX};
+    const GyroSeries k = {nullptr, nullptr, nullptr, 0, "candidates", GFW_GYRO_COARSE_MAX};
+    return sync_gyro_impl(c, e, g, n_ranges, k, true, initial_offset_ms, search_size_ms, nullptr, results, coarse_costs, fine_costs, out_on_device);
+}

@@ -1,5 +1,6 @@
-"""Host-side mirror of ``src/core/synchronization/find_offset/visual_features.rs``: the "visual features" offset search and, with ``for_rs``,
-the rolling-shutter (frame readout time) estimator.
+"""Host-side mirrors of ``src/core/synchronization/find_offset/``: the "visual features" offset search (visual_features.rs) and, with ``for_rs``,
+the rolling-shutter (frame readout time) estimator; the gyro-match offset search (essential_matrix.rs, offset method 0) and the fast initial offset
+rs-sync starts from (rs_sync.rs:26-45).
 
     offsets = synchronization.find_offsets_visual(compute_params, ranges, matched_points, sync_params, backend)
 
@@ -9,7 +10,15 @@ range is ONE device call, ``Backend.sync_visual_search`` (gfw_sync_visual_search
 The 90 %-of-range acceptance rule (:137) and the range's middle timestamp are applied here.
 
 Not covered: clips with per-frame time offsets, stabiliser data or lens meshes, keyframed lens data or video rotation inside a range,
-suppress_rotation; the optical flow that produces the matched points, pose estimation, rs_sync, essential_matrix, optimsync.
+suppress_rotation; the optical flow that produces the matched points, pose estimation, rs_sync itself, optimsync.
+
+    offsets = synchronization.find_offsets_essential(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params, backend)
+    initial_offset, search_size = synchronization.initial_offset_fast(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params, backend)
+
+``find_offsets`` of essential_matrix.rs:13-91 matches the angular rates pose estimation produced against the gyro's, per range over
+``2 * search_size`` coarse and 200 fine candidate offsets; here ALL ranges are one device call, ``Backend.sync_gyro_search`` (gfw_sync_gyro_search).  The guards,
+the range cut, the gyro window, the max-angle skip, the two 20 Hz low-pass calls (``warp.lowpass_gyro``), the 90 % rule and the middle timestamp are applied
+here.  The estimated rates are the caller's input: pose estimation is not covered.
 """
 import numpy as np
 
@@ -66,3 +75,87 @@ def find_offsets_visual(compute_params, ranges, matched_points, sync_params, bac
                 if abs(r.value - sync_params.initial_offset) < sync_params.search_size * 0.9:      # :137
                     out.append((middle_timestamp, r.value, r.cost))
     return out
+
+
+def _max_angle(items):
+    """get_max_angle (essential_matrix.rs:93-103)"""
+    m = 0.0
+    for _, g in items:
+        if g is not None:
+            for v in g:
+                if abs(v) > m:
+                    m = abs(v)
+    return m
+
+
+def _lowpassed(freq, sample_rate, items):
+    """filter_gyro_forward_backward over [(timestamp_ms, gyro or None)]; the reference ignores the filter's refusal (2 * freq > sample_rate) and goes on unfiltered"""
+    from . import warp
+    has = np.array([g is not None for _, g in items], dtype=np.uint8)
+    xyz = np.array([g if g is not None else (0.0, 0.0, 0.0) for _, g in items], dtype=np.float64).reshape(-1, 3)
+    out, _applied = warp.lowpass_gyro(freq, sample_rate, xyz, has)
+    rows = np.zeros((len(items), 4), dtype=np.float64)
+    rows[:, 0] = [t for t, _ in items]
+    rows[:, 1:] = out
+    return rows, has
+
+
+def essential_ranges(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params):
+    """The host half of essential_matrix.rs:13-50 -> [(range index, (est [n][4], est_has, gyro [m][4], gyro_has))] for the ranges that reach the search.
+
+    ``estimated_gyro``: {timestamp_us: (timestamp_ms, (x, y, z) or None)} (the estimator's BTreeMap<i64, TimeIMU>); ``raw_imu``: [(timestamp_ms, (x, y, z) or None)]."""
+    out = []
+    raw_imu_len = len(raw_imu)
+    if not estimated_gyro or not (duration_ms > 0.0) or raw_imu_len == 0:                              # :22
+        return out
+    keys = sorted(estimated_gyro)
+    for i, (from_ts, to_ts) in enumerate(ranges):
+        if to_ts <= from_ts:                                                                             # :26
+            continue
+        of_item = [estimated_gyro[k] for k in keys if from_ts <= k < to_ts]                              # range(from_ts..to_ts): the end excluded
+        if not of_item:
+            continue
+        first, last = of_item[0][0], of_item[-1][0]
+        gyro_item = [x for x in raw_imu
+                     if first - sync_params.search_size <= x[0] + sync_params.initial_offset <= last + sync_params.search_size]      # :31-38
+        if _max_angle(of_item) < 3.0:                                                                    # :40-44, on the unfiltered samples
+            continue
+        sample_rate = float(raw_imu_len) / (duration_ms / 1000.0)
+        est, est_has = _lowpassed(20.0, scaled_fps, of_item)
+        gyro, gyro_has = _lowpassed(20.0, sample_rate, gyro_item)
+        out.append((i, (est, est_has, gyro, gyro_has)))
+    return out
+
+
+def find_offsets_essential(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params, backend):
+    """``find_offsets`` (essential_matrix.rs:13-91) -> [(timestamp, offset, cost)]: one ``Backend.sync_gyro_search`` call for all ranges that reach the search."""
+    live = essential_ranges(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params)
+    if not live:
+        return []
+    results = backend.sync_gyro_search([r for _, r in live], sync_params.initial_offset, sync_params.search_size)
+    out = []
+    for (i, _), r in zip(live, results):
+        if not r.found:
+            continue
+        from_ts, to_ts = ranges[i]
+        middle_timestamp = (float(from_ts) + float(to_ts - from_ts) / 2.0) / 1000.0                      # :78
+        if abs(r.value - sync_params.initial_offset) < sync_params.search_size * 0.9:                    # :81
+            out.append((middle_timestamp, r.value, r.cost))
+    return out
+
+
+def median_offset(values):
+    """rs_sync.rs:27-35: the middle of the sorted offsets, the mean of the two middle ones for an even count"""
+    v = sorted(float(x) for x in values)
+    n = len(v)
+    return (v[n // 2 - 1] + v[n // 2]) / 2.0 if n % 2 == 0 else v[n // 2]
+
+
+def initial_offset_fast(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params, backend):
+    """rs_sync.rs:26-45 (``calc_initial_fast``): -> (initial_offset, search_size) the rs-sync solver starts from — the median of the gyro-match offsets and
+    3000 ms, or the inputs unchanged when nothing was found."""
+    if ranges and len(raw_imu) > 0:
+        offsets = find_offsets_essential(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params, backend)
+        if offsets:
+            return median_offset(o for _, o, _ in offsets), 3000.0
+    return sync_params.initial_offset, sync_params.search_size

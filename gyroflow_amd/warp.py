@@ -360,6 +360,60 @@ class Backend:
         self._check(self.lib.gfw_sync_visual_search(*args, C.cast(C.byref(res), C.c_void_p), coarse.ctypes.data if costs else None, fine.ctypes.data if costs else None, 0))
         return (res, coarse[:n_coarse], fine) if costs else res
 
+    @staticmethod
+    def _sync_gyro_ranges(ranges):
+        """[(est [n][4], est_has [n] or None, gyro [m][4], gyro_has [m] or None)] — rows (timestamp_ms, x, y, z) — -> the flat arrays gfw_sync_gyro_* take (kept alive by the caller)"""
+        def flat(col_data, col_has):
+            data = [np.asarray(r[col_data], dtype=np.float64).reshape(-1, 4) for r in ranges]
+            has = [np.ones(len(d), dtype=np.uint8) if r[col_has] is None else (np.asarray(r[col_has]).reshape(-1) != 0).astype(np.uint8) for r, d in zip(ranges, data)]
+            assert all(len(d) == len(h) for d, h in zip(data, has)), "one has byte per sample"
+            first = np.zeros(len(ranges) + 1, dtype=np.int32)
+            if ranges:
+                first[1:] = np.cumsum([len(d) for d in data])
+            cat = np.ascontiguousarray(np.concatenate(data)) if data else np.zeros((0, 4))
+            return first, cat, (np.ascontiguousarray(np.concatenate(has)) if has else np.zeros(0, dtype=np.uint8))
+        return flat(0, 1) + flat(2, 3)
+
+    def sync_gyro_costs(self, ranges, candidates, out_ptr=None):
+        """calculate_cost (find_offset/essential_matrix.rs:109-131) of caller-given candidate offsets for every range in one device call (gfw_sync_gyro_costs).
+
+        ``ranges``: [(est [n][4], est_has or None, gyro [m][4], gyro_has or None)], rows (timestamp_ms, x, y, z), the gyro slice cut to the range's window and
+        filtered; ``candidates``: one float64 array of offsets (ms) per range.  Returns one float64 cost array per range — or, with ``out_ptr`` (a device
+        pointer to as many doubles as there are candidates, range after range), None: in order on the stream."""
+        ef, e, eh, gf, g, gh = self._sync_gyro_ranges(ranges)
+        cands = [np.asarray(c, dtype=np.float64).reshape(-1) for c in candidates]
+        assert len(cands) == len(ranges)
+        cf = np.zeros(len(ranges) + 1, dtype=np.int32)
+        if cands:
+            cf[1:] = np.cumsum([len(c) for c in cands])
+        cand = np.ascontiguousarray(np.concatenate(cands)) if cands else np.zeros(0)
+        args = (self.ctx, ef.ctypes.data, e.ctypes.data, eh.ctypes.data, len(e), gf.ctypes.data, g.ctypes.data, gh.ctypes.data, len(g), len(ranges),
+                cf.ctypes.data, cand.ctypes.data, len(cand))
+        if out_ptr is not None:
+            self._check(self.lib.gfw_sync_gyro_costs(*args, out_ptr, 1))
+            return None
+        costs = np.zeros(max(len(cand), 1), dtype=np.float64)
+        self._check(self.lib.gfw_sync_gyro_costs(*args, costs.ctypes.data, 0))
+        return [costs[cf[r]:cf[r + 1]].copy() for r in range(len(ranges))]
+
+    def sync_gyro_search(self, ranges, initial_offset_ms=0.0, search_size_ms=5000.0, costs=False, result_ptr=None, coarse_ptr=None, fine_ptr=None):
+        """The two-stage search of essential_matrix.rs:52-75 for every range in one device call (gfw_sync_gyro_search); ``ranges`` as for sync_gyro_costs.
+        Returns [abi.SyncResult] — with ``costs`` also the coarse [n_ranges][n_coarse] and fine [n_ranges][200] float64 costs — or, with ``result_ptr`` (a
+        device pointer to n_ranges gfw_sync_result; ``coarse_ptr`` / ``fine_ptr``: None or device pointers), None: in order on the stream."""
+        ef, e, eh, gf, g, gh = self._sync_gyro_ranges(ranges)
+        n = len(ranges)
+        args = (self.ctx, ef.ctypes.data, e.ctypes.data, eh.ctypes.data, len(e), gf.ctypes.data, g.ctypes.data, gh.ctypes.data, len(g), n,
+                float(initial_offset_ms), float(search_size_ms))
+        if result_ptr is not None:
+            self._check(self.lib.gfw_sync_gyro_search(*args, result_ptr, coarse_ptr, fine_ptr, 1))
+            return None
+        res = (abi.SyncResult * max(n, 1))()
+        n_coarse = sync_gyro_coarse_count(search_size_ms)
+        coarse, fine = np.zeros(max(n * n_coarse, 1), dtype=np.float64), np.zeros((max(n, 1), abi.SYNC_FINE_CANDIDATES), dtype=np.float64)
+        self._check(self.lib.gfw_sync_gyro_search(*args, C.cast(res, C.c_void_p), coarse.ctypes.data if costs else None, fine.ctypes.data if costs else None, 0))
+        out = [res[i] for i in range(n)]
+        return (out, coarse[:n * n_coarse].reshape(n, n_coarse), fine[:n]) if costs else out
+
     def synchronize(self):
         self._check(self.lib.gfw_synchronize(self.ctx))
 
@@ -403,6 +457,27 @@ def sync_coarse_count(mode, search_size_ms, scaled_fps):
     v = float(search_size_ms) if int(mode) == 0 else (1000.0 / float(scaled_fps) if scaled_fps else float("inf"))
     steps = 0 if v != v or v <= 0.0 else int(min(v, 2.0 ** 62))
     return steps if int(mode) == 0 else 2 * steps
+
+
+def sync_gyro_coarse_count(search_size_ms):
+    """candidates of the gyro-match search's first stage: `search_size as usize * 2` (essential_matrix.rs:55) — the cast comes before the multiplication"""
+    v = float(search_size_ms)
+    return 0 if v != v or v <= 0.0 else int(min(v, 2.0 ** 62)) * 2
+
+
+def lowpass_gyro(freq, sample_rate, xyz, has=None):
+    """Lowpass::filter_gyro_forward_backward (filtering.rs:46-74) of a gyro series on the host (gfw_lowpass_gyro; no context, no GPU): -> (float64 [n][3], applied).
+    ``has``: None or [n], 0 = `gyro: None` (skipped, the filter state does not advance).  ``applied`` is False — the data returned as given — where the reference's
+    Coefficients::from_params fails (2 * freq > sample_rate) and the reference goes on unfiltered."""
+    v = np.array(xyz, dtype=np.float64).reshape(-1, 3)
+    v = np.ascontiguousarray(v)
+    h = None if has is None else np.ascontiguousarray((np.asarray(has).reshape(-1) != 0).astype(np.uint8))
+    assert h is None or len(h) == len(v)
+    lib = abi.load_library()
+    rc = lib.gfw_lowpass_gyro(float(freq), float(sample_rate), v.ctypes.data if len(v) else None, h.ctypes.data if h is not None and len(h) else None, len(v))
+    if rc < 0:
+        raise GfwError(rc, lib.gfw_last_error().decode())
+    return v, rc == 0
 
 
 def zoom_smooth(fov_minimal, adaptive_zoom_window, scaled_fps, method=0, trim_ranges=()):

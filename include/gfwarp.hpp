@@ -16,15 +16,19 @@
 //   gyroflow::{Luma8, Luma16, ...}         src/core/stabilization/pixel_formats.rs (PixelType implementors)
 //
 //   gyroflow::calculate_fovs               src/core/zooming/mod.rs:35-70    (the adaptive-zoom fov series: one device call + host smoothing)
+//   gyroflow::find_offsets_visual          src/core/synchronization/find_offset/visual_features.rs:10-147
+//   gyroflow::find_offsets_essential       src/core/synchronization/find_offset/essential_matrix.rs:13-91   (+ initial_offset_fast: rs_sync.rs:26-45)
 //
 // `FrameTransform::at_timestamp` itself (quaternions -> per-row matrices) is input here: the caller provides
 // `matrices`, or builds them on the device with gfw_build_matrices / gfw_build_matrices_batch.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
 #include <limits>
 #include <list>
+#include <map>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -374,6 +378,92 @@ inline std::vector<std::tuple<double, double, double>> find_offsets_visual(gfw_c
         if ((d < 0.0 ? -d : d) < sync_params.search_size * 0.9) final_offsets.emplace_back(middle_timestamp, r.value, r.cost);       // :137
     }
     return final_offsets;
+}
+
+// ---- synchronization/find_offset/essential_matrix.rs:13-91 `find_offsets` over gfw_sync_gyro_search: the gyro-match offset of every range (offset method 0), ALL
+// ranges in one device call; and rs_sync.rs:26-45, the fast initial offset rs-sync starts from.  `estimated_gyro`: the estimator's BTreeMap<i64 timestamp_us, TimeIMU>
+// (the angular rates pose estimation produced — the caller's input); `raw_imu`: gyro.raw_imu(); `duration_ms`: gyro.duration_ms.  The guards (:22, :26), the range cut
+// (`from_ts..to_ts`, the end excluded), the gyro window (:31-38), the max-angle skip (:40-44, on the unfiltered samples), the two 20 Hz low-pass calls
+// (gfw_lowpass_gyro; a refusal — 2 * 20 > rate — is ignored as the reference ignores it), the 90 % rule (:81) and the middle timestamp (:78) are applied here.
+struct TimeIMU { double timestamp_ms = 0.0; bool has_gyro = false; double gyro[3] = {0.0, 0.0, 0.0}; };
+struct EssentialRanges {                                                                            // what gfw_sync_gyro_search takes, and which range each entry is
+    std::vector<size_t> index;
+    std::vector<int32_t> est_first{0}, gyro_first{0};
+    std::vector<double> est, gyro;                                                                  // [][4] (timestamp_ms, x, y, z)
+    std::vector<uint8_t> est_has, gyro_has;
+};
+namespace detail {
+inline void essential_append(const std::vector<const TimeIMU *> &items, double rate, std::vector<int32_t> &first, std::vector<double> &rows, std::vector<uint8_t> &has) {
+    std::vector<double> xyz(items.size() * 3);
+    std::vector<uint8_t> h(items.size());
+    for (size_t i = 0; i < items.size(); ++i) { h[i] = items[i]->has_gyro ? 1 : 0; for (int a = 0; a < 3; ++a) xyz[i * 3 + a] = items[i]->has_gyro ? items[i]->gyro[a] : 0.0; }
+    const int rc = gfw_lowpass_gyro(20.0, rate, xyz.data(), h.data(), (int)items.size());           // `let _ =`: GFW_FILTER_NOT_APPLIED goes on unfiltered
+    if (rc < 0) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+    for (size_t i = 0; i < items.size(); ++i) {
+        rows.push_back(items[i]->timestamp_ms); rows.push_back(xyz[i * 3]); rows.push_back(xyz[i * 3 + 1]); rows.push_back(xyz[i * 3 + 2]);
+        has.push_back(h[i]);
+    }
+    first.push_back((int32_t)(rows.size() / 4));
+}
+}  // namespace detail
+inline EssentialRanges essential_ranges(const std::map<int64_t, TimeIMU> &estimated_gyro, const std::vector<TimeIMU> &raw_imu, double duration_ms, double scaled_fps,
+                                        const std::vector<std::pair<int64_t, int64_t>> &ranges, const SyncParams &sync_params) {
+    EssentialRanges out;
+    if (estimated_gyro.empty() || !(duration_ms > 0.0) || raw_imu.empty()) return out;              // :22
+    for (size_t r = 0; r < ranges.size(); ++r) {
+        if (ranges[r].second <= ranges[r].first) continue;                                          // :26
+        std::vector<const TimeIMU *> of_item, gyro_item;
+        for (auto it = estimated_gyro.lower_bound(ranges[r].first); it != estimated_gyro.end() && it->first < ranges[r].second; ++it) of_item.push_back(&it->second);
+        if (of_item.empty()) continue;
+        const double lo = of_item.front()->timestamp_ms - sync_params.search_size, hi = of_item.back()->timestamp_ms + sync_params.search_size;
+        for (const TimeIMU &x : raw_imu) { const double ts = x.timestamp_ms + sync_params.initial_offset; if (ts >= lo && ts <= hi) gyro_item.push_back(&x); }
+        double max_angle = 0.0;                                                                     // get_max_angle (:93-103)
+        for (const TimeIMU *x : of_item) if (x->has_gyro) for (int a = 0; a < 3; ++a) { const double v = x->gyro[a] < 0.0 ? -x->gyro[a] : x->gyro[a]; if (v > max_angle) max_angle = v; }
+        if (max_angle < 3.0) continue;
+        const double sample_rate = (double)raw_imu.size() / (duration_ms / 1000.0);
+        detail::essential_append(of_item, scaled_fps, out.est_first, out.est, out.est_has);
+        detail::essential_append(gyro_item, sample_rate, out.gyro_first, out.gyro, out.gyro_has);
+        out.index.push_back(r);
+    }
+    return out;
+}
+inline std::vector<std::tuple<double, double, double>> find_offsets_essential(gfw_ctx *ctx, const std::map<int64_t, TimeIMU> &estimated_gyro, const std::vector<TimeIMU> &raw_imu,
+                                                                              double duration_ms, double scaled_fps, const std::vector<std::pair<int64_t, int64_t>> &ranges,
+                                                                              const SyncParams &sync_params) {
+    std::vector<std::tuple<double, double, double>> offsets;
+    const EssentialRanges live = essential_ranges(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params);
+    if (live.index.empty()) return offsets;
+    std::vector<gfw_sync_result> results(live.index.size());
+    std::memset(results.data(), 0, sizeof(gfw_sync_result) * results.size());
+    const int rc = gfw_sync_gyro_search(ctx, live.est_first.data(), live.est.data(), live.est_has.data(), (int)live.est_has.size(), live.gyro_first.data(), live.gyro.data(),
+                                        live.gyro_has.data(), (int)live.gyro_has.size(), (int)live.index.size(), sync_params.initial_offset, sync_params.search_size,
+                                        results.data(), nullptr, nullptr, 0);
+    if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+    for (size_t k = 0; k < live.index.size(); ++k) {
+        if (!results[k].found) continue;
+        const auto &range = ranges[live.index[k]];
+        const double middle_timestamp = ((double)range.first + (double)(range.second - range.first) / 2.0) / 1000.0;      // :78
+        const double d = results[k].value - sync_params.initial_offset;
+        if ((d < 0.0 ? -d : d) < sync_params.search_size * 0.9) offsets.emplace_back(middle_timestamp, results[k].value, results[k].cost);       // :81
+    }
+    return offsets;
+}
+inline double median_offset(std::vector<double> v) {                                                // rs_sync.rs:27-35
+    std::stable_sort(v.begin(), v.end(), [](double a, double b) { return a < b; });
+    const size_t len = v.size();
+    return len % 2 == 0 ? (v[len / 2 - 1] + v[len / 2]) / 2.0 : v[len / 2];
+}
+// -> the (initial_offset, search_size) rs-sync starts from: the median of the gyro-match offsets and 3000 ms, or the inputs unchanged when nothing was found
+inline SyncParams initial_offset_fast(gfw_ctx *ctx, const std::map<int64_t, TimeIMU> &estimated_gyro, const std::vector<TimeIMU> &raw_imu, double duration_ms, double scaled_fps,
+                                      const std::vector<std::pair<int64_t, int64_t>> &ranges, SyncParams sync_params) {
+    if (ranges.empty() || raw_imu.empty()) return sync_params;
+    const auto offsets = find_offsets_essential(ctx, estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params);
+    if (offsets.empty()) return sync_params;
+    std::vector<double> v;
+    for (const auto &o : offsets) v.push_back(std::get<1>(o));
+    sync_params.initial_offset = median_offset(v);
+    sync_params.search_size = 3000.0;
+    return sync_params;
 }
 
 }  // namespace gyroflow
