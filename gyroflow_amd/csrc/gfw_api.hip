@@ -25,6 +25,9 @@
 #include "gfw_zoom.h"
 #include "gfw_sync.h"
 #include "gfw_sync_gyro.h"
+#include "gfw_matrices_host.h"
+#include "gfw_zoom_host.h"
+#include "gfw_sync_host.h"
 #include "gfw_sync_gyro_host.h"
 #include "gfw_jit.h"
 #include <stdlib.h>
@@ -97,14 +100,16 @@ struct gfw_ctx {
     double p1_slope = 0.0, p1_kappa = 0.0;         // max |ds/drho| over the table's range; roundoff amplification of the exact path's theta_d/r (section 2c)
     struct P1Radial *p1_radial = nullptr;          // the same for the radial models of round 6 (GoPro: gfw_api_certificate.inc); table in d_p1_table as well
     double p1_u1 = 0.0, p1_u2 = 0.0, p1_t32 = 0.0; // max sqrt(rho) |s'|, rho |s'|, rho^1.5 |s''| over the table's range: the curvature of the first pass's value across a lattice cell (gfw_frame.hip)
-    DevBuf d_pts_in, d_pts_out, d_pts_rot, d_pts_shift, d_pts_mesh;   // gfw_undistort_points staging
+    DevBuf d_pts_in, d_pts_rot, d_pts_shift, d_pts_mesh;   // gfw_undistort_points staging
+    // the results of a call with HOST outputs, of whichever entry point (CallOutputs, gfw_hostmem.h): such a call synchronises before it returns, so one buffer serves all
+    DevBuf d_out;
     DevBuf d_tracks;                              // quaternion tracks
-    // gfw_zoom_fovs: frame descriptors (+ caller-given rotations) staged through pinned memory, results for host outputs
+    // gfw_zoom_fovs: frame descriptors (+ caller-given rotations) staged through pinned memory
     // (one block, free again behind its COPY: the device side is ordered by the context's stream, and a second asynchronous call does not wait for the first search)
-    StagingRing<1> zoom_ring; DevBuf d_zoom_out;
-    // gfw_sync_visual_*: pairs, points and candidates staged the same way; rays / partial sums / fine candidates; results for host outputs
-    StagingRing<1> sync_ring; DevBuf d_sync_work, d_sync_out;
-    // gfw_sync_gyro_*: ranges, estimated samples, gyro keys and values, candidates staged the same way (work space and host-output space: the visual search's)
+    StagingRing<1> zoom_ring;
+    // gfw_sync_visual_*: pairs, points and candidates staged the same way; rays / partial sums / fine candidates
+    StagingRing<1> sync_ring; DevBuf d_sync_work;
+    // gfw_sync_gyro_*: ranges, estimated samples, gyro keys and values, candidates staged the same way (work space: the visual search's)
     static constexpr int kGyroSlots = 2;
     StagingRing<kGyroSlots> gyro_ring;
     // context-owned per-row tables built on the device (gfw_build_matrices): a small ring, built on copy_stream so that
@@ -800,6 +805,15 @@ static bool nothing_pending(const gfw_ctx *c) {
 }
 // Entry points other than gfw_undistort_image keep their place in the order of calls: whatever is being held leaves first (no lock when nothing is)
 int flush_if_pending(gfw_ctx *c) { return (!c || nothing_pending(c)) ? GFW_OK : gfw_flush(c); }
+// What every entry of the rows next to the warp does between validating its arguments and touching the device: the planes held for a frame leave first (they were
+// submitted earlier), then the calling thread's device is the context's
+static int enter_device(gfw_ctx *c) {
+    const int rc = flush_if_pending(c);
+    if (rc != GFW_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device), GFW_ERR_HIP);
+    return GFW_OK;
+}
+#define API_TRY(expr) do { const int rc_ = (expr); if (rc_ != GFW_OK) return rc_; } while (0)
 static int check_pixel_types(int nplanes, const int *pixel_types) {
     for (int i = 0; i < nplanes; ++i)
         if (pixel_types[i] < 0 || pixel_types[i] >= GFW_PIX_COUNT) { set_error("plane %d: unknown pixel type %d", i, pixel_types[i]); return GFW_ERR_INVALID_ARGUMENT; }
@@ -950,4 +964,7 @@ int gfw_undistort_clip_params(gfw_ctx *c, int n_frames, int nplanes, const gfw_b
 }  // extern "C"
 
 #include "gfw_api_testhooks.inc"
-#include "gfw_api_adjacent.inc"
+#include "gfw_api_matrices.inc"
+#include "gfw_api_points.inc"
+#include "gfw_api_zoom.inc"
+#include "gfw_api_sync.inc"

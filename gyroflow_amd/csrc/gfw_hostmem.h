@@ -2,7 +2,9 @@
 // None of them calls into HIP for a handle that was never created: a context that never met a device (gfw_debug_jit_key*) is destroyed without one.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <assert.h>
 #include <stddef.h>
+#include "gfw_layout.h"
 
 // Device (hipMalloc) or pinned host (hipHostMalloc) memory that grows on demand; growth does not preserve contents.  Move-only.
 template <bool PINNED>
@@ -61,6 +63,38 @@ struct StagingRing {
         if (e == hipSuccess) e = s.h.ensure(bytes);
         if (e == hipSuccess) e = s.d.ensure(bytes);
         *out = &s;
+        return e;
+    }
+};
+
+// An acquired slot as the block a call stages (BlockLayout, gfw_layout.h): the packers fill it at (h, d), one copy takes `total` bytes up.  Where free_again is
+// recorded is the call's own decision (behind the copy, or behind the last kernel that reads the device side): see StagingRing::acquire.
+struct StagedBlock {
+    StagingSlot *slot = nullptr;
+    char *h() const { return (char *)slot->h.ptr; }
+    const char *d() const { return (const char *)slot->d.ptr; }
+    hipError_t upload(size_t total, hipStream_t s) const { return hipMemcpyAsync(slot->d.ptr, slot->h.ptr, total, hipMemcpyHostToDevice, s); }
+    hipError_t free_again(hipStream_t s) const { return slot->free_again.record(s); }
+};
+
+// The outputs of one call.  add() every output (a NULL one stays NULL), reserve(), then dev(i) is what the kernels write: the caller's pointer when the outputs are
+// device memory, otherwise a slice of `buf`, which finish() copies to the caller's host memory.  ONE buffer serves every entry point of a context: a call with host
+// outputs synchronises before it returns, so no earlier call's results are still in the buffer when the next one takes it (or lets it grow, which frees it).
+struct CallOutputs {
+    struct Part { void *caller; size_t at, bytes; };
+    DevBuf &buf; const bool on_device;
+    static constexpr int kMaxParts = 4;              // the most any call adds: the visual sync search (result, coarse costs, fine costs, mapped points)
+    Part parts[kMaxParts]; int n = 0; BlockLayout layout;
+    CallOutputs(DevBuf &b, int out_on_device) : buf(b), on_device(out_on_device != 0) {}
+    int add(void *caller, size_t bytes) { assert(n < kMaxParts); parts[n] = Part{caller, caller ? layout.add(bytes) : 0, bytes}; return n++; }
+    hipError_t reserve() { return on_device ? hipSuccess : buf.ensure(layout.total); }
+    void *dev(int i) const { return !parts[i].caller || on_device ? parts[i].caller : (char *)buf.ptr + parts[i].at; }
+    // the copies back, then the one rule of when a call waits: a synchronous context, or results the caller reads from host memory on return
+    hipError_t finish(hipStream_t s, bool synchronous) const {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < n && !on_device && e == hipSuccess; ++i)
+            if (parts[i].caller && parts[i].bytes) e = hipMemcpyAsync(parts[i].caller, dev(i), parts[i].bytes, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && (synchronous || !on_device)) e = hipStreamSynchronize(s);
         return e;
     }
 };

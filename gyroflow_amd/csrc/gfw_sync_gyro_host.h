@@ -5,8 +5,20 @@
 #include <algorithm>
 #include <utility>
 #include <vector>
+#include "gfw_layout.h"
 
-// Host: what a call stages, filled into the caller's (pinned) arrays.  A series is the ABI's: range r owns first[r] .. first[r + 1] - 1 of data [][4] f64 (timestamp_ms, x, y, z)
+// The staged block: [n_ranges] GfwGyroRange, the estimated samples [][4] f64 and their has bytes, the gyro keys and values [][4] f64, the candidates.
+struct GfwGyroLayout { size_t o_ranges, o_est, o_has, o_keys, o_val, o_cand, total; };
+inline GfwGyroLayout gfw_gyro_layout(int n_ranges, size_t tot_est, size_t tot_gyro, size_t tot_cand) {
+    BlockLayout L;
+    GfwGyroLayout G;
+    G.o_ranges = L.add(sizeof(GfwGyroRange) * (size_t)n_ranges); G.o_est = L.add(32 * tot_est); G.o_has = L.add(tot_est);
+    G.o_keys = L.add(8 * tot_gyro); G.o_val = L.add(32 * tot_gyro); G.o_cand = L.add(8 * tot_cand);
+    G.total = L.total;
+    return G;
+}
+
+// Host: what a call stages, filled into the caller's arrays (gfw_gyro_fill below: the parts of ONE block).  A series is the ABI's: range r owns first[r] .. first[r + 1] - 1 of data [][4] f64 (timestamp_ms, x, y, z)
 // and of has (nullptr = all present).  Each range's gyro slice becomes the BTreeMap<usize, TimeIMU> of :50 flattened: keys ascending, a later sample with the same key
 // replacing an earlier one — the slice need not be ascending.  Candidates: `n_coarse` of them per range made by :59 (cand_first nullptr), or the caller's.
 // The arrays hold what the firsts span (keys / values: at most that) and are filled from 0 whatever first[0] is: ranges[r] holds offsets into the STAGED arrays, so
@@ -54,4 +66,12 @@ inline int gfw_gyro_stage(const GfwGyroSeries &est, const GfwGyroSeries &gyro, i
         if (G.cand_n > max_cand) max_cand = G.cand_n;
     }
     return max_cand;
+}
+// The same into the block at (h, d) — the layout above — with the argument block's input pointers.
+inline int gfw_gyro_fill(const GfwGyroLayout &L, const GfwGyroSeries &est, const GfwGyroSeries &gyro, int n_ranges, const int32_t *cand_first, const double *candidates,
+                         size_t n_coarse, double initial_offset_ms, double search_size_ms, char *h, const char *d, GfwGyroArgs &A) {
+    A.ranges = (const GfwGyroRange *)(d + L.o_ranges); A.est = (const double *)(d + L.o_est); A.est_has = (const uint8_t *)(d + L.o_has);
+    A.keys = (const unsigned long long *)(d + L.o_keys); A.gyro = (const double *)(d + L.o_val); A.candidates = (const double *)(d + L.o_cand);
+    return gfw_gyro_stage(est, gyro, n_ranges, cand_first, candidates, n_coarse, initial_offset_ms, search_size_ms, (GfwGyroRange *)(h + L.o_ranges), (double *)(h + L.o_est),
+                          (uint8_t *)(h + L.o_has), (unsigned long long *)(h + L.o_keys), (double *)(h + L.o_val), (double *)(h + L.o_cand));
 }

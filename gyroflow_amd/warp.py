@@ -77,6 +77,37 @@ def frame_stab_table(stabs):
     return table, keep
 
 
+def frame_mesh_table(meshes):
+    """[float64 mesh or None per frame] -> (ctypes arrays of pointers and lengths as gfw_zoom_fovs_stab takes them, NULL / 0 where None; what they point into).
+    Frames that name the SAME array object share one conversion, hence one pointer.  Public like frame_stab_table beside it: the interpreter tier of the tests
+    hands the entry point's own arguments to the host-interpreted kernels."""
+    n = max(len(meshes), 1)
+    mp, lp, held = (C.c_void_p * n)(), (C.c_size_t * n)(), {}
+    for k, m in enumerate(meshes):
+        if m is None or len(m) == 0:
+            continue
+        if id(m) not in held:
+            held[id(m)] = np.ascontiguousarray(m, dtype=np.float64)
+        mp[k], lp[k] = held[id(m)].ctypes.data, held[id(m)].size
+    return mp, lp, held
+
+
+def _matrix_arg(matrices, matrix_count=None):
+    """a frame's rows as numpy [rows][14] f32, or a device pointer (GFW_OPT_MATRICES_ON_DEVICE) with its row count -> (pointer, rows, the array to keep alive)"""
+    if isinstance(matrices, np.ndarray):
+        m = np.ascontiguousarray(matrices, dtype=np.float32)
+        return m.ctypes.data, m.shape[0], m
+    return matrices, matrix_count, None
+
+
+def _mesh_arg(mesh, dtype=np.float32):
+    """None, an empty or a lens mesh -> (pointer or None, values, the array to keep alive)"""
+    if mesh is None or not len(mesh):
+        return None, 0, None
+    m = np.ascontiguousarray(mesh, dtype=dtype)
+    return m.ctypes.data, m.size, m
+
+
 def last_backend():
     return _last_backend
 
@@ -220,10 +251,7 @@ class Backend:
         array started from: the 32-bit pattern ``fill`` (default 0, what parallel_exr leaves)."""
         m = np.ascontiguousarray(matrices, dtype=np.float32)
         coords = np.full((height, width, 2), fill or 0, dtype=np.uint32).view(np.float32)
-        meshp, meshn = None, 0
-        if mesh is not None and len(mesh):
-            mesh = np.ascontiguousarray(mesh, dtype=np.float32)
-            meshp, meshn = mesh.ctypes.data, mesh.size
+        meshp, meshn, _mesh = _mesh_arg(mesh)
         self._check(self.lib.gfw_stmap_undistort(self.ctx, C.byref(params), m.ctypes.data, m.shape[0], meshp, meshn, width, height, coords.ctypes.data, 0))
         return coords
 
@@ -246,10 +274,7 @@ class Backend:
             shifts = np.ascontiguousarray(shifts, dtype=np.float32).reshape(-1, 5)
             assert shifts.shape[0] == rot.shape[0]
             sp = shifts.ctypes.data
-        meshp, meshn = None, 0
-        if mesh is not None and len(mesh):
-            mesh = np.ascontiguousarray(mesh, dtype=np.float64)
-            meshp, meshn = mesh.ctypes.data, mesh.size
+        meshp, meshn, _mesh = _mesh_arg(mesh, np.float64)
         self._check(self.lib.gfw_undistort_points(self.ctx, C.byref(params), pp, n, gw, rot.ctypes.data, rot.shape[0], sp,
                                                   index_mode, meshp, meshn, out.ctypes.data, 0))
         return out
@@ -296,13 +321,7 @@ class Backend:
         mp = lp = None
         if meshes is not None:
             assert len(meshes) == n
-            mp, lp, held = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))(), {}
-            for k, m in enumerate(meshes):
-                if m is None or len(m) == 0:
-                    continue
-                if id(m) not in held:
-                    held[id(m)] = np.ascontiguousarray(m, dtype=np.float64)
-                mp[k], lp[k] = held[id(m)].ctypes.data, held[id(m)].size
+            mp, lp, _held = frame_mesh_table(meshes)
         if out_ptr is not None:
             self._check(self.lib.gfw_zoom_fovs_stab(self.ctx, C.byref(params), C.byref(search), C.cast(arr, C.c_void_p), n, rp, sp, mp, lp, out_ptr, debug_ptr, 1))
             return None
@@ -423,15 +442,8 @@ class Backend:
 
     def undistort_image(self, buffers, params, matrices, mesh=None, matrix_count=None):
         """One plane (OclWrapper::undistort_image).  ``matrices``: numpy [rows][14] f32, or a device pointer int."""
-        if isinstance(matrices, np.ndarray):
-            m = np.ascontiguousarray(matrices, dtype=np.float32)
-            mp, mc = m.ctypes.data, m.shape[0]
-        else:
-            mp, mc = matrices, matrix_count
-        meshp, meshn = None, 0
-        if mesh is not None and len(mesh):
-            mesh = np.ascontiguousarray(mesh, dtype=np.float32)
-            meshp, meshn = mesh.ctypes.data, mesh.size
+        mp, mc, _m = _matrix_arg(matrices, matrix_count)
+        meshp, meshn, _mesh = _mesh_arg(mesh)
         self._check(self.lib.gfw_undistort_image(self.ctx, C.byref(buffers), C.byref(params), mp, mc, None, 0, meshp, meshn))
 
     def undistort_frame(self, planes, params, pixel_types, matrices, mesh=None, matrix_count=None):
@@ -440,15 +452,8 @@ class Backend:
         barr = (abi.Buffers * n)(*planes)
         parr = (abi.KernelParams * n)(*params)
         tarr = (C.c_int * n)(*[abi.PIXEL_TYPES[t][0] if isinstance(t, str) else t for t in pixel_types])
-        if isinstance(matrices, np.ndarray):
-            m = np.ascontiguousarray(matrices, dtype=np.float32)
-            mp, mc = m.ctypes.data, m.shape[0]
-        else:
-            mp, mc = matrices, matrix_count
-        meshp, meshn = None, 0
-        if mesh is not None and len(mesh):
-            mesh = np.ascontiguousarray(mesh, dtype=np.float32)
-            meshp, meshn = mesh.ctypes.data, mesh.size
+        mp, mc, _m = _matrix_arg(matrices, matrix_count)
+        meshp, meshn, _mesh = _mesh_arg(mesh)
         self._check(self.lib.gfw_undistort_frame(self.ctx, n, barr, parr, tarr, mp, mc, meshp, meshn))
 
 
@@ -514,11 +519,7 @@ class FrameCall:
         self.barr = (abi.Buffers * n)(*planes)
         self.parr = (abi.KernelParams * n)(*params)
         self.tarr = (C.c_int * n)(*[abi.PIXEL_TYPES[t][0] if isinstance(t, str) else t for t in pixel_types])
-        if isinstance(matrices, np.ndarray):
-            self.m = np.ascontiguousarray(matrices, dtype=np.float32)
-            self.mp, self.mc = self.m.ctypes.data, self.m.shape[0]
-        else:                                       # device pointer (GFW_OPT_MATRICES_ON_DEVICE)
-            self.mp, self.mc = matrices, matrix_count
+        self.mp, self.mc, self.m = _matrix_arg(matrices, matrix_count)
         self.fn = backend.lib.gfw_undistort_frame
 
     def __call__(self):
@@ -532,11 +533,7 @@ class PlaneCalls:
     (one process_pixels per plane, each plane its own Stabilization / backend object, src/rendering/mod.rs:494-545)."""
 
     def __init__(self, backends, planes, params, matrices, matrix_count=None):
-        if isinstance(matrices, np.ndarray):
-            self.m = np.ascontiguousarray(matrices, dtype=np.float32)
-            mp, mc = self.m.ctypes.data, self.m.shape[0]
-        else:
-            mp, mc = matrices, matrix_count
+        mp, mc, self.m = _matrix_arg(matrices, matrix_count)
         self.keep = [(abi.Buffers.from_buffer_copy(b), abi.KernelParams.from_buffer_copy(p)) for b, p in zip(planes, params)]
         for i, (_, p) in enumerate(self.keep):
             p.plane_index = i
@@ -559,17 +556,10 @@ class ClipCall:
         self.barr = (abi.Buffers * (nf * n))(*[b for fr in frames for b in fr])
         self.parr = (abi.KernelParams * n)(*params)
         self.tarr = (C.c_int * n)(*[abi.PIXEL_TYPES[t][0] if isinstance(t, str) else t for t in pixel_types])
-        self.keep, ptrs = [], []
-        for m in matrices:
-            if isinstance(m, np.ndarray):
-                m = np.ascontiguousarray(m, dtype=np.float32)
-                self.keep.append(m)
-                ptrs.append(m.ctypes.data)
-                matrix_count = m.shape[0]
-            else:
-                ptrs.append(m)
-        self.marr = (C.c_void_p * nf)(*ptrs)
-        self.mc = matrix_count
+        args = [_matrix_arg(m, matrix_count) for m in matrices]
+        self.keep = [a[2] for a in args if a[2] is not None]
+        self.marr = (C.c_void_p * nf)(*[a[0] for a in args])
+        self.mc = next((a[1] for a in reversed(args) if a[2] is not None), matrix_count)
         self.fn = backend.lib.gfw_undistort_clip
 
     def __call__(self):

@@ -74,8 +74,20 @@ def kernel_source(top="gfw_frame.hip", n_asm=13):
     return src
 
 
+def _host_headers(text, seen):
+    """the texts of the product's host-only headers that `text` (the files under tests/emu/) includes, and of what those include from beside themselves"""
+    out = []
+    for name in re.findall(r'#include "(?:\.\./\.\./gyroflow_amd/csrc/)?(gfw_\w+\.h)"', text):
+        if name not in seen:
+            seen.add(name)
+            t = open(os.path.join(G.CSRC, name)).read()
+            out += [t] + _host_headers(t, seen)
+    return out
+
+
 def build(defs, header, top="gfw_frame.hip", n_asm=13, driver="emu_driver.inc", extra_flags=("-DGFW_JIT=1", "-DGFW_BAKE=1"), opt="-O1"):
-    """-> path of the host library for these template arguments (+ bake header) (cached under build/emu/ by content)."""
+    """-> path of the host library for these template arguments (+ bake header) (cached under build/emu/ by content: the kernel source, the files under
+    tests/emu/, and the host-only headers of the product that the drivers include — the entry points' own packers)."""
     if not CXX.endswith("clang++"):
         import pytest
         pytest.skip("the host interpreter is built with the ROCm clang++ (half-precision and vector extensions of the kernel headers); not found")
@@ -83,7 +95,8 @@ def build(defs, header, top="gfw_frame.hip", n_asm=13, driver="emu_driver.inc", 
     text = ('#include "emu_prelude.h"\n' + header + "\n" + kernel_source(top, n_asm) + '\n#include "%s"\n' % driver)
     flags = ["-std=c++17", opt, "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wno-everything", "-I" + EMU] + list(extra_flags) + \
             ["-D%s=%s" % kv for kv in sorted(defs.items())]
-    key = hashlib.sha256((text + " ".join(flags) + "".join(open(os.path.join(EMU, f)).read() for f in sorted(os.listdir(EMU)))).encode()).hexdigest()[:20]
+    emu = "".join(open(os.path.join(EMU, f)).read() for f in sorted(os.listdir(EMU)))
+    key = hashlib.sha256((text + " ".join(flags) + emu + "".join(_host_headers(emu, set()))).encode()).hexdigest()[:20]
     so = os.path.join(OUT, "emu_%s.so" % key)
     if not os.path.exists(so):
         # names of this process's own: two pytest-xdist workers may build the same key at once, and a source file rewritten under a running compiler ends it with SIGBUS

@@ -17,7 +17,8 @@ def lib():
     if _lib is None:
         L = C.CDLL(_emu.build({}, "", top="gfw_sync.hip", n_asm=2, driver="emu_sync_driver.inc", extra_flags=()))
         vp, i32 = C.c_void_p, C.c_int
-        L.gfw_emu_sync.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, C.c_double, vp, C.c_double, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        f64 = C.c_double
+        L.gfw_emu_sync.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, f64, vp, vp, vp, vp, vp, i32, vp, i32, i32, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp]
         L.gfw_emu_sync_table.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp]
         L.gfw_emu_sync_point_split.argtypes = [vp, vp, vp, vp, i32, vp, vp]
         L.gfw_emu_sync_point_split.restype = None
@@ -25,20 +26,18 @@ def lib():
     return _lib
 
 
-def _run(params, model, digital, search, pairs, candidates, mode, tracks, offsets, duration_ms, want_mapped):
+def _run(params, model, digital, search, pairs, candidates, mode, tracks, offsets, duration_ms, want_mapped, how=(0.0, 0.0, 0.0, 30.0)):
+    """candidates: [n][2] (mode < 0), or the count of coarse candidates the search of `how` = (initial_offset_ms, search_size_ms, frame_readout_time_ms, scaled_fps) makes"""
     com = _emu.common_for(_emu._Lenses(model, digital), params)
     ts, first, pa, pb = warp.Backend._sync_pairs(pairs)
     total, n_pairs = int(first[-1]), len(pairs)
-    pts = np.ascontiguousarray(np.concatenate([pa, pb]), dtype=np.float32)
-    cand = np.ascontiguousarray(candidates, dtype=np.float64).reshape(-1, 2)
-    n = cand.shape[0]
+    cand = np.ascontiguousarray(candidates, dtype=np.float64).reshape(-1, 2) if mode < 0 else None
+    n = cand.shape[0] if mode < 0 else int(candidates)
     (ot, oq), (st, sq) = tracks
     ot, st, oq, sq = (np.ascontiguousarray(ot, np.int64), np.ascontiguousarray(st, np.int64), np.ascontiguousarray(oq, np.float64), np.ascontiguousarray(sq, np.float64))
     use = bool(search.use_sync_offsets) and offsets is not None
     ft = np.ascontiguousarray(offsets[0], np.int64) if use else np.zeros(0, np.int64)
     fv = np.ascontiguousarray(offsets[1], np.float64) if use else np.zeros(0)
-    nk = np.array(list(search.new_k), dtype=np.float64)
-    what = np.array([search.width, search.height, search.horizontal_readout, n_pairs, total], dtype=np.int32)
     rays = np.zeros((max(2 * total, 1), 4), dtype=np.float32)
     partial = np.zeros(max(n, FINE) * max(n_pairs, 1), dtype=np.uint64)
     fine, costs, fine_costs = np.zeros((FINE, 2)), np.full(max(n, 1), -7.0), np.full(FINE, -7.0)
@@ -46,7 +45,7 @@ def _run(params, model, digital, search, pairs, candidates, mode, tracks, offset
     res = abi.SyncResult()
     p = lambda a: a.ctypes.data if a is not None and a.size else None
     rc = lib().gfw_emu_sync(C.cast(C.byref(params), C.c_void_p), C.cast(C.byref(com), C.c_void_p), p(ot), p(oq), len(ot), p(st), p(sq), len(st), p(ft), p(fv), len(ft),
-                            float(duration_ms), nk.ctypes.data, float(search.video_rotation_deg), what.ctypes.data, p(ts), first.ctypes.data, p(pts), p(cand), n, mode,
+                            float(duration_ms), C.cast(C.byref(search), C.c_void_p), p(ts), first.ctypes.data, p(pa), p(pb), n_pairs, p(cand), n, mode, *[float(v) for v in how],
                             rays.ctypes.data, partial.ctypes.data, fine.ctypes.data, costs.ctypes.data, p(mapped), C.cast(C.byref(res), C.c_void_p) if mode >= 0 else None,
                             fine_costs.ctypes.data)
     assert rc == 0, "gfw_emu_sync -> %d" % rc
@@ -62,13 +61,10 @@ def sync_visual_costs(params, model, digital, search, pairs, candidates, tracks,
 def sync_visual_search(params, model, digital, search, pairs, mode, tracks, initial_offset_ms=0.0, search_size_ms=0.0, frame_readout_time_ms=0.0, scaled_fps=30.0,
                        offsets=None, duration_ms=1.0):
     """gfw_sync_visual_search through the host-interpreted kernels -> (abi.SyncResult, coarse costs [n_coarse], fine costs [200]); the coarse candidates are made as
-    the entry point makes them"""
+    the entry point makes them, by its own code"""
     n = warp.sync_coarse_count(mode, search_size_ms, scaled_fps)
-    if mode == 0:
-        cand = [(initial_offset_ms + (-(search_size_ms / 2.0) + float(i)), frame_readout_time_ms) for i in range(n)]
-    else:
-        cand = [(0.0, float(i - n // 2)) for i in range(n)]
-    costs, _, res, fine_costs, _ = _run(params, model, digital, search, pairs, np.array(cand, dtype=np.float64).reshape(-1, 2), mode, tracks, offsets, duration_ms, False)
+    costs, _, res, fine_costs, _ = _run(params, model, digital, search, pairs, n, mode, tracks, offsets, duration_ms, False,
+                                        (initial_offset_ms, search_size_ms, frame_readout_time_ms, scaled_fps))
     return res, costs, fine_costs
 
 

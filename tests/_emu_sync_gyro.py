@@ -1,9 +1,7 @@
 """TEST INFRASTRUCTURE: the gyro-match search's kernel SOURCE (gyroflow_amd/csrc/gfw_sync_gyro.hip) and the entry points' host staging (gfw_gyro_stage,
-gfw_sync_gyro.h) interpreted on the host, the way tests/_emu_sync.py runs gfw_sync.hip: tests/emu/emu_sync_gyro_driver.inc behind the unedited source, the lanes of
+gfw_sync_gyro_host.h) interpreted on the host, the way tests/_emu_sync.py runs gfw_sync.hip: tests/emu/emu_sync_gyro_driver.inc behind the unedited source, the lanes of
 a workgroup as cooperative fibers that rendezvous at __syncthreads.  Not a product path."""
 import ctypes as C
-import hashlib
-import os
 
 import numpy as np
 
@@ -18,9 +16,7 @@ FINE = abi.SYNC_FINE_CANDIDATES
 def lib():
     global _lib
     if _lib is None:
-        host = open(os.path.join(_emu.G.CSRC, "gfw_sync_gyro_host.h")).read()          # the driver includes it: its text is part of the build's identity
-        L = C.CDLL(_emu.build({}, "// gfw_sync_gyro_host.h %s\n" % hashlib.sha256(host.encode()).hexdigest()[:16], top="gfw_sync_gyro.hip", n_asm=0,
-                              driver="emu_sync_gyro_driver.inc", extra_flags=()))
+        L = C.CDLL(_emu.build({}, "", top="gfw_sync_gyro.hip", n_asm=0, driver="emu_sync_gyro_driver.inc", extra_flags=()))
         vp, i32 = C.c_void_p, C.c_int
         L.gfw_emu_sync_gyro.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp]
         _lib = L

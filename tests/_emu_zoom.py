@@ -16,7 +16,7 @@ def lib():
     if _lib is None:
         L = C.CDLL(_emu.build({}, "", top="gfw_zoom.hip", n_asm=2, driver="emu_zoom_driver.inc", extra_flags=()))
         vp, i32 = C.c_void_p, C.c_int
-        L.gfw_emu_zoom.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, C.c_double, vp, C.c_float, vp, i32, vp, vp, vp]
+        L.gfw_emu_zoom.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, C.c_double, vp, vp, i32, vp, vp, vp]
         L.gfw_emu_zoom_table.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, vp]
         _lib = L
     return _lib
@@ -42,12 +42,11 @@ def zoom_fovs(params, model, digital, search, frames, rotations=None, tracks=Non
         targs += [arr(offsets[0], np.int64), arr(offsets[1], np.float64), len(offsets[0])]
     else:
         targs += [None, None, 0]
-    sarr = np.array([search.width, search.height, search.org_output_width, search.org_output_height, search.horizontal_readout], dtype=np.int32)
     fov = np.zeros(n, dtype=np.float64)
     dbg = np.zeros((n, 120, 2), dtype=np.float64) if debug else None
     rp = arr(np.asarray(rotations, dtype=np.float32).reshape(-1, 9), np.float32) if rotations is not None else None
-    rc = lib().gfw_emu_zoom(C.cast(C.byref(params), C.c_void_p), C.cast(C.byref(com), C.c_void_p), *targs, float(duration_ms), sarr.ctypes.data,
-                            float(search.fov_algorithm_margin), C.cast(frames, C.c_void_p), n, rp, fov.ctypes.data, dbg.ctypes.data if debug else None)
+    rc = lib().gfw_emu_zoom(C.cast(C.byref(params), C.c_void_p), C.cast(C.byref(com), C.c_void_p), *targs, float(duration_ms),
+                            C.cast(C.byref(search), C.c_void_p), C.cast(frames, C.c_void_p), n, rp, fov.ctypes.data, dbg.ctypes.data if debug else None)
     assert rc == 0, "gfw_emu_zoom -> %d" % rc
     return fov, dbg
 

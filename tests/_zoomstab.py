@@ -22,7 +22,7 @@ import math
 
 import numpy as np
 
-from gyroflow_amd import abi
+from gyroflow_amd import abi, warp
 import _emu
 import _hoststmt as H
 import _oracle as O
@@ -230,32 +230,6 @@ def inputs(clip, given_rotations=False, tile=1):
     return kp, search, frames, rot, (stabs * tile if stabs is not None else None), (meshes * tile if meshes is not None else None)
 
 
-class GfwStab(C.Structure):
-    """GfwStab (gyroflow_amd/csrc/gfw_matrices.h)"""
-    _fields_ = [("offset", C.c_double), ("sensor_h", C.c_double), ("crop_y", C.c_double), ("crop_h", C.c_double), ("scale_x", C.c_double), ("scale_y", C.c_double),
-                ("height", C.c_double), ("ibis", C.c_void_p), ("ois", C.c_void_p), ("ibis_n", C.c_int32), ("ois_n", C.c_int32)]
-
-
-def stab_table(stabs, y_signs):
-    """what gfw_api_adjacent.inc's stab_device makes of [dict or None]: (ctypes array of GfwStab, the arrays it points into).  y_signs: the framebuffer sign of the
-    matrix path per frame (frame_transform.rs:234-241), 1.0 for at_timestamp_for_points (:413-416)"""
-    table, keep = (GfwStab * max(len(stabs), 1))(), []
-    for k, st in enumerate(stabs):
-        g = table[k]
-        if st is None:
-            g.ibis_n = g.ois_n = -1
-            continue
-        ibis = np.ascontiguousarray(st["ibis"], dtype=np.float64).reshape(-1, 4)
-        ois = np.ascontiguousarray(st["ois"], dtype=np.float64).reshape(-1, 4)
-        keep += [ibis, ois]
-        g.offset, g.sensor_h, g.crop_y, g.crop_h = st["offset"], st["sensor_size"][1], st["crop_area"][1], st["crop_area"][3]
-        g.scale_x = st["width"] / st["crop_area"][2] / st["pixel_pitch"][0]
-        g.scale_y = st["height"] / st["crop_area"][3] / st["pixel_pitch"][1] * y_signs[k]
-        g.height = st["height"]
-        g.ibis, g.ois, g.ibis_n, g.ois_n = ibis.ctypes.data if len(ibis) else None, ois.ctypes.data if len(ois) else None, len(ibis), len(ois)
-    return table, keep
-
-
 _zlib = None
 
 
@@ -265,7 +239,7 @@ def emu_zoom_fovs(params, model, digital, search, frames, rotations=None, stabs=
     if _zlib is None:
         L = C.CDLL(_emu.build({}, "", top="gfw_zoom.hip", n_asm=2, driver="emu_zoom_stab_driver.inc", extra_flags=()))
         vp, i32 = C.c_void_p, C.c_int
-        L.gfw_emu_zoom_stab.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, C.c_double, vp, C.c_float, vp, i32, vp, vp, vp, vp, vp, vp]
+        L.gfw_emu_zoom_stab.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, C.c_double, vp, vp, i32, vp, vp, vp, vp, vp, vp]
         _zlib = L
     n = len(frames)
     com = _emu.common_for(_emu._Lenses(model, digital), params)
@@ -281,29 +255,17 @@ def emu_zoom_fovs(params, model, digital, search, frames, rotations=None, stabs=
     else:
         targs = [None, None, 0, None, None, 0]
     targs += [arr(offsets[0], np.int64), arr(offsets[1], np.float64), len(offsets[0])] if offsets else [None, None, 0]
-    sarr = np.array([search.width, search.height, search.org_output_width, search.org_output_height, search.horizontal_readout], dtype=np.int32)
     fov, dbg = np.zeros(n, dtype=np.float64), np.zeros((n, 120, 2), dtype=np.float64)
     rp = arr(np.asarray(rotations, dtype=np.float32).reshape(-1, 9), np.float32) if rotations is not None else None
-    sp = None
+    sp = mp = lp = None                                                          # the entry point's own arguments (warp.Backend.zoom_fovs_stab makes them the same way)
     if stabs is not None:
-        table, held = stab_table(stabs, [1.0] * n)
-        keep += [table, held]
-        sp = C.cast(table, C.c_void_p)
-    mp = rp2 = None
-    if meshes is not None:                                                       # consecutive frames naming the same array: one copy
-        ref, data = np.zeros((n, 2), dtype=np.int32), []
-        at = first = 0
-        for k, m in enumerate(meshes):
-            if m is None or len(m) == 0:
-                continue
-            if not (k and meshes[k - 1] is m):
-                first = at
-                data.append(np.asarray(m, dtype=np.float64))
-                at += len(m)
-            ref[k] = (first, len(m))
-        mp, rp2 = arr(np.concatenate(data) if data else np.zeros(1), np.float64), arr(ref, np.int32)
-    rc = _zlib.gfw_emu_zoom_stab(C.cast(C.byref(params), C.c_void_p), C.cast(C.byref(com), C.c_void_p), *targs, float(duration_ms), sarr.ctypes.data,
-                                 float(search.fov_algorithm_margin), C.cast(frames, C.c_void_p), n, rp, fov.ctypes.data, dbg.ctypes.data, sp, mp, rp2)
+        sp, held = warp.frame_stab_table(stabs)
+        keep.append(held)
+    if meshes is not None:
+        mp, lp, held = warp.frame_mesh_table(meshes)
+        keep.append(held)
+    rc = _zlib.gfw_emu_zoom_stab(C.cast(C.byref(params), C.c_void_p), C.cast(C.byref(com), C.c_void_p), *targs, float(duration_ms),
+                                 C.cast(C.byref(search), C.c_void_p), C.cast(frames, C.c_void_p), n, rp, fov.ctypes.data, dbg.ctypes.data, sp, mp, lp)
     assert rc == 0, "gfw_emu_zoom_stab -> %d" % rc
     return fov, dbg
 
@@ -326,7 +288,7 @@ def emu_build_matrices_stab(org, smoothed, timings, stabs, rows, offsets=None, d
     fts = np.ascontiguousarray(offsets[0] if offsets else [], dtype=np.int64)
     fms = np.ascontiguousarray(offsets[1] if offsets else [], dtype=np.float64)
     out = np.zeros((n, rows, 16), dtype=np.float32)
-    table, keep = stab_table(stabs, [-1.0 if t.framebuffer_inverted else 1.0 for t in timings])
+    table, keep = warp.frame_stab_table(stabs)
     lib.gfw_emu_build_matrices_stab.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
                                                 C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     rc = lib.gfw_emu_build_matrices_stab(ot.ctypes.data, oq.ctypes.data, len(ot), st.ctypes.data, sq.ctypes.data, len(st),

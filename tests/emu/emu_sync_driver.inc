@@ -2,6 +2,8 @@
 // gfw_sync_visual_costs / gfw_sync_visual_search enqueue them.  The fibers interpret workgroups of 64 x 4 lanes on a one-dimensional grid: the lens and reduce stages
 // are launched that way on the device too; a cost workgroup is one wave (the lanes beyond leave at once) and its (candidate, pair) is unfolded from the linear index.
 #include "emu_fibers.inc"
+#include <vector>
+#include "../../gyroflow_amd/csrc/gfw_sync_host.h"
 [[noreturn]] void emu_unsupported(const char *what) { fprintf(stderr, "emu: %s is not interpreted\n", what); abort(); }
 
 static gfw_kernel_params emu_sP; static GfwCommon emu_sC; static GfwSyncArgs emu_sA; static GfwSyncReduceArgs emu_sR;
@@ -21,25 +23,33 @@ static int emu_sync_costs_launch(int n) {                                     //
     return emu::run_grid(n * emu_sA.n_pairs, emu_sync_cost_body);
 }
 
-// what: width, height, horizontal_readout, n_pairs, total.  work: rays [2 * total][4] f32, partial [max(n, 200) * max(n_pairs, 1)] u64, fine [200][2] f64 — the
-// caller's, as the context's device work space.  mode < 0: the costs of `candidates` (result NULL); 0 / 1: the search from the coarse `candidates`.
+// The arguments of gfw_sync_visual_costs (mode < 0: the costs of the `n` caller-given `candidates`, result NULL) / gfw_sync_visual_search (mode 0 / 1: `n` is the count
+// of coarse candidates the caller sized `costs` for — made here by the entry point's own rule, which has to agree).  What the entry stages goes into ONE block of
+// exactly the layout's bytes ("device" = host memory).  work: rays [2 * total][4] f32, partial [max(n, 200) * max(n_pairs, 1)] u64, fine [200][2] f64 — the caller's,
+// as the context's device work space.
 extern "C" int gfw_emu_sync(const void *kp, const void *common, const int64_t *org_ts, const double *org_q, int org_n, const int64_t *sm_ts, const double *sm_q, int sm_n,
-                            const int64_t *off_ts, const double *off_ms, int off_n, double duration_ms, const double *new_k, double video_rotation_deg, const int *what,
-                            const int64_t *pair_ts, const int32_t *pair_first, const float *points, const double *candidates, int n, int mode,
+                            const int64_t *off_ts, const double *off_ms, int off_n, double duration_ms, const gfw_sync_search *search,
+                            const int64_t *pair_ts, const int32_t *pair_first, const float *points_a, const float *points_b, int n_pairs, const double *candidates, int n, int mode,
+                            double initial_offset_ms, double search_size_ms, double frame_readout_time_ms, double scaled_fps,
                             float *rays, unsigned long long *partial, double *fine, double *costs, float *mapped, void *result, double *fine_costs) {
     memcpy(&emu_sP, kp, sizeof(emu_sP)); memcpy(&emu_sC, common, sizeof(emu_sC));
+    if (mode >= 0 && n != (int)gfw_sync_coarse_steps(mode, search_size_ms, scaled_fps) * (mode ? 2 : 1)) return -2;
     GfwSyncArgs &A = emu_sA;
     memset(&A, 0, sizeof(A));
+    const GfwSyncLayout S = gfw_sync_layout(n_pairs, n_pairs ? pair_first[n_pairs] : 0, (size_t)n);
+    static std::vector<uint64_t> block;
+    block.assign(S.total / 8, 0);
+    char *h = (char *)block.data();
+    gfw_sync_fill(S, pair_ts, pair_first, points_a, points_b, n_pairs, mode < 0 ? candidates : nullptr, n, mode, initial_offset_ms, search_size_ms, frame_readout_time_ms, h, h, A);
     A.T = GfwTracks{org_ts, org_q, org_n, sm_ts, sm_q, sm_n, off_ts, off_ms, off_n, duration_ms};
-    for (int i = 0; i < 9; ++i) A.F.new_k[i] = new_k[i];
-    A.F.video_rotation_deg = video_rotation_deg;
-    A.pair_ts = pair_ts; A.pair_first = pair_first; A.points = points; A.rays = (float4 *)rays; A.partial = partial;
-    A.candidates = candidates; A.mapped = mapped;
-    A.w = (float)what[0]; A.h = (float)what[1]; A.horizontal = what[2]; A.readout_dim = what[2] ? what[0] : what[1];
-    A.n_pairs = what[3]; A.total = what[4];
+    for (int i = 0; i < 9; ++i) A.F.new_k[i] = search->new_k[i];
+    A.F.video_rotation_deg = search->video_rotation_deg;
+    A.rays = (float4 *)rays; A.partial = partial; A.mapped = mapped;
+    A.w = (float)search->width; A.h = (float)search->height;
+    A.horizontal = search->horizontal_readout; A.readout_dim = search->horizontal_readout ? search->width : search->height;
     GfwSyncReduceArgs &R = emu_sR;
     memset(&R, 0, sizeof(R));
-    R.partial = partial; R.candidates = candidates; R.costs = costs; R.result = (gfw_sync_result *)result; R.fine = fine;
+    R.partial = partial; R.candidates = A.candidates; R.costs = costs; R.result = (gfw_sync_result *)result; R.fine = fine;
     R.n = n; R.n_pairs = A.n_pairs; R.column = mode == 1 ? 1 : 0; R.stage = 0;
     int rc = A.total > 0 ? emu::run_grid((A.total * 2 + 255) / 256, emu_sync_rays_body) : 0;
     if (!rc) rc = emu_sync_costs_launch(n);

@@ -1,5 +1,5 @@
 // emu_sync_gyro_driver.inc — TEST INFRASTRUCTURE: launches of the gyro-match search's kernels (gfw_sync_gyro.hip, compiled for the host above) on the fibers, in the order
-// gfw_sync_gyro_costs / gfw_sync_gyro_search enqueue them, over what gfw_gyro_stage (the entry points' own host staging, gfw_sync_gyro.h) makes of the caller's arrays.
+// gfw_sync_gyro_costs / gfw_sync_gyro_search enqueue them, over what gfw_gyro_stage (the entry points' own host staging, gfw_sync_gyro_host.h) makes of the caller's arrays.
 // The fibers interpret workgroups of 64 x 4 lanes on a one-dimensional grid: the pick stage is launched that way on the device too; a cost workgroup's (block of
 // candidates, range) is unfolded from the linear index.
 #include "emu_fibers.inc"
@@ -28,18 +28,15 @@ extern "C" int gfw_emu_sync_gyro(const int32_t *est_first, const double *est, co
     const size_t n_coarse = search ? (size_t)gfw_gyro_key(search_size_ms) * 2 : 0;
     const size_t tot_est = (size_t)(est_first[n_ranges] - est_first[0]), tot_gyro = (size_t)(gyro_first[n_ranges] - gyro_first[0]);
     const size_t tot_cand = search ? n_coarse * (size_t)n_ranges : (size_t)(cand_first[n_ranges] - cand_first[0]);
-    std::vector<GfwGyroRange> ranges((size_t)n_ranges);
-    std::vector<double> h_est(tot_est * 4 + 1), h_val(tot_gyro * 4 + 1), h_cand(tot_cand + 1);
-    std::vector<uint8_t> h_has(tot_est + 1);
-    std::vector<unsigned long long> h_keys(tot_gyro + 1);
-    const GfwGyroSeries se = {est_first, est, est_has}, sg = {gyro_first, gyro, gyro_has};
-    const int max_cand = gfw_gyro_stage(se, sg, n_ranges, search ? nullptr : cand_first, candidates, n_coarse, initial_offset_ms, search_size_ms, ranges.data(), h_est.data(), h_has.data(),
-                                        h_keys.data(), h_val.data(), h_cand.data());
-    if (gyro_kept) for (int r = 0; r < n_ranges; ++r) gyro_kept[r] = ranges[r].gyro_n;
+    const GfwGyroLayout L = gfw_gyro_layout(n_ranges, tot_est, tot_gyro, tot_cand);
+    std::vector<uint64_t> block(L.total / 8);                                 // ONE block of exactly the layout's bytes ("device" = host memory)
+    char *h = (char *)block.data();
     GfwGyroArgs &A = emu_gA;
     memset(&A, 0, sizeof(A));
-    A.ranges = ranges.data(); A.est = h_est.data(); A.est_has = h_has.data(); A.keys = h_keys.data(); A.gyro = h_val.data();
-    A.candidates = h_cand.data(); A.costs = search ? costs : costs + cand_first[0]; A.stage = 0;      // as the entry point: the caller's entries cand_first[0] ..
+    const GfwGyroSeries se = {est_first, est, est_has}, sg = {gyro_first, gyro, gyro_has};
+    const int max_cand = gfw_gyro_fill(L, se, sg, n_ranges, search ? nullptr : cand_first, candidates, n_coarse, initial_offset_ms, search_size_ms, h, h, A);
+    if (gyro_kept) for (int r = 0; r < n_ranges; ++r) gyro_kept[r] = A.ranges[r].gyro_n;
+    A.costs = search ? costs : costs + cand_first[0]; A.stage = 0;          // as the entry point: the caller's entries cand_first[0] ..
     int rc = emu_gyro_costs_launch(n_ranges, max_cand);
     if (rc || !search) return rc;
     GfwGyroPickArgs &R = emu_gR;

@@ -1,0 +1,28 @@
+"""The entry points' host packers (gfw_matrices_host.h, gfw_zoom_host.h, gfw_sync_host.h, gfw_sync_gyro_host.h) in a stand-alone program (tests/cpp/test_host_packers.cpp)
+built with AddressSanitizer and UBSan: the host pass of the project's compiler only, no device, no library, nothing loaded into Python.  Each packer fills a heap block
+of exactly its layout's total at a fake device base; the program checks the parts' alignment, the argument pointers and the contents, the sanitizers every access."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    assert os.path.exists(HIPCC), "hipcc not found"
+    out = str(tmp_path_factory.mktemp("cpp") / "test_host_packers")
+    r = subprocess.run([HIPCC, "-x", "hip", "--offload-arch=gfx950", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
+                        "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                        os.path.join(ROOT, "tests", "cpp", "test_host_packers.cpp"), "-o", out], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    return out
+
+
+def test_host_packers_under_asan_and_ubsan(exe):
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "host packers ok" in r.stdout
