@@ -653,10 +653,14 @@ def undistort_points(params, model, digital, rotations, points=None, grid=None, 
 def build_matrices(org, smoothed, nk, timestamps_ms, frame_readout_time_ms, rows, readout_dim, video_rotation_deg=0.0, framebuffer_inverted=False,
                    per_frame_offset_ms=0.0, offsets=None, duration_ms=1.0, suppress_rotation=0, stab=None):
     """gfw_build_matrices(_batch / _stab) through the host-interpreted kernels -> float32 [frames][rows][16] (packed rows).  Arguments as the Python
-    wrappers of gyroflow_amd/warp.py take them; `stab` as a dict(offset, sensor_size, crop_area, pixel_pitch, width, height, ibis, ois)."""
+    wrappers of gyroflow_amd/warp.py take them; `stab` as a dict(offset, sensor_size, crop_area, pixel_pitch, width, height, ibis, ois).  `rows` / `readout_dim`:
+    one value, or one per frame (the grid is then sized by the largest, as gfw_build_matrices_batch sizes it; rows past a frame's own stay zero)."""
     lib = C.CDLL(build({}, "", top="gfw_matrices.hip", n_asm=2, driver="emu_matrices_driver.inc", extra_flags=()))
     ts_list = list(np.atleast_1d(timestamps_ms))
     n = len(ts_list)
+    rows_of = list(rows) if isinstance(rows, (list, tuple)) else [rows] * n
+    dim_of = list(readout_dim) if isinstance(readout_dim, (list, tuple)) else [readout_dim] * n
+    rows = max(rows_of)
     arr = (abi.FrameTiming * n)()
     nkf = np.asarray(nk, dtype=np.float64).reshape(9)
     for k, ts in enumerate(ts_list):
@@ -664,7 +668,7 @@ def build_matrices(org, smoothed, nk, timestamps_ms, frame_readout_time_ms, rows
         t.timestamp_ms, t.per_frame_time_offset_ms, t.frame_readout_time_ms = float(ts), per_frame_offset_ms, frame_readout_time_ms
         for i in range(9):
             t.new_k[i] = nkf[i]
-        t.video_rotation_deg, t.rows, t.readout_dim = video_rotation_deg, rows, readout_dim
+        t.video_rotation_deg, t.rows, t.readout_dim = video_rotation_deg, rows_of[k], dim_of[k]
         t.framebuffer_inverted = 1 if framebuffer_inverted else 0
         t.suppress_rotation = int(suppress_rotation)
     ot, oq = np.ascontiguousarray(org[0], dtype=np.int64), np.ascontiguousarray(org[1], dtype=np.float64)

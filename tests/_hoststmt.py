@@ -28,10 +28,22 @@ def slerp(a, b, t):
 
 
 def _as_i64(v):
-    """Rust `f64 as i64`: truncate toward zero (saturating, NaN -> 0)."""
+    """Rust `f64 as i64`: truncate toward zero, saturating, NaN -> 0 (total: infinities and values beyond i64 included)."""
     if v != v:
         return 0
-    return int(max(min(math.trunc(v), 2 ** 63 - 1), -2 ** 63))
+    if v >= 9223372036854775807.0:
+        return 2 ** 63 - 1
+    if v <= -9223372036854775808.0:
+        return -2 ** 63
+    return int(math.trunc(v))
+
+
+def _round(v):
+    """f64::round: to the nearest integer, halves away from zero, exactly (no `v + 0.5`, which rounds); NaN and the infinities pass through."""
+    if v != v or math.isinf(v):
+        return v
+    t = float(math.trunc(v))
+    return t + math.copysign(1.0, v) if abs(v - t) >= 0.5 else t
 
 
 def offset_at(offsets, timestamp_ms):
@@ -59,8 +71,7 @@ def quat_at(ts_us, quats, timestamp_ms, offsets=None, duration_ms=1.0):
     if len(ts_us) < 2 or not (duration_ms > 0.0):
         return np.array([1.0, 0.0, 0.0, 0.0])
     timestamp_ms = timestamp_ms - offset_at(offsets, timestamp_ms)
-    r = timestamp_ms * 1000.0
-    lookup = int(min(max(int(math.floor(r + 0.5)) if r >= 0 else int(math.ceil(r - 0.5)), int(ts_us[0])), int(ts_us[-1])))
+    lookup = max(min(_as_i64(_round(timestamp_ms * 1000.0)), int(ts_us[-1])), int(ts_us[0]))      # ((x * 1000.0).round() as i64).min(last).max(first)
     i = int(np.searchsorted(ts_us, lookup, side="right")) - 1
     if ts_us[i] == lookup or i + 1 >= len(ts_us):
         return quats[i].copy()
