@@ -59,13 +59,13 @@ def sync_visual_costs(params, model, digital, search, pairs, candidates, tracks,
 
 
 def sync_visual_search(params, model, digital, search, pairs, mode, tracks, initial_offset_ms=0.0, search_size_ms=0.0, frame_readout_time_ms=0.0, scaled_fps=30.0,
-                       offsets=None, duration_ms=1.0):
+                       offsets=None, duration_ms=1.0, fine=False):
     """gfw_sync_visual_search through the host-interpreted kernels -> (abi.SyncResult, coarse costs [n_coarse], fine costs [200]); the coarse candidates are made as
-    the entry point makes them, by its own code"""
+    the entry point makes them, by its own code.  fine: also the 200 fine candidates [200][2] the reduce stage wrote"""
     n = warp.sync_coarse_count(mode, search_size_ms, scaled_fps)
-    costs, _, res, fine_costs, _ = _run(params, model, digital, search, pairs, n, mode, tracks, offsets, duration_ms, False,
-                                        (initial_offset_ms, search_size_ms, frame_readout_time_ms, scaled_fps))
-    return res, costs, fine_costs
+    costs, _, res, fine_costs, fine_cands = _run(params, model, digital, search, pairs, n, mode, tracks, offsets, duration_ms, False,
+                                                 (initial_offset_ms, search_size_ms, frame_readout_time_ms, scaled_fps))
+    return (res, costs, fine_costs, fine_cands) if fine else (res, costs, fine_costs)
 
 
 def sync_table(mapped, pair_first, width, height, candidates=None, column=0):

@@ -32,6 +32,7 @@ class _Side:
         self.readout, self.timestamps = float(readout), [timestamp_ms]
         self.tracks, self._nk = clip.tracks, clip.new_k()
         self.sync_offsets, self.duration_ms = (clip.sync_offsets if use_sync_offsets else None), clip.duration_ms
+        self._on_lookup = getattr(clip, "on_lookup", None)      # a clip given as plain data may watch its lookups (tests/_tablecase.py counts the ones between unequal keys)
 
     def time_offset_at(self, k):
         return 0.0
@@ -40,6 +41,8 @@ class _Side:
         return self._nk
 
     def quat_at(self, track, timestamp_ms):
+        if self._on_lookup is not None:
+            self._on_lookup(track, timestamp_ms, self.sync_offsets, self.duration_ms)
         return H.quat_at(track[0], track[1], timestamp_ms, self.sync_offsets, self.duration_ms)
 
 
