@@ -119,6 +119,8 @@ SYNC_FINE_CANDIDATES = 200       # the second stage's candidates
 SYNC_PAIR_POINTS_MAX = 4096
 SYNC_GYRO_RANGES_MAX, SYNC_GYRO_EST_MAX, SYNC_GYRO_SAMPLES_MAX, SYNC_GYRO_CANDIDATES_MAX = 65535, 65536, 1 << 22, 2000000      # gfw_sync_gyro_*: per call / per range
 SYNC_GYRO_RING_SLOTS = 2         # staging slots of gfw_sync_gyro_*: calls an asynchronous context takes before one waits for an earlier copy
+SYNC_OPTIM_FFT_MIN, SYNC_OPTIM_FFT_MAX, SYNC_OPTIM_SAMPLES_MAX, SYNC_OPTIM_TARGET_MAX, SYNC_OPTIM_TRIM_MAX = 16, 8192, 1 << 24, 65535, 1024      # gfw_sync_optim_*
+SYNC_OPTIM_RING_SLOTS = 2        # staging slots of gfw_sync_optim_*
 FILTER_NOT_APPLIED = 1           # gfw_lowpass_gyro: the reference's from_params would fail; the data is untouched
 ZOOM_RECT_POINTS = 120           # points_around_rect(w, h, 31, 31)
 
@@ -202,6 +204,10 @@ def bind(lib):
     lib.gfw_lowpass_gyro.argtypes = [C.c_double, C.c_double, vp, vp, i32]; lib.gfw_lowpass_gyro.restype = i32
     lib.gfw_sync_gyro_costs.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, i32, vp, i32]; lib.gfw_sync_gyro_costs.restype = i32
     lib.gfw_sync_gyro_search.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, i32]; lib.gfw_sync_gyro_search.restype = i32
+    lib.gfw_optim_tables.argtypes = [i32, vp, vp, vp]; lib.gfw_optim_tables.restype = i32
+    lib.gfw_optim_resample.argtypes = [vp, vp, vp, i32, vp, C.c_int64, vp, vp]; lib.gfw_optim_resample.restype = i32
+    lib.gfw_sync_optim_rank.argtypes = [vp, vp, C.c_int64, C.c_double, vp, vp, vp, vp, vp, i32]; lib.gfw_sync_optim_rank.restype = i32
+    lib.gfw_sync_optim_points.argtypes = [vp, vp, C.c_int64, C.c_double, i32, vp, i32, vp, vp, vp, vp, vp, i32]; lib.gfw_sync_optim_points.restype = i32
     lib.gfw_pack_matrices.argtypes = [vp, i32, vp]; lib.gfw_pack_matrices.restype = i32
     lib.gfw_checksum64.argtypes = [vp, vp, sz, vp]; lib.gfw_checksum64.restype = i32
     lib.gfw_set_frame_checksums.argtypes = [vp, vp, sz]; lib.gfw_set_frame_checksums.restype = i32
@@ -226,7 +232,8 @@ EXPORTS = ["gfw_abi_version", "gfw_list_devices", "gfw_set_device", "gfw_get_inf
            "gfw_pixel_type_info", "gfw_undistort_clip", "gfw_undistort_clip_params", "gfw_jit_status", "gfw_get_profile_frames", "gfw_debug_jit_compile", "gfw_debug_source_id", "gfw_debug_p1_radial", "gfw_debug_paired_launches", "gfw_debug_frames_per_launch",
            "gfw_debug_jit_key_clip_params", "gfw_zoom_fovs", "gfw_zoom_smooth",
            "gfw_build_matrices_batch_stab", "gfw_zoom_fovs_stab", "gfw_sync_visual_costs", "gfw_sync_visual_search",
-           "gfw_lowpass_gyro", "gfw_sync_gyro_costs", "gfw_sync_gyro_search"]
+           "gfw_lowpass_gyro", "gfw_sync_gyro_costs", "gfw_sync_gyro_search",
+           "gfw_optim_tables", "gfw_optim_resample", "gfw_sync_optim_rank", "gfw_sync_optim_points"]
 
 
 def load_library(path=None):

@@ -10,7 +10,7 @@ range is ONE device call, ``Backend.sync_visual_search`` (gfw_sync_visual_search
 The 90 %-of-range acceptance rule (:137) and the range's middle timestamp are applied here.
 
 Not covered: clips with per-frame time offsets, stabiliser data or lens meshes, keyframed lens data or video rotation inside a range,
-suppress_rotation; the optical flow that produces the matched points, pose estimation, rs_sync itself, optimsync.
+suppress_rotation; the optical flow that produces the matched points, pose estimation, rs_sync itself.
 
     offsets = synchronization.find_offsets_essential(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params, backend)
     initial_offset, search_size = synchronization.initial_offset_fast(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params, backend)
@@ -19,6 +19,13 @@ suppress_rotation; the optical flow that produces the matched points, pose estim
 ``2 * search_size`` coarse and 200 fine candidate offsets; here ALL ranges are one device call, ``Backend.sync_gyro_search`` (gfw_sync_gyro_search).  The guards,
 the range cut, the gyro window, the max-angle skip, the two 20 Hz low-pass calls (``warp.lowpass_gyro``), the 90 % rule and the middle timestamp are applied
 here.  The estimated rates are the caller's input: pose estimation is not covered.
+
+    optim = synchronization.OptimSync.new(raw_imu)
+    points_ms, rank, ratio = optim.run(target_sync_points, trim_ranges_s, backend)
+
+``OptimSync`` (optimsync.rs) decides WHERE in the clip to sync, before any optical flow (lib.rs:2054-2060): ``new`` resamples the gyro at its average rate on
+the host (``warp.optim_resample``), ``run`` is ONE device call, ``Backend.sync_optim_points`` (gfw_sync_optim_points) — the windowed spectrum of the whole clip,
+band energies, rank, masks, non-maximum suppression and one pick per segment.
 """
 import numpy as np
 
@@ -159,3 +166,26 @@ def initial_offset_fast(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges
         if offsets:
             return median_offset(o for _, o, _ in offsets), 3000.0
     return sync_params.initial_offset, sync_params.search_size
+
+
+class OptimSync:
+    """``OptimSync`` (optimsync.rs:10-226): the gyro series at its average rate, and the choice of a clip's sync points from it."""
+
+    def __init__(self, sample_rate, gyro):
+        self.sample_rate, self.gyro = float(sample_rate), np.ascontiguousarray(np.asarray(gyro, dtype=np.float64).reshape(3, -1))
+
+    @classmethod
+    def new(cls, raw_imu):
+        """``OptimSync::new`` (:30-66).  ``raw_imu``: [(timestamp_ms, (x, y, z) or None)]; None without samples, as the reference."""
+        from . import warp
+        if len(raw_imu) == 0:
+            return None
+        ts = np.array([float(t) for t, _ in raw_imu], dtype=np.float64)
+        has = np.array([0 if g is None else 1 for _, g in raw_imu], dtype=np.uint8)
+        xyz = np.array([(0.0, 0.0, 0.0) if g is None else tuple(g) for _, g in raw_imu], dtype=np.float64).reshape(-1, 3)
+        gyro, rate = warp.optim_resample(ts, xyz, has)
+        return cls(rate, gyro)
+
+    def run(self, target_sync_points, trim_ranges_s, backend):
+        """``OptimSync::run`` (:68-225) -> (points_ms, rank before the masks, ratio = 16 / sample_rate): one ``Backend.sync_optim_points`` call."""
+        return backend.sync_optim_points(self.gyro, self.sample_rate, target_sync_points, trim_ranges_s)

@@ -433,6 +433,42 @@ class Backend:
         out = [res[i] for i in range(n)]
         return (out, coarse[:n * n_coarse].reshape(n, n_coarse), fine[:n]) if costs else out
 
+    def sync_optim_rank(self, gyro, sample_rate, out_ptrs=None):
+        """The band energies and the rank of every window of a gyro series (optimsync.rs:73-149) in one device call (gfw_sync_optim_rank).
+        ``gyro``: [3][S] float64, axis after axis (``optim_resample``).  Returns (lf, mf, hf, rank) float32 [n_windows] — or, with ``out_ptrs`` (four device
+        pointers or None each, to n_windows floats), the window count: in order on the stream."""
+        g = np.ascontiguousarray(np.asarray(gyro, dtype=np.float64).reshape(3, -1))
+        s = g.shape[1]
+        n_w = C.c_int32(0)
+        args = (self.ctx, g.ctypes.data if s else None, s, float(sample_rate))
+        if out_ptrs is not None:
+            self._check(self.lib.gfw_sync_optim_rank(*args, *out_ptrs, C.addressof(n_w), 1))
+            return n_w.value
+        cap = max(s // 16 + 1, 1)
+        outs = [np.zeros(cap, dtype=np.float32) for _ in range(4)]
+        self._check(self.lib.gfw_sync_optim_rank(*args, *[o.ctypes.data for o in outs], C.addressof(n_w), 0))
+        return tuple(o[:n_w.value] for o in outs)
+
+    def sync_optim_points(self, gyro, sample_rate, target_sync_points, trim_ranges_s, details=False, out_ptrs=None):
+        """OptimSync::run (optimsync.rs:68-225) in one device call (gfw_sync_optim_points): where in the clip to sync.  ``trim_ranges_s``: [(from_s, to_s)].
+        Returns (points_ms float64, rank float32 [n_windows] before the masks, ratio) — with ``details`` also rank_nms — or, with ``out_ptrs`` = (points_ms,
+        n_points, rank or None, rank_nms or None) device pointers, the ratio: in order on the stream."""
+        g = np.ascontiguousarray(np.asarray(gyro, dtype=np.float64).reshape(3, -1))
+        s = g.shape[1]
+        tr = np.ascontiguousarray(np.asarray(list(trim_ranges_s), dtype=np.float64).reshape(-1, 2))
+        ratio = C.c_double(0.0)
+        args = (self.ctx, g.ctypes.data if s else None, s, float(sample_rate), int(target_sync_points), tr.ctypes.data if len(tr) else None, len(tr))
+        if out_ptrs is not None:
+            self._check(self.lib.gfw_sync_optim_points(*args, *out_ptrs, C.addressof(ratio), 1))
+            return ratio.value
+        cap = max(s // 16 + 1, 1)
+        pts, n_pts = np.zeros(max(int(target_sync_points), 1), dtype=np.float64), C.c_int32(0)
+        rank, nms = np.zeros(cap, dtype=np.float32), np.zeros(cap, dtype=np.float32)
+        self._check(self.lib.gfw_sync_optim_points(*args, pts.ctypes.data, C.addressof(n_pts), rank.ctypes.data, nms.ctypes.data if details else None, C.addressof(ratio), 0))
+        n_w = optim_window_count(s, sample_rate)
+        out = (pts[:n_pts.value], rank[:n_w], ratio.value)
+        return out + (nms[:n_w],) if details else out
+
     def synchronize(self):
         self._check(self.lib.gfw_synchronize(self.ctx))
 
@@ -468,6 +504,34 @@ def sync_gyro_coarse_count(search_size_ms):
     """candidates of the gyro-match search's first stage: `search_size as usize * 2` (essential_matrix.rs:55) — the cast comes before the multiplication"""
     v = float(search_size_ms)
     return 0 if v != v or v <= 0.0 else int(min(v, 2.0 ** 62)) * 2
+
+
+def optim_window_count(n_samples, sample_rate):
+    """windows of gfw_sync_optim_*: `windows(fft_size).step_by(16)` with fft_size = `sample_rate.round() as usize` (optimsync.rs:82, :93-94)"""
+    v = float(sample_rate)
+    n = 0 if v != v or v <= 0.0 else int(min(np.floor(v + 0.5), 2.0 ** 62))
+    return 0 if n < 1 or n_samples < n else (int(n_samples) - n) // 16 + 1
+
+
+def optim_resample(timestamps_ms, xyz, has=None):
+    """OptimSync::new (optimsync.rs:30-66) on the host (gfw_optim_resample; no context, no GPU): the gyro resampled at its average rate -> (float64 [3][S], sample_rate).
+    ``has``: None or [n], 0 = `gyro: None`."""
+    ts = np.ascontiguousarray(np.asarray(timestamps_ms, dtype=np.float64).reshape(-1))
+    v = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+    h = None if has is None else np.ascontiguousarray((np.asarray(has).reshape(-1) != 0).astype(np.uint8))
+    assert len(v) == len(ts) and (h is None or len(h) == len(ts))
+    lib = abi.load_library()
+    n_out, rate = C.c_int64(0), C.c_double(0.0)
+    args = (ts.ctypes.data if len(ts) else None, v.ctypes.data if len(ts) else None, h.ctypes.data if h is not None and len(h) else None, len(ts))
+    rc = lib.gfw_optim_resample(*args, None, 0, C.addressof(n_out), C.addressof(rate))
+    if rc < 0:
+        raise GfwError(rc, lib.gfw_last_error().decode())
+    out = np.zeros((3, n_out.value), dtype=np.float64)
+    if out.size:
+        rc = lib.gfw_optim_resample(*args, out.ctypes.data, n_out.value, C.addressof(n_out), C.addressof(rate))
+        if rc < 0:
+            raise GfwError(rc, lib.gfw_last_error().decode())
+    return out, rate.value
 
 
 def lowpass_gyro(freq, sample_rate, xyz, has=None):

@@ -593,7 +593,7 @@ int   gfw_zoom_smooth(const double *fov_minimal, int n, double adaptive_zoom_win
  * HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA, a non-zero reserved slot, no tracks.
  * NOT covered: clips with per_frame_time_offsets, camera_stab_data or mesh_correction (in the reference the frame index, and so
  * the mesh, follows `timestamp - offs`); lens data or a video rotation keyframed inside a range; suppress_rotation; optical
- * flow, pose estimation, rs_sync, optimsync.  (essential_matrix: gfw_sync_gyro_search below.) */
+ * flow, pose estimation, rs_sync.  (essential_matrix: gfw_sync_gyro_search below; optimsync: gfw_sync_optim_points below.) */
 typedef struct gfw_sync_search {
     int32_t width, height;            /* params.width / height: the bounds test (`w as f32`) and the readout divisor */
     int32_t horizontal_readout;
@@ -644,7 +644,7 @@ int   gfw_sync_visual_search(gfw_ctx *ctx, const gfw_kernel_params *params, cons
  * GFW_ERR_INVALID_ARGUMENT, the range named in gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative
  * counts, a negative or descending first array, a slice outside its array, a non-finite initial_offset or search_size, a negative
  * search_size, counts over the limits above.  Non-finite sample values are not rejected; the pick among NaN costs is unspecified.
- * NOT covered: pose estimation, optical flow, rs_sync itself, optimsync.
+ * NOT covered: pose estimation, optical flow, rs_sync itself.
  *
  * gfw_lowpass_gyro: Lowpass::filter_gyro_forward_backward (filtering.rs:46-74) of xyz [n][3] f64 in place, on the host (no context):
  * biquad's second-order Butterworth low-pass (Q = 1/sqrt 2), transposed direct form II, forward over the series and then backward;
@@ -660,6 +660,49 @@ int   gfw_sync_gyro_search(gfw_ctx *ctx, const int32_t *est_first, const double 
                            const int32_t *gyro_first, const double *gyro, const uint8_t *gyro_has, int n_gyro, int n_ranges,
                            double initial_offset_ms, double search_size_ms, gfw_sync_result *results, double *coarse_costs, double *fine_costs,
                            int out_on_device);
+
+/* ---- synchronization: where in a clip to sync (OptimSync) in one device call ----
+ * optimsync.rs:68-225, which StabilizationManager runs before any optical flow: a Blackman-windowed spectrum of
+ * fft_size = round(sample_rate) gyro samples per axis every 16 samples, every bin folded with its mirror
+ * (`zip(cm.iter(), cm.iter().rev())`: X[k] + X[fft_size-1-k]), norm * scale, the axes merged as (x + y) + z; the band sums lf / mf / hf over
+ * bins [map_to_bin(0), map_to_bin(2)), [.. 2, 30), [.. 30, 2000) with map_to_bin(f) = round(fft_size / sample_rate * f) clamped to
+ * 0 .. fft_size/2 - 1; the rank (the low-motion formula when max(mf) < 50); the masks (rank < 50, outside every trim range, the first
+ * and last 2 s when the windows span more than 12 s); the non-maximum suppression over `(sample_rate / 16 / 2 * 8) as usize` windows;
+ * per segment of ceil(len / target) windows the LAST maximal element unless it is < 0.1, as the time
+ * (idx * 16 + fft_size / 2.0) / sample_rate * 1000.0 ms.
+ * The reference's transform is rustfft in f32, whose summation order is no contract; the quantity is restated: bin k of
+ * a window is the left fold over n of xw[n] * cos[(k n) mod fft_size] (and of -(xw[n] * sin[..])), every product and sum one f32 operation,
+ * xw[n] = (x[n] as f32) * win[n], the tables those of gfw_optim_tables; X[fft_size-1-k] of a real input is conj(X[k+1]); the norm is
+ * sqrtf(re * re + im * im).  Everything behind the bins is the reference's own f32 arithmetic in its own order.
+ *   gyro       [3][n_samples] f64, axis after axis (OptimSync::new's series: gfw_optim_resample); cast to f32 while staging
+ *   limits     fft_size 16 .. 8192, n_samples <= 2^24, target_sync_points 1 .. 65535, at most 1024 trim ranges
+ * gfw_sync_optim_rank: lf, mf, hf, rank (before the masks) [n_windows] f32, each NULL or host / device memory (out_on_device);
+ * n_windows (NULL, or ALWAYS host memory: the arguments decide it) = 0 when n_samples < fft_size, else (n_samples - fft_size) / 16 + 1.
+ * gfw_sync_optim_points: points_ms [target_sync_points] f64 of which the first *n_points (int32) are written, in segment order; rank
+ * (before the masks) and rank_nms [n_windows] f32, NULL or memory as points_ms; ratio (NULL, or ALWAYS host memory) = 16 / sample_rate.
+ * trim_ranges_s [n_trim][2] f64 seconds; an empty list yields no points (`any` over nothing).  n_samples < fft_size succeeds with 0
+ * windows and 0 points.  The series travels in one pinned staging copy; both calls run in order on the context's stream (three and six
+ * launches for any clip length); with device outputs an asynchronous context returns without waiting.  Rejected with
+ * GFW_ERR_INVALID_ARGUMENT, the reason in gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative counts,
+ * target_sync_points < 1 (the reference divides by it) or > 65535, a non-finite or non-positive sample_rate, fft_size outside
+ * 16 .. 8192, n_samples > 2^24, more than 1024 trim ranges.  Non-finite gyro values are not rejected; the result among NaNs is
+ * unspecified.
+ *
+ * Host only, no context:
+ * gfw_optim_tables: blackman(fft_size) as optimsync.rs:15-27 writes it (f32 arithmetic, the C library's cosf, size = width - 1) and the
+ * twiddles cos / sin(2 pi j / fft_size), evaluated in f64 and rounded once; each array [fft_size] f32 or NULL.
+ * gfw_optim_resample: OptimSync::new (:30-66) of timestamps_ms [n], xyz [n][3], has [n] (0 = `gyro: None`; NULL = all present): the
+ * average rate over the samples that have a value, then `(duration_ms * rate / 1000.0) as usize` samples at i * 1000 / rate, each the
+ * two-sided linear interpolation around partition_point(timestamp < t) in f64 (a None side counts as zeros).  out: NULL (a query of
+ * *n_out and *sample_rate) or [3][out_stride] f64 with out_stride >= *n_out.  Rejected: n < 1, more than 2^24 samples. */
+int   gfw_optim_tables(int fft_size, float *win, float *cosv, float *sinv);
+int   gfw_optim_resample(const double *timestamps_ms, const double *xyz, const uint8_t *has, int n, double *out, int64_t out_stride,
+                         int64_t *n_out, double *sample_rate);
+int   gfw_sync_optim_rank(gfw_ctx *ctx, const double *gyro, int64_t n_samples, double sample_rate, float *lf, float *mf, float *hf, float *rank,
+                          int32_t *n_windows, int out_on_device);
+int   gfw_sync_optim_points(gfw_ctx *ctx, const double *gyro, int64_t n_samples, double sample_rate, int target_sync_points,
+                            const double *trim_ranges_s, int n_trim, double *points_ms, int32_t *n_points, float *rank, float *rank_nms,
+                            double *ratio, int out_on_device);
 
 /* First-pass audit of the fused kernel (GFW_OPT_KERNEL_VARIANT = 3): counters8 = {certified pixels,
  * certified-but-different-from-exact (must stay 0), queued to the exact path, queue overflows,

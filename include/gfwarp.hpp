@@ -18,12 +18,14 @@
 //   gyroflow::calculate_fovs               src/core/zooming/mod.rs:35-70    (the adaptive-zoom fov series: one device call + host smoothing)
 //   gyroflow::find_offsets_visual          src/core/synchronization/find_offset/visual_features.rs:10-147
 //   gyroflow::find_offsets_essential       src/core/synchronization/find_offset/essential_matrix.rs:13-91   (+ initial_offset_fast: rs_sync.rs:26-45)
+//   gyroflow::OptimSync                    src/core/synchronization/optimsync.rs   (where in a clip to sync: new on the host, run in one device call)
 //
 // `FrameTransform::at_timestamp` itself (quaternions -> per-row matrices) is input here: the caller provides
 // `matrices`, or builds them on the device with gfw_build_matrices / gfw_build_matrices_batch.
 #pragma once
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <limits>
@@ -465,5 +467,50 @@ inline SyncParams initial_offset_fast(gfw_ctx *ctx, const std::map<int64_t, Time
     sync_params.search_size = 3000.0;
     return sync_params;
 }
+
+// OptimSync (optimsync.rs:10-226): where in a clip to sync, decided before any optical flow (lib.rs:2054-2060).  `make` is OptimSync::new — the gyro resampled at its
+// average rate on the host (gfw_optim_resample; nullopt without samples, as the reference's None) — and `run` is OptimSync::run in ONE device call
+// (gfw_sync_optim_points): (points in ms, the rank of every window before the masks, ratio = 16 / sample_rate).
+struct OptimSync {
+    double sample_rate = 0.0;
+    std::array<std::vector<double>, 3> gyro;
+
+    static std::optional<OptimSync> make(const std::vector<TimeIMU> &raw_imu) {
+        if (raw_imu.empty()) return std::nullopt;
+        std::vector<double> ts(raw_imu.size()), xyz(raw_imu.size() * 3);
+        std::vector<uint8_t> has(raw_imu.size());
+        for (size_t i = 0; i < raw_imu.size(); ++i) {
+            ts[i] = raw_imu[i].timestamp_ms; has[i] = raw_imu[i].has_gyro ? 1 : 0;
+            for (int a = 0; a < 3; ++a) xyz[i * 3 + a] = raw_imu[i].gyro[a];
+        }
+        OptimSync o;
+        int64_t n = 0;
+        int rc = gfw_optim_resample(ts.data(), xyz.data(), has.data(), (int)raw_imu.size(), nullptr, 0, &n, &o.sample_rate);
+        if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+        std::vector<double> flat((size_t)n * 3);
+        if (n) rc = gfw_optim_resample(ts.data(), xyz.data(), has.data(), (int)raw_imu.size(), flat.data(), n, &n, &o.sample_rate);
+        if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+        for (int a = 0; a < 3; ++a) o.gyro[a].assign(flat.begin() + (size_t)a * (size_t)n, flat.begin() + (size_t)(a + 1) * (size_t)n);
+        return o;
+    }
+
+    std::tuple<std::vector<double>, std::vector<float>, double> run(gfw_ctx *ctx, size_t target_sync_points, const std::vector<std::pair<double, double>> &trim_ranges_s) const {
+        if (!ctx) throw GyroflowCoreError(GyroflowCoreError::Unknown, "OptimSync::run: no backend context for the sync point search");
+        const size_t n = gyro[0].size();
+        std::vector<double> flat(n * 3), trim(trim_ranges_s.size() * 2), points(std::max<size_t>(target_sync_points, 1));
+        for (int a = 0; a < 3; ++a) std::copy(gyro[a].begin(), gyro[a].end(), flat.begin() + (size_t)a * n);
+        for (size_t i = 0; i < trim_ranges_s.size(); ++i) { trim[2 * i] = trim_ranges_s[i].first; trim[2 * i + 1] = trim_ranges_s[i].second; }
+        std::vector<float> rank(n / 16 + 2);
+        int32_t n_points = 0;
+        double ratio = 0.0;
+        int rc = gfw_sync_optim_points(ctx, flat.data(), (int64_t)n, sample_rate, (int)std::min<size_t>(target_sync_points, (size_t)1 << 30), trim.data(), (int)trim_ranges_s.size(),
+                                       points.data(), &n_points, rank.data(), nullptr, &ratio, 0);
+        if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+        const double fft = std::floor(sample_rate + 0.5);
+        const size_t n_windows = (double)n < fft ? 0 : (n - (size_t)fft) / 16 + 1;                  // windows(fft_size).step_by(16), fft_size = sample_rate.round()
+        points.resize((size_t)n_points); rank.resize(n_windows);
+        return {points, rank, ratio};
+    }
+};
 
 }  // namespace gyroflow
