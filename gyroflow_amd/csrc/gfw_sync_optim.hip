@@ -21,6 +21,7 @@
 #define GFW_OPTIM_DYN_LDS(name) extern __shared__ float4 name[]
 #endif
 
+#define GFW_OPTIM_PICK_RESET (1 << 30)                                                 // pick stage: a lane's run held a NaN (rides in its s_idx)
 __device__ __forceinline__ int gfw_optim_lane() { return (int)(threadIdx.y * 64u + threadIdx.x); }
 
 // Spectrum stage: workgroup blockIdx.x is window blockIdx.x
@@ -127,7 +128,10 @@ __global__ __launch_bounds__(GFW_OPTIM_LANES) void gfw_optim_nms_kernel(const Gf
 }
 
 // One pick per segment (:182-204): workgroup blockIdx.x is a segment.  A lane folds a contiguous run, lane 0 the lanes' picks in lane order: together
-// Iterator::max_by over the segment in index order, which keeps the LAST maximal element
+// Iterator::max_by(partial_cmp(..).unwrap_or(Equal)) over the segment in index order — the sequential fold of `x > y ? x : y`, which keeps the LAST maximal element
+// and which a NaN RESETS: nothing compares greater than a NaN and a NaN compares greater than nothing, so the fold's state behind a NaN is what a fold begun at that
+// NaN would hold, whatever came before.  That operation is not associative, so a lane also reports whether its run held a NaN (bit 30 of s_idx: a segment has at
+// most 2^20 windows), and lane 0 then REPLACES its running pick by that lane's instead of comparing — the value behind the NaN must not meet the earlier maximum
 __global__ __launch_bounds__(GFW_OPTIM_LANES) void gfw_optim_pick_kernel(const GfwOptimArgs A) {
     __shared__ float s_val[GFW_OPTIM_LANES];
     __shared__ int s_idx[GFW_OPTIM_LANES];
@@ -138,19 +142,21 @@ __global__ __launch_bounds__(GFW_OPTIM_LANES) void gfw_optim_pick_kernel(const G
     const int run = (n + GFW_OPTIM_LANES - 1) / GFW_OPTIM_LANES;
     const int c0 = t * run < n ? t * run : n, c1 = c0 + run < n ? c0 + run : n;
     float best = 0.0f;
-    int idx = -1;
+    int idx = -1, reset = 0;
     for (int c = c0; c < c1; ++c) {
         const float v = A.rank_nms[start + c];
         if (idx < 0 || !(best > v)) { best = v; idx = c; }                           // max_by: the later of equals (and of what does not compare)
+        if (v != v) reset = GFW_OPTIM_PICK_RESET;
     }
-    s_val[t] = best; s_idx[t] = idx;
+    s_val[t] = best; s_idx[t] = idx < 0 ? idx : (idx | reset);
     __syncthreads();
     if (t == 0) {
         int pick = -1;
         float high = 0.0f;
         for (int j = 0; j < GFW_OPTIM_LANES; ++j) {
-            if (s_idx[j] < 0) continue;
-            if (pick < 0 || !(high > s_val[j])) { high = s_val[j]; pick = s_idx[j]; }
+            const int at = s_idx[j];
+            if (at < 0) continue;
+            if (pick < 0 || (at & GFW_OPTIM_PICK_RESET) || !(high > s_val[j])) { high = s_val[j]; pick = at & (GFW_OPTIM_PICK_RESET - 1); }
         }
         double ms = -1.0;
         if (pick >= 0 && !(high < 0.1f)) ms = ((double)(start + pick) * 16.0 + (double)A.fft_size / 2.0) / A.sample_rate * 1000.0;       // :199

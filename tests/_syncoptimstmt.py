@@ -155,10 +155,10 @@ def tail(lf, mf, hf, sample_rate, n, target, trims, dtype):
     """Everything behind the band energies (:134-204), in `dtype` arithmetic -> dict(points, rank, masked, rank_nms, ratio)"""
     T = dtype
     w = len(mf)
-    mf_max = T(0.0)
-    for v in ([np.max(mf)] if w else []):                                            # fold(0.0, f32::max): the order does not matter among numbers
-        mf_max = max(mf_max, v)
-    if mf_max < T(50.0):
+    # fold(0.0, f32::max): f32::max ignores a NaN, as fmaxf does, so the fold is total — and among numbers the order does not matter
+    mf_max = T(np.fmax.reduce(np.asarray(mf, dtype=T), initial=T(0.0))) if w else T(0.0)
+    low_motion = bool(mf_max < T(50.0))
+    if low_motion:
         rank = (lf + mf) / (T(1.0) + nlfunc(hf, T(450.0)) * T(0.003))
     else:
         rank = mf / (T(1.0) + nlfunc(hf, T(450.0)) * T(0.003)) / (T(1.0) + nlfunc(lf, T(650.0)) * T(0.003))
@@ -180,6 +180,7 @@ def tail(lf, mf, hf, sample_rate, n, target, trims, dtype):
             rank_nms[j] = T(0.0)
     points = []
     seg = (w + target - 1) // target
+    seg_pick = np.full(target, -1, dtype=np.int64)                                   # the window a segment's point stands for, -1 without one
     for i in range(target):
         start = i * seg
         end = min(start + seg, w)
@@ -192,8 +193,9 @@ def tail(lf, mf, hf, sample_rate, n, target, trims, dtype):
                 best = c
         if part[best] < T(0.1):
             continue
+        seg_pick[i] = start + best
         points.append((float(start + best) * 16.0 + float(n) / 2.0) / float(sample_rate) * 1000.0)
-    return dict(points=np.array(points, dtype=np.float64), rank=rank, masked=masked, rank_nms=rank_nms, ratio=ratio)
+    return dict(points=np.array(points, dtype=np.float64), rank=rank, masked=masked, rank_nms=rank_nms, ratio=ratio, low_motion=low_motion, seg_pick=seg_pick)
 
 
 def run_literal(gyro, sample_rate, target, trims):
@@ -235,6 +237,17 @@ def band_bound(merged64, absum, sample_rate):
 def same_bits(a, b):
     a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
     return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def same_bits_nan(a, b):
+    """same_bits for inputs that may be non-finite: NaNs at the same indices, with any sign or payload (x86 and the GPU may produce different default-NaN bit
+    patterns, and which operand's payload an operation forwards is no contract); every other element equal as a uint32 / uint64 view"""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.dtype != b.dtype or a.shape != b.shape or a.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        return False
+    na, nb = np.isnan(a), np.isnan(b)
+    view = np.uint32 if a.dtype == np.dtype(np.float32) else np.uint64
+    return bool(np.array_equal(na, nb) and np.array_equal(a.view(view)[~na], b.view(view)[~nb]))
 
 
 # ---- OptimSync::new ----

@@ -86,6 +86,37 @@ def reference_loops(rank, sample_rate, n, target, trims):
     return points, rank, nms
 
 
+def f32_max(a, b):
+    """f32::max: the other operand when one is a NaN"""
+    if a != a:
+        return b
+    if b != b:
+        return a
+    return a if a > b else b
+
+
+def reference_from_bands(lf, mf, hf, sample_rate, n, target, trims):
+    """The `mf_max` fold and the rank formulas (:136-149) in f32, one scalar operation at a time, ahead of reference_loops (whose compares are exact on f32 values
+    held as Python floats) -> (points, rank, masked rank, suppressed rank, low_motion)"""
+    T = np.float32
+    nlfunc = lambda arg, trip: T(0.0) if arg < trip else arg - trip
+    mf_max = T(0.0)
+    for v in mf:
+        mf_max = f32_max(mf_max, T(v))
+    low_motion = bool(mf_max < T(50.0))
+    rank = []
+    with np.errstate(all="ignore"):
+        for l, m, h in zip(lf, mf, hf):
+            l, m, h = T(l), T(m), T(h)
+            if low_motion:
+                rank.append((l + m) / (T(1.0) + nlfunc(h, T(450.0)) * T(0.003)))
+            else:
+                rank.append(m / (T(1.0) + nlfunc(h, T(450.0)) * T(0.003)) / (T(1.0) + nlfunc(l, T(650.0)) * T(0.003)))
+    assert all(type(v) is T for v in rank)
+    pts, masked, nms = reference_loops(rank, sample_rate, n, target, trims)
+    return np.array(pts, dtype=np.float64), np.array(rank, dtype=T), np.array(masked, dtype=T), np.array(nms, dtype=T), low_motion
+
+
 def tail64(mf, sample_rate, target, trims, lf=None, hf=None):
     mf = np.asarray(mf, dtype=np.float64)
     z = np.zeros_like(mf)
