@@ -91,6 +91,11 @@
 #define GFW_ROW_CLUSTER 0       // measured in round 5 (46.4 = 46.4 us; with the row's stores held back behind the NEXT row's matrix fetches 44.3 against 42.3: profiles/r05_ab_ablations.txt): the luma pair's and the chroma site's taps of a
                                  // 4:2:2 / 4:4:4 planar lane-row fetched in ONE cluster, stores last (the luma store between them is an aliasing barrier: the row waits twice)
 #endif
+#ifndef GFW_NT_STORE
+#define GFW_NT_STORE 1           // round 7: the branch-free row's destination stores (store_value1, store_pair1) are marked non-temporal — a destination line is written once and never
+                                 // read by the kernel, while source lines are re-read (L1 -> L2 read requests are 4.4 times the source bytes): 42.5 -> 41.9 us per C2 frame,
+                                 // five alternating pairs, every "on" run below every "off" run (profiles/r07_row_memops.txt).  0: plain stores (A/B)
+#endif
 #ifndef GFW_P1_LATTICE
 #define GFW_P1_LATTICE 1         // round 5: the certified first pass evaluated at the nodes of a lattice (every 8th luma column of the wave's first and last row: one node per
                                  // lane, once per tile) and interpolated bilinearly for the pixels, its curvature added to the certificate's half-width (DESIGN.md
@@ -1107,17 +1112,23 @@ __device__ __forceinline__ GfwVote lut_interior(int bx, int by, int w, int h) { 
     if (!(w >= I + TAP_MARGIN && h >= I)) return gfw_lanes(false);
     return gfw_lanes((unsigned)(bx >> 5) <= (unsigned)(w - I - TAP_MARGIN)) & gfw_lanes((unsigned)(by >> 5) <= (unsigned)(h - I));
 }
+// a destination store of the branch-free row: non-temporal under GFW_NT_STORE (a macro, so that the pointer keeps its alignment typedef)
+#if GFW_NT_STORE && !defined(GFW_HOST_INTERPRETER)
+#define GFW_STORE_OUT(p, v) __builtin_nontemporal_store((v), (p))
+#else
+#define GFW_STORE_OUT(p, v) (*(p) = (v))
+#endif
 template <typename T>
 __device__ __forceinline__ void store_value1(uint8_t *dst, int off, uint32_t v, unsigned long long *ck = nullptr) {
     if constexpr (is_f32<T>::value && sizeof(T) == 4) { *reinterpret_cast<uint32_t *>(dst + (uint32_t)off) = v; gfw_ck<uint32_t>((uint32_t)off, v, ck); }
     else if constexpr (is_f32<T>::value) { const T h = (T)__builtin_bit_cast(float, v); *reinterpret_cast<T *>(dst + (uint32_t)off) = h; gfw_ck<T>((uint32_t)off, h, ck); }      // (f16 planes: the f32 bit pattern, narrowed)
-    else { *reinterpret_cast<T *>(dst + (uint32_t)off) = (T)v; gfw_ck<T>((uint32_t)off, (T)v, ck); }
+    else { GFW_STORE_OUT(reinterpret_cast<T *>(dst + (uint32_t)off), (T)v); gfw_ck<T>((uint32_t)off, (T)v, ck); }
 }
 // two horizontally adjacent samples of an integer plane leave as ONE store (the pair's address need not be aligned to the pair: global memory takes it)
 template <typename T>
 __device__ __forceinline__ void store_pair1(uint8_t *dst, int off, uint32_t v0, uint32_t v1, unsigned long long *ck = nullptr, bool ck_inside = false) {
-    if constexpr (sizeof(T) == 1) { typedef uint16_t u16u __attribute__((aligned(1))); *reinterpret_cast<u16u *>(dst + (uint32_t)off) = (uint16_t)(v0 | (v1 << 8)); }
-    else if constexpr (sizeof(T) == 2) { typedef uint32_t u32u __attribute__((aligned(2))); *reinterpret_cast<u32u *>(dst + (uint32_t)off) = v0 | (v1 << 16); }
+    if constexpr (sizeof(T) == 1) { typedef uint16_t u16u __attribute__((aligned(1))); GFW_STORE_OUT(reinterpret_cast<u16u *>(dst + (uint32_t)off), (u16u)(v0 | (v1 << 8))); }
+    else if constexpr (sizeof(T) == 2) { typedef uint32_t u32u __attribute__((aligned(2))); GFW_STORE_OUT(reinterpret_cast<u32u *>(dst + (uint32_t)off), (u32u)(v0 | (v1 << 16))); }
     else { typedef uint2 u2u __attribute__((aligned(4))); *reinterpret_cast<u2u *>(dst + (uint32_t)off) = uint2{v0, v1}; }
     if constexpr (sizeof(T) == 1) gfw_ck_pair<uint8_t>((uint32_t)off, v0, v1, ck, ck_inside);
     else if constexpr (sizeof(T) == 2) gfw_ck_pair<uint16_t>((uint32_t)off, v0, v1, ck, ck_inside);
