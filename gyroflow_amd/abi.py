@@ -185,6 +185,8 @@ def bind(lib):
     lib.gfw_undistort_clip.restype = i32
     lib.gfw_undistort_clip_params.argtypes = [vp, i32, i32, C.POINTER(Buffers), C.POINTER(KernelParams), C.POINTER(i32), C.POINTER(vp), i32]
     lib.gfw_undistort_clip_params.restype = i32
+    lib.gfw_undistort_clip_lens.argtypes = [vp, i32, i32, C.POINTER(Buffers), C.POINTER(KernelParams), C.POINTER(i32), C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(sz)]
+    lib.gfw_undistort_clip_lens.restype = i32
     lib.gfw_debug_jit_compile.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, sz]; lib.gfw_debug_jit_compile.restype = C.c_long
     lib.gfw_jit_status.argtypes = [vp, C.POINTER(C.c_double), C.c_char_p, sz]; lib.gfw_jit_status.restype = i32
     lib.gfw_set_quaternion_tracks.argtypes = [vp, vp, vp, i32, vp, vp, i32]; lib.gfw_set_quaternion_tracks.restype = i32
@@ -221,6 +223,9 @@ def bind(lib):
     lib.gfw_debug_jit_key_clip_params.argtypes = [i32, i32, C.POINTER(Buffers), C.POINTER(KernelParams), C.POINTER(i32), i32, i32, C.POINTER(vp), i32, i32, i32,
                                                   C.c_char_p, C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, sz]
     lib.gfw_debug_jit_key_clip_params.restype = i32
+    lib.gfw_debug_jit_key_clip_lens.argtypes = [i32, i32, C.POINTER(Buffers), C.POINTER(KernelParams), C.POINTER(i32), i32, i32, C.POINTER(vp), i32, i32, C.POINTER(sz),
+                                                C.c_char_p, C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, sz]
+    lib.gfw_debug_jit_key_clip_lens.restype = i32
     lib.gfw_pixel_type_info.argtypes = [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_float)]
     lib.gfw_pixel_type_info.restype = i32
     return lib
@@ -230,7 +235,7 @@ EXPORTS = ["gfw_abi_version", "gfw_list_devices", "gfw_set_device", "gfw_get_inf
            "gfw_create", "gfw_destroy", "gfw_undistort_image", "gfw_undistort_frame", "gfw_set_option",
            "gfw_get_stream", "gfw_set_stream", "gfw_synchronize", "gfw_flush", "gfw_import_external_fd", "gfw_release_external", "gfw_last_backend", "gfw_get_profile", "gfw_last_error", "gfw_debug_math", "gfw_debug_jit_key", "gfw_debug_selftest", "gfw_get_audit", "gfw_pack_matrices", "gfw_checksum64", "gfw_set_frame_checksums", "gfw_set_quaternion_tracks", "gfw_build_matrices", "gfw_build_matrices_stab", "gfw_set_sync_offsets", "gfw_build_matrices_batch", "gfw_stmap_undistort", "gfw_undistort_points",
            "gfw_pixel_type_info", "gfw_undistort_clip", "gfw_undistort_clip_params", "gfw_jit_status", "gfw_get_profile_frames", "gfw_debug_jit_compile", "gfw_debug_source_id", "gfw_debug_p1_radial", "gfw_debug_paired_launches", "gfw_debug_frames_per_launch",
-           "gfw_debug_jit_key_clip_params", "gfw_zoom_fovs", "gfw_zoom_smooth",
+           "gfw_debug_jit_key_clip_params", "gfw_undistort_clip_lens", "gfw_debug_jit_key_clip_lens", "gfw_zoom_fovs", "gfw_zoom_smooth",
            "gfw_build_matrices_batch_stab", "gfw_zoom_fovs_stab", "gfw_sync_visual_costs", "gfw_sync_visual_search",
            "gfw_lowpass_gyro", "gfw_sync_gyro_costs", "gfw_sync_gyro_search",
            "gfw_optim_tables", "gfw_optim_resample", "gfw_sync_optim_rank", "gfw_sync_optim_points"]

@@ -88,6 +88,9 @@ struct gfw_ctx {
     size_t src_len = 0, dst_len = 0;              // sizes declared at create (opencl.rs:287-293)
     std::vector<DevBuf> stage_src, stage_dst;      // per-plane staging for HOST buffers
     DevBuf d_mesh;
+    // gfw_undistort_clip_lens: the lens slots and meshes of a moving-lens launch (gfw_api_clip.inc lens_stage), one slot of the ring per launch in flight
+    static constexpr int kLensSlots = 4;
+    StagingRing<kLensSlots> lens_ring;
     // per-row matrices: ring of (pinned host, device) slots so that an asynchronous caller can enqueue several frames; uploads run on their own stream and
     // overlap the previous frame's kernel: mat_copied[slot] hands the copy over to the context's stream, the slot is free again behind the kernel that read it
     static constexpr int kMatSlots = 4;
@@ -574,7 +577,8 @@ static bool int_products_exact(int n_max, int n) {
 }
 
 // One frame as the entry points take it: gfw_undistort_frame's arguments, a frame of a clip call, the planes a PlaneGroup assembled
-struct FrameIn { int nplanes; const gfw_buffers *planes; const gfw_kernel_params *params; const int *pixel_types; const float *matrices; int matrix_count; const float *mesh; size_t mesh_len; };
+struct FrameIn { int nplanes; const gfw_buffers *planes; const gfw_kernel_params *params; const int *pixel_types; const float *matrices; int matrix_count; const float *mesh; size_t mesh_len;
+                 bool mesh_checked = false; };      // (gfw_undistort_clip_lens validated the mesh before its first frame)
 #include "gfw_api_certificate.inc"
 #include "gfw_api_eligibility.inc"
 #include "gfw_api_clip.inc"
@@ -615,7 +619,7 @@ static int checksum_written(gfw_ctx *c, int nplanes, const gfw_buffers *planes, 
 // What run_planes' stages hand on: the planes as the kernels take them, the frame's tables on the device, its checksum word (gfw_set_frame_checksums; nullptr: off) ...
 struct StagedFrame { GfwPlane pl[8]; const float *d_mat = nullptr, *d_mesh = nullptr; unsigned long long *sum = nullptr; };
 // ... and the kernel that serves it: the fused one (Y, S) or the generic one per plane; the former's specialised build if there is one, which may take the checksum
-struct KernelChoice { bool fused = false, perframe = false; GfwYuvArgs Y; FusedShape S; hipFunction_t jf = nullptr; int jgrid = 0; bool sum_taken = false; };
+struct KernelChoice { bool fused = false; int perframe = 0; GfwYuvArgs Y; FusedShape S; hipFunction_t jf = nullptr; int jgrid = 0; bool sum_taken = false; };
 static const char *fused_backend(const FusedShape &S, bool jit) { return jit ? (S.fast1 ? "yuv_fused_p1_jit" : "yuv_fused_jit") : (S.fast1 ? "yuv_fused_p1" : "yuv_fused"); }
 // Stage 1: validate the call and stage what the kernels read — the checksum word, the matrices, the mesh, host planes
 static int stage_frame(gfw_ctx *c, const FrameIn &F, StagedFrame &G) {
@@ -628,15 +632,12 @@ static int stage_frame(gfw_ctx *c, const FrameIn &F, StagedFrame &G) {
         if (F.params[i].matrix_count != F.matrix_count) { set_error("plane %d: matrix_count %d != %d", i, F.params[i].matrix_count, F.matrix_count); return GFW_ERR_INVALID_ARGUMENT; }
     }
     if (F.mesh_len > GFW_MESH_MAX) { set_error("Buffer size mismatch buf_mesh_data! %d vs %zu", GFW_MESH_MAX, F.mesh_len); return GFW_ERR_BUFFER_SIZE_MISMATCH; }  // opencl.rs:352
-    { const int mrc = validate_mesh(F.mesh, F.mesh_len); if (mrc != GFW_OK) return mrc; }
+    if (!F.mesh_checked) { const int mrc = validate_mesh(F.mesh, F.mesh_len); if (mrc != GFW_OK) return mrc; }
     // gfw_set_frame_checksums: this frame's word (taken here, before anything is enqueued: a frame that writes host memory cannot be summed on the device)
     G.sum = c->dry ? nullptr : next_sum(c);
     if (G.sum) for (int i = 0; i < F.nplanes; ++i) if (F.planes[i].output.kind == GFW_BUF_HOST) { set_error("gfw_set_frame_checksums: plane %d writes a host buffer", i); return GFW_ERR_INVALID_ARGUMENT; }
     { const int rc = upload_matrices(c, F.matrices, F.matrix_count, &G.d_mat); if (rc != GFW_OK) return rc; }
-    if (F.mesh && F.mesh_len) {
-        HIP_TRY(hipMemcpyAsync(c->d_mesh.ptr, F.mesh, F.mesh_len * sizeof(float), hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
-        G.d_mesh = (const float *)c->d_mesh.ptr;
-    }
+    if (F.mesh && F.mesh_len) G.d_mesh = (const float *)c->d_mesh.ptr;      // (uploaded by run_planes once the frame is known to leave on its own: upload_mesh)
     if ((int)c->stage_src.size() < F.nplanes) { c->stage_src.resize(F.nplanes); c->stage_dst.resize(F.nplanes); }
     for (int i = 0; i < F.nplanes; ++i) {
         const gfw_buffers &b = F.planes[i];
@@ -683,7 +684,7 @@ static int choose_kernel(gfw_ctx *c, const FrameIn &F, const StagedFrame &G, Cli
         const long long lane_rows = (long long)Y.tiles_x * Y.tiles_y * gfw_yuv_rows_per_lane(S.fast1 != 0, 0) * S.dh;
         Y.checksum = (aligned && lane_rows < 8 * 32768ll) ? 1 : 0;
     }
-    K.perframe = batch && batch->perframe;            // (gfw_undistort_clip_params: the per-frame flavour, whose key blanks the per-frame fields)
+    K.perframe = clip_flavour(batch);                 // (gfw_undistort_clip_params: the per-frame flavour, whose key blanks the per-frame fields; gfw_undistort_clip_lens: the moving-lens one)
     K.jf = jit_for(c, Y, S, K.perframe, &K.jgrid);
     if (!K.jf && S.fast1 && Y.p1_rform) {
         // a table over r is read by specialised builds only: until one is loaded (or for good, without hiprtc and without a cached kernel) the frame takes the
@@ -706,13 +707,14 @@ static int join_launch(gfw_ctx *c, const FrameIn &F, const KernelChoice &K, unsi
     // (a frame that REBUILT the table has already sent them on their way, before the copy: p1_setup — they read the table with the range they were set up for)
     if (batch->n > 0 && (batch->fn != K.jf || batch->CA.Y.p1_table != Y.p1_table || batch->CA.Y.p1_rho_max != Y.p1_rho_max ||
                          batch->CA.Y.p1_rho_scale != Y.p1_rho_scale || batch->CA.Y.p1_eps != Y.p1_eps || batch->CA.Y.p1_ew != Y.p1_ew ||
-                         !(batch->perframe ? clip_same_params_pf(batch->CA.Y, Y) : clip_same_params(batch->CA.Y, Y)) || clip_overlaps(batch, F.planes, F.nplanes))) {
+                         !(batch->perframe ? clip_same_params_pf(batch->CA.Y, Y, batch->lens) : clip_same_params(batch->CA.Y, Y)) || clip_overlaps(batch, F.planes, F.nplanes))) {
         const int frc = clip_flush(c, batch); if (frc != GFW_OK) return frc;
     }
     if (batch->n == 0) { batch->CA.Y = Y; batch->fn = K.jf; batch->grid = K.jgrid; batch->first = F.planes; batch->backend = fused_backend(K.S, true);
                          batch->limit = clip_launch_limit(Y, F.nplanes, batch->n_call); }
     const GfwFramePer slot = frame_slot(Y);
-    { const int frc = clip_append(c, batch, frame_dyn(Y), K.perframe ? &slot : nullptr, sum); if (frc != GFW_OK) return frc; }
+    const GfwLensSlot lens = lens_slot(Y, nullptr, F.mesh_len);      // (the mesh: staged with the launch, from the caller's memory)
+    { const int frc = clip_append(c, batch, frame_dyn(Y), K.perframe ? &slot : nullptr, sum, K.perframe >= 2 ? &lens : nullptr, (Y.extras & 32) ? F.mesh : nullptr); if (frc != GFW_OK) return frc; }
     if (sum && !K.sum_taken) {                        // (a frame of a launch whose kernel does not take sums: behind the launch it has just joined)
         const int frc = clip_flush(c, batch); if (frc != GFW_OK) return frc;
         return checksum_written(c, F.nplanes, F.planes, F.params, sum);
@@ -726,7 +728,8 @@ static int launch_fused(gfw_ctx *c, const KernelChoice &K, unsigned long long *s
         GfwClipArgs CA;
         CA.Y = K.Y; CA.n_frames = 1; CA.pad_ = 0; CA.fr[0] = frame_dyn(K.Y);
         const GfwFramePer slot = frame_slot(K.Y);      // (a frame of gfw_undistort_clip_params that cannot join a launch — host buffers, a table of the ring — still takes its call's kernel)
-        const int rc = jit_launch(c, K.jf, K.jgrid, CA, K.perframe ? &slot : nullptr, &sum); if (rc != GFW_OK) return rc;
+        const GfwLensSlot lens = lens_slot(K.Y, K.Y.common.mesh, (size_t)K.Y.common.mesh_len);      // (the same for gfw_undistort_clip_lens; its mesh is the context's, uploaded for this frame)
+        const int rc = jit_launch(c, K.jf, K.jgrid, CA, K.perframe ? &slot : nullptr, &sum, K.perframe >= 2 ? &lens : nullptr); if (rc != GFW_OK) return rc;
     } else HIP_TRY(gfw_launch_yuv(K.Y, S.kind, S.taps, S.n0, S.dw, S.dh, S.interleaved != 0, S.fast1 != 0, c->stream), GFW_ERR_HIP);
     c->last_backend = fused_backend(S, K.jf != nullptr);
     return GFW_OK;
@@ -797,6 +800,8 @@ static int run_planes(gfw_ctx *c, const FrameIn &F, ClipBatch *batch = nullptr) 
     { const int rc = choose_kernel(c, F, G, batch, K); if (rc != GFW_OK) return rc; }
     if (K.jf && batch && frame_can_wait(c, F)) return join_launch(c, F, K, G.sum, batch);
     { const int rc = clip_flush(c, batch); if (rc != GFW_OK) return rc; }      // (the calls are ordered: what is pending leaves first)
+    // the frame's mesh goes to the context's one buffer only now: a frame that joined a launch above brought its mesh along with the launch's staged block
+    if (G.d_mesh) HIP_TRY(hipMemcpyAsync(c->d_mesh.ptr, F.mesh, F.mesh_len * sizeof(float), hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
     prof_begin(c);
     { const int rc = K.fused ? launch_fused(c, K, G.sum) : launch_per_plane(c, F, G); if (rc != GFW_OK) return rc; }
     return finish_frame(c, F, G, K.sum_taken);
@@ -961,6 +966,50 @@ int gfw_undistort_clip_params(gfw_ctx *c, int n_frames, int nplanes, const gfw_b
     clip_params_batch(batch, n_frames, nplanes, params);
     for (int f = 0; f < n_frames; ++f) {
         const int rc = run_planes(c, FrameIn{nplanes, planes + (size_t)f * nplanes, params + (size_t)f * nplanes, pixel_types, matrices[f], matrix_count, nullptr, 0}, &batch);
+        if (rc != GFW_OK) return clip_end(c, &batch, rc);
+    }
+    return clip_end(c, &batch, GFW_OK);
+}
+
+// The frame loop of a render whose LENS moves from frame to frame as well (FrameTransform::at_timestamp fills f, c, k and r_limit from
+// get_lens_data_at_timestamp — a zoom lens's interpolated profile, per-frame lens telemetry —, light_refraction_coefficient from a keyframe and the mesh from
+// mesh_correction[frame]).  Frames run exactly as gfw_undistort_frame would run each with its own params and mesh; frames that share everything the kernel is
+// compiled for leave in launches of the moving-lens flavour of the specialised kernel.  A call in which nothing of that moves and no
+// frame has a mesh IS gfw_undistort_clip_params.
+int gfw_undistort_clip_lens(gfw_ctx *c, int n_frames, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params,
+                            const int *pixel_types, const float *const *matrices, int matrix_count,
+                            const float *const *meshes, const size_t *mesh_lens) {
+    if (!c) { set_error("null context"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (n_frames < 0 || matrix_count < 0) { set_error("negative count: %d frames, %d matrix rows", n_frames, matrix_count); return GFW_ERR_INVALID_ARGUMENT; }
+    if (!planes || !params || !pixel_types || !matrices) { set_error("null clip arrays"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (nplanes < 1 || nplanes > 8) { set_error("nplanes %d", nplanes); return GFW_ERR_INVALID_ARGUMENT; }
+    if (mesh_lens && !meshes) { set_error("mesh_lens without meshes"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (meshes && !mesh_lens) { set_error("meshes without mesh_lens"); return GFW_ERR_INVALID_ARGUMENT; }
+    { const int prc = check_pixel_types(nplanes, pixel_types); if (prc != GFW_OK) return prc; }
+    // every frame's mesh is validated before anything is staged or launched: the kernels use mesh[0..2] as an offset and as loop bounds.  Consecutive frames that
+    // name the same mesh share the verdict.  In the same pass: does anything of the lens move at all?
+    bool moves = false;
+    for (int f = 0; f < n_frames; ++f) {
+        const float *m = meshes ? meshes[f] : nullptr; const size_t ml = meshes ? mesh_lens[f] : 0;
+        if (ml != 0 && !m) { set_error("frame %d: mesh of %zu values at a null pointer", f, ml); return GFW_ERR_INVALID_ARGUMENT; }
+        if (ml > GFW_MESH_MAX) { set_error("frame %d: Buffer size mismatch buf_mesh_data! %d vs %zu", f, GFW_MESH_MAX, ml); return GFW_ERR_BUFFER_SIZE_MISMATCH; }
+        if (m && ml && !(f > 0 && meshes[f - 1] == m && mesh_lens[f - 1] == ml)) {
+            const int mrc = validate_mesh(m, ml);
+            if (mrc != GFW_OK) { const std::string why = g_last_error; set_error("frame %d: %s", f, why.c_str()); return mrc; }
+        }
+        const gfw_kernel_params &p = params[(size_t)f * nplanes], &p0 = params[0];
+        moves = moves || (m && ml) || memcmp(p.f, p0.f, sizeof(p.f)) || memcmp(p.c, p0.c, sizeof(p.c)) || memcmp(p.k, p0.k, sizeof(p.k)) ||
+                memcmp(&p.r_limit, &p0.r_limit, sizeof(float)) || memcmp(&p.light_refraction_coefficient, &p0.light_refraction_coefficient, sizeof(float));
+    }
+    if (!moves) return gfw_undistort_clip_params(c, n_frames, nplanes, planes, params, pixel_types, matrices, matrix_count);
+    { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
+    ClipBatch batch;
+    batch.n_call = n_frames; batch.perframe = true; batch.lens = true;
+    for (int f = 0; f < n_frames; ++f) {
+        const float *m = meshes ? meshes[f] : nullptr; const size_t ml = (meshes && m) ? mesh_lens[f] : 0;
+        FrameIn F{nplanes, planes + (size_t)f * nplanes, params + (size_t)f * nplanes, pixel_types, matrices[f], matrix_count, ml ? m : nullptr, ml};
+        F.mesh_checked = true;
+        const int rc = run_planes(c, F, &batch);
         if (rc != GFW_OK) return clip_end(c, &batch, rc);
     }
     return clip_end(c, &batch, GFW_OK);

@@ -19,7 +19,15 @@ struct ClipBatch {
     bool perframe = false;
     GfwFramePer pf[GFW_CLIP_MAX] = {};
     double env_hx = 0.0, env_hy = 0.0;
+    // gfw_undistort_clip_lens: every frame brings its own lens and mesh as well.  Its launches take the moving-lens flavour (GFW_JIT_PERFRAME=2), ls[k] is frame k's
+    // lens slot and mesh_h[k] its mesh on the host (nullptr: none, or already on the device — a frame launched alone names the context's d_mesh); slots and
+    // meshes are staged to the device per launch (lens_stage).  The flavour takes the exact first pass, so there is no envelope.
+    bool lens = false;
+    GfwLensSlot ls[GFW_CLIP_MAX] = {};
+    const float *mesh_h[GFW_CLIP_MAX] = {};
 };
+static bool clip_lens_flavour(const ClipBatch *b) { return b && b->lens; }
+static int clip_flavour(const ClipBatch *b) { return !b ? 0 : b->lens ? 2 : b->perframe ? 1 : 0; }
 static void clip_envelope(const ClipBatch *b, double &hx, double &hy) {
     if (b && b->perframe) { hx = fmax(hx, b->env_hx); hy = fmax(hy, b->env_hy); }
 }
@@ -47,6 +55,15 @@ static GfwFramePer frame_slot(const GfwYuvArgs &Y) {
     F.fov = Y.kp.fov; F.lens_correction_amount = Y.kp.lens_correction_amount;
     F.background_margin = Y.kp.background_margin; F.background_margin_feather = Y.kp.background_margin_feather;
     F.fill_bg = Y.fill_bg; F.pad_ = 0;
+    return F;
+}
+// A frame's lens slot of a moving-lens launch: what get_lens_data_at_timestamp, the refraction keyframe and mesh_correction[frame] move (DESIGN.md section 3.2a).
+// `mesh`: as the kernel is to read it — a device address, or nullptr for lens_stage to fill in once the launch's meshes have their place
+static GfwLensSlot lens_slot(const GfwYuvArgs &Y, const float *mesh, size_t mesh_len) {
+    GfwLensSlot F;
+    memcpy(F.f, Y.f, sizeof(F.f)); memcpy(F.c, Y.c, sizeof(F.c)); memcpy(F.k, Y.k, sizeof(F.k));
+    F.r_limit_sq = Y.r_limit_sq; F.refraction = Y.kp.light_refraction_coefficient;
+    F.mesh = mesh; F.mesh_len = (Y.extras & 32) ? (int32_t)mesh_len : 0; F.pad_ = 0;
     return F;
 }
 // gfw_set_frame_checksums: the word of the next frame submitted on the context (nullptr: off)
@@ -124,12 +141,20 @@ static bool clip_same_params(const GfwYuvArgs &a, const GfwYuvArgs &b) {
 // The same for a launch of the per-frame flavour: the argument blocks must agree once the per-frame fields are blanked — in the manner of jit_for's key.  The feature
 // bits those fields select (extras: a lens-correction amount below 1, background mode 3, refraction) stay in the comparison, so a frame whose amount reaches 1.0
 // opens a new launch (the flavour's kernel is another).
-static bool clip_same_params_pf(const GfwYuvArgs &a, const GfwYuvArgs &b) {
+// `lens`: a launch of the moving-lens flavour — the lens, the refraction coefficient and the mesh are blanked as well; k_all_zero and the feature bits (refraction
+// on, a mesh present) stay, so a frame that differs there opens a new launch.
+static bool clip_same_params_pf(const GfwYuvArgs &a, const GfwYuvArgs &b, bool lens = false) {
     GfwYuvArgs x = a, y = b;
     for (GfwYuvArgs *v : {&x, &y}) {
         v->t2[0] = v->t2[1] = 0.0f; v->fill_bg = 0;
         v->kp.fov = 0.0f; v->kp.lens_correction_amount = 0.0f; v->kp.background_margin = 0.0f; v->kp.background_margin_feather = 0.0f;
         v->kp.translation2d[0] = v->kp.translation2d[1] = 0.0f; v->kp.flags &= ~GFW_FLAG_FILL_WITH_BACKGROUND;
+        if (lens) {
+            memset(v->f, 0, sizeof(v->f)); memset(v->c, 0, sizeof(v->c)); memset(v->k, 0, sizeof(v->k)); v->r_limit_sq = 0.0f;
+            memset(v->kp.f, 0, sizeof(v->kp.f)); memset(v->kp.c, 0, sizeof(v->kp.c)); memset(v->kp.k, 0, sizeof(v->kp.k)); v->kp.r_limit = 0.0f;
+            v->kp.light_refraction_coefficient = 0.0f;
+            v->common.mesh = nullptr; v->common.mesh_len = 0;
+        }
     }
     return clip_same_params(x, y);
 }
@@ -161,10 +186,41 @@ static void timeline_dump(gfw_ctx *c, hipFunction_t fn) {
             if (FILE *f = fopen((std::string(tl_file) + ".blocks").c_str(), "wb")) { fwrite(host.data(), 8, host.size(), f); fclose(f); }
     }
 }
-// One launch of the specialised kernel (the profile bracket is the caller's).  `pf`: the frames' slots (per-frame flavour) or nullptr; `sums`: used under CA.Y.checksum
-static int jit_launch(gfw_ctx *c, hipFunction_t fn, int grid, const GfwClipArgs &CA, const GfwFramePer *pf, unsigned long long *const *sums) {
+// The lens slots and the meshes of one moving-lens launch, staged through the context's ring (gfw_hostmem.h): a block of GFW_CLIP_MAX slots followed by the launch's
+// meshes, GFW_LENS_MESH_STRIDE floats apart.  Consecutive frames that name the same mesh (pointer and length) share one copy of it.  Each launch in flight has a
+// slot of the ring to itself — the host waits for a slot's last reader before it refills it —, and the copy is enqueued on the context's stream ahead of the
+// launch: a later launch's staging cannot disturb what an earlier, still-running one reads.  The caller records free_again behind the launch.
+static int lens_stage(gfw_ctx *c, int n, const GfwLensSlot *ls, const float *const *mesh_h, StagedBlock &B) {
+    HIP_TRY(c->lens_ring.acquire(GFW_LENS_BLOCK_BYTES, c->stream, &B.slot), GFW_ERR_HIP);
+    GfwLensSlot *h = (GfwLensSlot *)B.h();
+    const size_t mesh_at = GFW_CLIP_MAX * sizeof(GfwLensSlot);
+    int n_mesh = 0;
+    for (int k = 0; k < n; ++k) {
+        h[k] = ls[k];
+        if (!mesh_h || !mesh_h[k] || ls[k].mesh_len <= 0) continue;
+        if (ls[k].mesh_len > GFW_MESH_MAX) { set_error("frame %d of the launch: mesh of %d values", k, ls[k].mesh_len); return GFW_ERR_BUFFER_SIZE_MISMATCH; }
+        const bool shared = k > 0 && mesh_h[k - 1] == mesh_h[k] && ls[k - 1].mesh_len == ls[k].mesh_len;
+        if (!shared) { memcpy(B.h() + mesh_at + (size_t)n_mesh * GFW_LENS_MESH_STRIDE * sizeof(float), mesh_h[k], (size_t)ls[k].mesh_len * sizeof(float)); ++n_mesh; }
+        h[k].mesh = (const float *)(B.d() + mesh_at + (size_t)(n_mesh - 1) * GFW_LENS_MESH_STRIDE * sizeof(float));
+    }
+    for (int k = n; k < GFW_CLIP_MAX; ++k) memset(&h[k], 0, sizeof(h[k]));
+    HIP_TRY(B.upload(mesh_at + (size_t)n_mesh * GFW_LENS_MESH_STRIDE * sizeof(float), c->stream), GFW_ERR_HIP);
+    return GFW_OK;
+}
+// One launch of the specialised kernel (the profile bracket is the caller's).  `pf`: the frames' slots (per-frame flavour) or nullptr; `sums`: used under CA.Y.checksum;
+// `ls` / `mesh_h`: the frames' lens slots and host meshes (moving-lens flavour, with `pf`) or nullptr
+static int jit_launch(gfw_ctx *c, hipFunction_t fn, int grid, const GfwClipArgs &CA, const GfwFramePer *pf, unsigned long long *const *sums,
+                      const GfwLensSlot *ls = nullptr, const float *const *mesh_h = nullptr) {
     hipError_t e;
-    if (pf) {
+    if (pf && ls) {
+        StagedBlock B;
+        { const int src = lens_stage(c, CA.n_frames, ls, mesh_h, B); if (src != GFW_OK) return src; }
+        GfwClipArgsPL PL;
+        PL.PF.C = CA; memset(PL.PF.fr_pf, 0, sizeof(PL.PF.fr_pf)); memcpy(PL.PF.fr_pf, pf, (size_t)CA.n_frames * sizeof(GfwFramePer));
+        PL.lens = (const GfwLensSlot *)B.d();
+        e = gfw_jit_launch_pl(fn, PL, grid, c->stream);
+        if (e == hipSuccess) e = B.free_again(c->stream);
+    } else if (pf) {
         GfwClipArgsPF PF;
         PF.C = CA; memset(PF.fr_pf, 0, sizeof(PF.fr_pf)); memcpy(PF.fr_pf, pf, (size_t)CA.n_frames * sizeof(GfwFramePer));
         e = gfw_jit_launch_pf(fn, PF, grid, c->stream);
@@ -178,16 +234,17 @@ static int clip_flush(gfw_ctx *c, ClipBatch *b) {
     if (!b || b->n == 0) return GFW_OK;
     b->CA.n_frames = b->n; b->CA.pad_ = 0;
     prof_begin(c);
-    const int rc = jit_launch(c, b->fn, b->grid, b->CA, b->perframe ? b->pf : nullptr, b->sums);
+    const int rc = jit_launch(c, b->fn, b->grid, b->CA, b->perframe ? b->pf : nullptr, b->sums, b->lens ? b->ls : nullptr, b->mesh_h);
     prof_end(c, b->n);
     b->n = 0;
     return rc;
 }
 // A frame joins the pending launch (opened by run_planes: join_launch): its pointers, its slot in the per-frame flavour, its checksum word.  A full launch leaves.
-static int clip_append(gfw_ctx *c, ClipBatch *b, const GfwFrameDyn &D, const GfwFramePer *slot, unsigned long long *sum) {
+static int clip_append(gfw_ctx *c, ClipBatch *b, const GfwFrameDyn &D, const GfwFramePer *slot, unsigned long long *sum, const GfwLensSlot *lens = nullptr, const float *mesh_h = nullptr) {
     b->sums[b->n] = sum;
     sum_commit(c, sum);                               // the frame is part of the pending launch from here on
     if (slot) b->pf[b->n] = *slot;
+    if (lens) { b->ls[b->n] = *lens; b->mesh_h[b->n] = mesh_h; }
     b->CA.fr[b->n++] = D;
     c->last_backend = b->backend;
     return b->n >= b->limit ? clip_flush(c, b) : GFW_OK;

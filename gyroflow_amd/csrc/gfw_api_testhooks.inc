@@ -124,6 +124,35 @@ extern "C" int gfw_debug_jit_key_clip_params(int n_frames, int nplanes, const gf
     return jit_key_out(arch, jit_build_defs(Y, S, true, audit_build, nullptr), bake_header(Y, S, true), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
 }
 
+// The same for the first launch of a gfw_undistort_clip_lens call (the moving-lens flavour): `mesh_lens` as that call takes it (NULL: no frame has a mesh; the
+// meshes' contents do not enter the key, only whether frame 0 has one).  A call in which no lens field moves and no frame has a mesh answers as
+// gfw_debug_jit_key_clip_params does (audit 0).  Returns 1 (outputs untouched) where an ahead-of-time kernel would run.
+extern "C" int gfw_debug_jit_key_clip_lens(int n_frames, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params, const int *pixel_types, int distortion_model,
+                                           int digital_lens, const float *const *host_matrices, int matrix_count, int matrices_on_device, const size_t *mesh_lens, const char *arch,
+                                           char *defs_out, size_t defs_cap, char *header_out, size_t header_cap, char *name_out, size_t name_cap) {
+    if (!planes || !params || !pixel_types || !arch || n_frames < 1 || nplanes < 1 || nplanes > 4 || (!matrices_on_device && (!host_matrices || !host_matrices[0]))) {
+        set_error("bad arguments"); return GFW_ERR_INVALID_ARGUMENT; }
+    bool moves = false;
+    for (int f = 0; f < n_frames; ++f) {
+        const gfw_kernel_params &p = params[(size_t)f * nplanes], &p0 = params[0];
+        moves = moves || (mesh_lens && mesh_lens[f]) || memcmp(p.f, p0.f, sizeof(p.f)) || memcmp(p.c, p0.c, sizeof(p.c)) || memcmp(p.k, p0.k, sizeof(p.k)) ||
+                memcmp(&p.r_limit, &p0.r_limit, sizeof(float)) || memcmp(&p.light_refraction_coefficient, &p0.light_refraction_coefficient, sizeof(float));
+    }
+    if (!moves) return gfw_debug_jit_key_clip_params(n_frames, nplanes, planes, params, pixel_types, distortion_model, digital_lens, host_matrices, matrix_count, matrices_on_device, 0, arch,
+                                                     defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
+    const size_t ml0 = mesh_lens ? mesh_lens[0] : 0;
+    if (ml0 > GFW_MESH_MAX) { set_error("frame 0: mesh of %zu values", ml0); return GFW_ERR_BUFFER_SIZE_MISMATCH; }
+    gfw_ctx c;
+    c.model = distortion_model; c.digital = digital_lens; c.matrices_on_device = matrices_on_device; c.arch = arch;
+    ClipBatch batch;
+    batch.n_call = n_frames; batch.perframe = true; batch.lens = true;
+    GfwYuvArgs Y; FusedShape S;
+    static const float no_mesh[GFW_MESH_MAX] = {};      // (fused_eligible asks only whether a mesh is there)
+    { const int rc = dry_fused_args(c, n_frames, FrameIn{nplanes, planes, params, pixel_types, matrices_on_device ? nullptr : host_matrices[0], matrix_count, ml0 ? no_mesh : nullptr, ml0}, &batch, Y, S);
+      if (rc != GFW_OK) return rc; }
+    return jit_key_out(arch, jit_build_defs(Y, S, 2, false, nullptr), bake_header(Y, S, 2), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
+}
+
 extern "C" int gfw_checksum64(gfw_ctx *c, const void *d_buf, size_t bytes, unsigned long long *d_out) {
     if (!c || !d_buf || !d_out || (bytes & 7) || ((uintptr_t)d_buf & 15)) { set_error("bad checksum arguments"); return GFW_ERR_INVALID_ARGUMENT; }
     { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }

@@ -78,6 +78,14 @@ struct GfwClipArgs { GfwYuvArgs Y; int32_t n_frames; int32_t pad_; GfwFrameDyn f
 // loop's FILL_WITH_BACKGROUND).  The flavour reads them from fr_pf[frame] instead of literals or `Y.kp`; 2 224 + 16 x 32 B stays inside the 4 KB of arguments.
 struct GfwFramePer { float t2[2]; float fov, lens_correction_amount, background_margin, background_margin_feather; int32_t fill_bg; int32_t pad_; };
 struct GfwClipArgsPF { GfwClipArgs C; GfwFramePer fr_pf[GFW_CLIP_MAX]; };
+// The launch of the moving-lens flavour (GFW_JIT_PERFRAME=2 builds, gfw_undistort_clip_lens): each frame also brings its lens (FrameTransform::at_timestamp fills
+// f, c, k and r_limit from get_lens_data_at_timestamp — a zoom lens's interpolated profile, per-frame lens telemetry —, the refraction coefficient from a keyframe
+// and the mesh from mesh_correction[frame]).  A slot is 88 B: sixteen of them beside the 2 736 B above would pass the 4 KB of arguments, so the slots — and the
+// meshes they point to — live in device memory, staged per launch, and the argument block carries one pointer (2 744 B).
+struct GfwLensSlot { float f[2], c[2], k[12]; float r_limit_sq, refraction; const float *mesh; int32_t mesh_len; int32_t pad_; };
+struct GfwClipArgsPL { GfwClipArgsPF PF; const GfwLensSlot *lens; };
+#define GFW_LENS_MESH_STRIDE 840                                          // floats between the meshes of a launch's staged block (GFW_MESH_MAX, rounded up to 16 bytes)
+#define GFW_LENS_BLOCK_BYTES (GFW_CLIP_MAX * sizeof(GfwLensSlot) + (size_t)GFW_CLIP_MAX * GFW_LENS_MESH_STRIDE * sizeof(float))
 
 #if !defined(GFW_JIT) || !GFW_JIT
 int gfw_yuv_rows_per_lane(bool fast1, int tune_rb);

@@ -113,9 +113,24 @@
 #ifndef GFW_JIT_PERFRAME
 #define GFW_JIT_PERFRAME 0       // 1 (baked builds only): the per-frame flavour of gfw_undistort_clip_params — translation2d, fov, lens_correction_amount, background
                                  // margin and feather and FILL_WITH_BACKGROUND come from the current frame's slot of the launch (GfwClipArgsPF.fr_pf), not literals or Y.kp
+                                 // 2 (gfw_undistort_clip_lens): a superset of 1 — the lens moves per frame as well (a zoom lens, per-frame lens telemetry, a mesh per
+                                 // frame): f, c, k[0..11], r_limit_sq, the refraction coefficient and the mesh come from the current frame's lens slot, an array in
+                                 // device memory that the argument block points to (GfwClipArgsPL.lens), loaded where the tile walk changes frame
 #endif
 #if GFW_JIT_PERFRAME && !GFW_BAKE
 #error "GFW_JIT_PERFRAME is a flavour of the run-time specialised (baked) build"
+#endif
+#if GFW_JIT_PERFRAME >= 2 && GFW_JIT_FAST1
+#error "the moving-lens flavour takes the exact first pass: the certified pass's table and envelope are functions of the lens"
+#endif
+#define GFW_LENS_PF (GFW_JIT_PERFRAME >= 2)
+// The lens slots are written before the launch and never during it: read through the constant address space, a wave-uniform index gives scalar loads
+#if GFW_LENS_PF && defined(__HIP_DEVICE_COMPILE__)
+typedef const __attribute__((address_space(4))) GfwLensSlot *GfwLensSlots;
+#define GFW_LENS_SLOTS(p) ((GfwLensSlots)(p))
+#else
+typedef const GfwLensSlot *GfwLensSlots;
+#define GFW_LENS_SLOTS(p) (p)
 #endif
 #ifndef GFW_TLB
 #define GFW_TLB(k) do {} while (0)
@@ -307,7 +322,31 @@ struct LeanOps {
 // Lens + per-plane uniforms, VGPR-resident for the pixel loops.
 struct Lens {
     float f0, f1, c0, c1, k0, k1, k2, k3, t2x, t2y, rl2;
+#if GFW_LENS_PF
+    float kx[8], refr;                // the moving-lens flavour: k[4..11], the refraction coefficient and the mesh of the current frame (its lens slot)
+    const float *mesh; int mesh_len;
+#endif
 };
+// Plane 0's KernelParams and the shared block as the lens routines of gfw_warp.h take them.  The moving-lens flavour overlays the current frame's lens on copies
+// (every index a literal: the copies are registers, and only the fields a body reads are ever loaded); every other build hands the argument block's own on.
+#if GFW_LENS_PF
+__device__ __forceinline__ gfw_kernel_params gfw_lens_kp(const gfw_kernel_params &P, const Lens &L) {
+    gfw_kernel_params K = P;
+    K.f[0] = L.f0; K.f[1] = L.f1; K.c[0] = L.c0; K.c[1] = L.c1;
+    K.k[0] = L.k0; K.k[1] = L.k1; K.k[2] = L.k2; K.k[3] = L.k3;
+    K.k[4] = L.kx[0]; K.k[5] = L.kx[1]; K.k[6] = L.kx[2]; K.k[7] = L.kx[3]; K.k[8] = L.kx[4]; K.k[9] = L.kx[5]; K.k[10] = L.kx[6]; K.k[11] = L.kx[7];
+    K.light_refraction_coefficient = L.refr;
+    return K;
+}
+__device__ __forceinline__ GfwCommon gfw_lens_common(const GfwCommon &C, const Lens &L) {
+    GfwCommon K = C;
+    K.mesh = L.mesh; K.mesh_len = L.mesh_len;
+    return K;
+}
+#define GFW_LENS_KP(A, L) const gfw_kernel_params KP = gfw_lens_kp((A).kp, L); const GfwCommon CM = gfw_lens_common((A).common, L)
+#else
+#define GFW_LENS_KP(A, L) const gfw_kernel_params &KP = (A).kp; const GfwCommon &CM = (A).common
+#endif
 struct Maps {                       // source_rect maps: u * mul / den  (den, rcp shared by luma and chroma)
     float mul_lx, mul_ly, mul_cx, mul_cy, den_x, rcp_x, den_y, rcp_y;
 };
@@ -367,6 +406,7 @@ __device__ __forceinline__ GfwPt rd(float px, float py, const float4 ma, const f
     const float Y = (px * ma.w) + (py * mb.x) + mb.y;
     const float W = (px * mb.z) + (py * mb.w) + m8;
     GfwPt o{0.0f, 0.0f, false};
+    GFW_LENS_KP(A, L);
     if (MODEL == GFW_MODEL_OPENCV_FISHEYE) {
         // proven operand range of the lean divide: |X|,|Y| <= 2^19, W in [2^-20, 2^20]  (=> |a|,|b| <= 2^39).  The range test subsumes the
         // reference's `w > 0` (:137), so the usual pixel pays one test; everything else — non-positive or tiny W, huge operands, NaN —
@@ -389,7 +429,7 @@ __device__ __forceinline__ GfwPt rd(float px, float py, const float4 ma, const f
         // instantiation); same position in the chain — after `+ c` — and the reference's own arithmetic (gfw_warp.h)
         if (AF(extras) & 2) {
             float d0, d1;
-            gfw_lens::distort<GFW_BK_digital>(GFW_BK_digital, o.x, o.y, 1.0f, A.kp, A.common, d0, d1);
+            gfw_lens::distort<GFW_BK_digital>(GFW_BK_digital, o.x, o.y, 1.0f, KP, CM, d0, d1);
             o.x = d0; o.y = d1;
         }
 #endif
@@ -402,12 +442,12 @@ __device__ __forceinline__ GfwPt rd(float px, float py, const float4 ma, const f
         float Wd = W;
         if ((AF(extras) & 4) && W != 0.0f) {
             const float r = sqrtf(X * X + Y * Y) / W;
-            const float sin_theta_d = (r / sqrtf(1.0f + r * r)) * A.kp.light_refraction_coefficient;
+            const float sin_theta_d = (r / sqrtf(1.0f + r * r)) * KP.light_refraction_coefficient;
             const float r_d = sin_theta_d / sqrtf(1.0f - sin_theta_d * sin_theta_d);
             if (r_d != 0.0f) Wd *= r / r_d;
         }
         float du, dv;
-        gfw_lens::distort<(MODEL == GFW_MODEL_GENERIC_EXTRA ? -1 : MODEL)>(AF(model), X, Y, Wd, A.kp, A.common, du, dv);
+        gfw_lens::distort<(MODEL == GFW_MODEL_GENERIC_EXTRA ? -1 : MODEL)>(AF(model), X, Y, Wd, KP, CM, du, dv);
         float u = du * L.f0, v = dv * L.f1;
         if (AF(extras) & 1) {
             const float m9 = ext[1], m10 = ext[2], m11 = ext[3], m12 = ext[4], m13 = ext[5];
@@ -419,10 +459,10 @@ __device__ __forceinline__ GfwPt rd(float px, float py, const float4 ma, const f
             }
         }
         u = u + L.c0; v = v + L.c1;
-        if (MODEL == GFW_MODEL_GENERIC_EXTRA && (AF(extras) & 32)) gfw_mesh_apply(u, v, A.kp, A.common);   // Sony mesh + focal-plane distortion (:169-214)
+        if (MODEL == GFW_MODEL_GENERIC_EXTRA && (AF(extras) & 32)) gfw_mesh_apply(u, v, KP, CM);   // Sony mesh + focal-plane distortion (:169-214)
         if (AF(extras) & 2) {
             float d0, d1;
-            gfw_lens::distort<GFW_BAKED_DIGITAL_MODEL>(GFW_CLIP_DIGITAL, u, v, 1.0f, A.kp, A.common, d0, d1);
+            gfw_lens::distort<GFW_BAKED_DIGITAL_MODEL>(GFW_CLIP_DIGITAL, u, v, 1.0f, KP, CM, d0, d1);
             u = d0; v = d1;
         }
         o.x = u; o.y = v;
@@ -1293,8 +1333,9 @@ namespace {
 // other argument, so a launch can carry several of them and the occupancy tail of one frame is filled by the next (the effect two
 // HIP streams showed: 79.3 -> 71.7 us per C2 frame, profiles/r03_ab_northstar.txt) without a second stream or a second launch.
 // `fr_pf` (GFW_JIT_PERFRAME builds only): the frames' per-frame KernelParams fields, indexed by frame like clip->fr (never tested, for the reason given for `clip`).
+// `fr_lens` (GFW_JIT_PERFRAME = 2 builds only): the frames' lens slots in device memory, indexed the same way.
 template <int MODEL, typename T, int N0, int I, int DW, int DH, bool INTERLEAVED_UV, int RB, bool FAST1, bool AUDIT>
-__device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwClipArgs *clip, const GfwFramePer *fr_pf = nullptr) {
+__device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwClipArgs *clip, const GfwFramePer *fr_pf = nullptr, GfwLensSlots fr_lens = nullptr) {
     // A baked build (run time, gfw_jit.hip) reads every clip-invariant argument as a literal from the bake header (AF(x) = GFW_BK_x): the
     // loads, the uniform branches and the scalar registers they pin disappear — the reference bakes its per-clip constants into the
     // OpenCL source it compiles per clip the same way (opencl.rs:181-214).  Pointers and the per-frame fields stay arguments.
@@ -1428,9 +1469,28 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
 
     // uniform floats of the pixel loops
     Lens L;
+#if GFW_LENS_PF
+    // the current frame's lens, from its slot (wave-uniform: scalar loads; frame 0 here, the next frame's where the tile walk changes frame)
+    auto load_lens = [&](int fi) {
+        L.f0 = fr_lens[fi].f[0]; L.f1 = fr_lens[fi].f[1]; L.c0 = fr_lens[fi].c[0]; L.c1 = fr_lens[fi].c[1];
+        L.k0 = fr_lens[fi].k[0]; L.k1 = fr_lens[fi].k[1]; L.k2 = fr_lens[fi].k[2]; L.k3 = fr_lens[fi].k[3];
+        L.rl2 = fr_lens[fi].r_limit_sq;
+        if (MODEL != GFW_MODEL_OPENCV_FISHEYE) {     // (the lean body reads four coefficients and neither refraction nor a mesh)
+            L.kx[0] = fr_lens[fi].k[4]; L.kx[1] = fr_lens[fi].k[5]; L.kx[2] = fr_lens[fi].k[6]; L.kx[3] = fr_lens[fi].k[7];
+            L.kx[4] = fr_lens[fi].k[8]; L.kx[5] = fr_lens[fi].k[9]; L.kx[6] = fr_lens[fi].k[10]; L.kx[7] = fr_lens[fi].k[11];
+            L.refr = fr_lens[fi].refraction;
+        } else { L.kx[0] = L.kx[1] = L.kx[2] = L.kx[3] = L.kx[4] = L.kx[5] = L.kx[6] = L.kx[7] = 0.0f; L.refr = 1.0f; }
+        if (MODEL == GFW_MODEL_GENERIC_EXTRA && (AF(extras) & 32)) { L.mesh = (const float *)fr_lens[fi].mesh; L.mesh_len = fr_lens[fi].mesh_len; }
+        else { L.mesh = nullptr; L.mesh_len = 0; }
+    };
+    load_lens(0);
+    L.t2x = fr_pf[0].t2[0]; L.t2y = fr_pf[0].t2[1];
+#else
     L.f0 = AFA(f, 0); L.f1 = AFA(f, 1); L.c0 = AFA(c, 0); L.c1 = AFA(c, 1);
     L.k0 = AFA(k, 0); L.k1 = AFA(k, 1); L.k2 = AFA(k, 2); L.k3 = AFA(k, 3);
-#if GFW_JIT_PERFRAME
+#endif
+#if GFW_LENS_PF
+#elif GFW_JIT_PERFRAME
     L.t2x = fr_pf[0].t2[0]; L.t2y = fr_pf[0].t2[1]; L.rl2 = AF(r_limit_sq);
 #else
     L.t2x = AFA(t2, 0); L.t2y = AFA(t2, 1); L.rl2 = AF(r_limit_sq);
@@ -1612,6 +1672,9 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
             fr_fill = fr_pf[fi].fill_bg != 0;
             two_pass = two_pass_clip && !fr_fill;
 #endif
+#if GFW_LENS_PF
+            load_lens(fi);
+#endif
             if (two_pass) {
                 load_mid();
                 if (FAST1) p1_bound(fi);
@@ -1767,7 +1830,7 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
                     int sy = 0;
                     if (live) {
                         float ox = (float)lx + L.t2x, oy = (float)ly + L.t2y;
-                        if (MODEL != GFW_MODEL_OPENCV_FISHEYE && (AF(extras) & 8)) gfw_lens_correction_blend<(MODEL == GFW_MODEL_GENERIC_EXTRA ? -1 : MODEL)>(ox, oy, A.kp, A.common, AF(model), GFW_CLIP_DIGITAL, GFW_FR_FOV, GFW_FR_AMOUNT);   // :429-460
+                        if (MODEL != GFW_MODEL_OPENCV_FISHEYE && (AF(extras) & 8)) { GFW_LENS_KP(A, L); gfw_lens_correction_blend<(MODEL == GFW_MODEL_GENERIC_EXTRA ? -1 : MODEL)>(ox, oy, KP, CM, AF(model), GFW_CLIP_DIGITAL, GFW_FR_FOV, GFW_FR_AMOUNT); }   // :429-460
                         sy = pass1_exact<MODEL>(ox, oy, M, matrices, L, A);
                     }
                     srow(r * NPX + k, tid) = (unsigned short)(live ? min(sy, AF(matrix_count) - 1) : 0);
@@ -1973,7 +2036,7 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
                     const int lx = cx * DW + i, ly = cy * DH + j;
                     if (!WHOLE && (lx >= AF(out_w) || ly >= AF(out_h))) continue;
                     float ox = (float)lx + L.t2x, oy = (float)ly + L.t2y;
-                    if (MODEL != GFW_MODEL_OPENCV_FISHEYE && (AF(extras) & 8)) gfw_lens_correction_blend<(MODEL == GFW_MODEL_GENERIC_EXTRA ? -1 : MODEL)>(ox, oy, A.kp, A.common, AF(model), GFW_CLIP_DIGITAL, GFW_FR_FOV, GFW_FR_AMOUNT);       // :429-460
+                    if (MODEL != GFW_MODEL_OPENCV_FISHEYE && (AF(extras) & 8)) { GFW_LENS_KP(A, L); gfw_lens_correction_blend<(MODEL == GFW_MODEL_GENERIC_EXTRA ? -1 : MODEL)>(ox, oy, KP, CM, AF(model), GFW_CLIP_DIGITAL, GFW_FR_FOV, GFW_FR_AMOUNT); }       // :429-460
                     const int sy = two_pass_clip ? (int)srow(r * NPX + k, tid) : default_row<MODEL>(ox, oy, A);      // (two_pass: already clamped to the table; the min below is then idle)
                     GfwPt p;
                     if (GFW_ABL(8)) { p.x = ox * 0.5f; p.y = oy * 0.5f; p.ok = true; }              // timing ablation only
@@ -2152,9 +2215,16 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
 #endif
 #if GFW_JIT_PERFRAME
 // the per-frame flavour: the launch's argument block carries a slot per frame (GfwClipArgsPF); the body indexes the slot array, never takes `&C` of a field it copies
+#if GFW_LENS_PF
+// the moving-lens flavour: the per-frame flavour's block and the address of the launch's lens slots
+extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GFW_JIT_WAVES, 8))) void gfw_jit_kernel(const GfwClipArgsPL C) {
+    gfw_yuv_body<GFW_JIT_MODEL, GFW_JIT_T, GFW_JIT_N0, GFW_FRAME_TAPS, GFW_JIT_DW, GFW_JIT_DH, (GFW_JIT_IL != 0), GFW_JIT_RB, false, (GFW_JIT_AUDIT != 0)>(C.PF.C.Y, &C.PF.C, C.PF.fr_pf, GFW_LENS_SLOTS(C.lens));
+}
+#else
 extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GFW_JIT_WAVES, 8))) void gfw_jit_kernel(const GfwClipArgsPF C) {
     gfw_yuv_body<GFW_JIT_MODEL, GFW_JIT_T, GFW_JIT_N0, GFW_FRAME_TAPS, GFW_JIT_DW, GFW_JIT_DH, (GFW_JIT_IL != 0), GFW_JIT_RB, (GFW_JIT_FAST1 != 0), (GFW_JIT_AUDIT != 0)>(C.C.Y, &C.C, C.fr_pf);
 }
+#endif
 #else
 extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GFW_JIT_WAVES, 8))) void gfw_jit_kernel(const GfwClipArgs C) {
     gfw_yuv_body<GFW_JIT_MODEL, GFW_JIT_T, GFW_JIT_N0, GFW_FRAME_TAPS, GFW_JIT_DW, GFW_JIT_DH, (GFW_JIT_IL != 0), GFW_JIT_RB, (GFW_JIT_FAST1 != 0), (GFW_JIT_AUDIT != 0)>(C.Y, &C);

@@ -644,6 +644,34 @@ class ClipParamsCall(ClipCall):
         self.fn = backend.lib.gfw_undistort_clip_params
 
 
+class ClipLensCall(ClipParamsCall):
+    """Pre-marshalled ``gfw_undistort_clip_lens`` call: as ``ClipParamsCall``, for a clip whose lens (f, c, k, r_limit), refraction coefficient and mesh move
+    per frame as well.  ``meshes``: ``None``, or one entry per frame — ``None`` or the frame's ``mesh_correction`` block (f32, at most 839 values)."""
+
+    def __init__(self, backend, frames, params, pixel_types, matrices, matrix_count=None, meshes=None):
+        super().__init__(backend, frames, params, pixel_types, matrices, matrix_count)
+        self.fn = backend.lib.gfw_undistort_clip_lens
+        self.mesh_keep, self.mesh_ptrs, self.mesh_lens = [], None, None
+        if meshes is not None:
+            if len(meshes) != self.nf:
+                raise ValueError("meshes: one entry (or None) per frame")
+            ptrs, lens, last = [], [], (None, None)
+            for m in meshes:
+                if m is None or len(m) == 0:
+                    ptrs.append(None); lens.append(0)
+                    continue
+                if m is not last[0]:                          # (the same object on consecutive frames: one array, one pointer — the library uploads it once)
+                    last = (m, np.ascontiguousarray(m, dtype=np.float32))
+                    self.mesh_keep.append(last[1])
+                ptrs.append(last[1].ctypes.data); lens.append(last[1].size)
+            self.mesh_ptrs, self.mesh_lens = (C.c_void_p * self.nf)(*ptrs), (C.c_size_t * self.nf)(*lens)
+
+    def __call__(self):
+        rc = self.fn(self.be.ctx, self.nf, self.n, self.barr, self.parr, self.tarr, self.marr, self.mc, self.mesh_ptrs, self.mesh_lens)
+        if rc != 0:
+            self.be._check(rc)
+
+
 def run_plane(src, in_size, dst, out_size, params, pixel_type, model, digital, matrices, mesh=None, **rects):
     """Convenience: create a backend, warp one HOST plane in place into ``dst``."""
     b = host_buffers(src, in_size, dst, out_size, **rects)

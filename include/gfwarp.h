@@ -277,6 +277,28 @@ int gfw_undistort_clip_params(gfw_ctx *ctx, int n_frames, int nplanes,
                               const gfw_kernel_params *params,
                               const int *pixel_types,
                               const float *const *matrices, int matrix_count);
+/* The same frame loop for a clip whose LENS moves from frame to frame as well — FrameTransform::at_timestamp fills f, c, k[12] and r_limit from
+ * get_lens_data_at_timestamp (frame_transform.rs:82-163: the interpolated profile of a zoom lens, the per-frame focal length, principal point and
+ * distortion coefficients of Sony / RED / BRAW telemetry), light_refraction_coefficient from a keyframe and mesh_data from mesh_correction[frame].
+ * `meshes` is NULL or holds n_frames pointers, frame f's mesh_correction[frame].1 as f32 (NULL: that frame has none); `mesh_lens` is NULL with `meshes`
+ * NULL, else the meshes' lengths in floats (0: none; at most 839).  Every mesh is validated on the host before anything is staged or launched;
+ * consecutive frames that name the same pointer and length share one validation and one upload.
+ * Results are bit-identical to n_frames ordered gfw_undistort_frame calls, each given its own frame's params and mesh.  Ordering, overlap,
+ * synchronous-default, checksum-ring, launch-size and error behaviour are those of gfw_undistort_clip_params.  Frames share launches when they differ
+ * only in what that call lets move, in f, c, k[0..11], r_limit, light_refraction_coefficient and in the CONTENTS of their meshes; a frame that differs
+ * in anything the kernel is compiled for (sizes, strides, pixel types, lens model ids, interpolation, background mode, stretches, rotation, whether a
+ * mesh is present, whether refraction is on, whether k[0..3] are all zero, ...) starts a new launch.  These launches take the exact first pass.  A frame
+ * the fused kernel does not serve (a mesh with input_rotation, EWA, host buffers) goes out on its own behind the pending ones, as gfw_undistort_frame
+ * would send it.  A call in which none of the lens fields moves and no frame has a mesh IS gfw_undistort_clip_params.
+ * Rejected before any output is touched or anything enqueued, gfw_last_error() naming the frame: negative counts, mesh_lens without meshes (or the
+ * reverse), a length with a NULL pointer (GFW_ERR_INVALID_ARGUMENT); a length above 839, a malformed mesh header (GFW_ERR_BUFFER_SIZE_MISMATCH). */
+int gfw_undistort_clip_lens(gfw_ctx *ctx, int n_frames, int nplanes,
+                            const gfw_buffers *planes,
+                            const gfw_kernel_params *params,
+                            const int *pixel_types,
+                            const float *const *matrices, int matrix_count,
+                            const float *const *meshes,
+                            const size_t *mesh_lens);
 
 /* ---- options / stream ---------------------------------------------------*/
 enum {

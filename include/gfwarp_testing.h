@@ -39,6 +39,12 @@ int   gfw_debug_jit_key(int nplanes, const gfw_buffers *planes, const gfw_kernel
 int   gfw_debug_jit_key_clip_params(int n_frames, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params, const int *pixel_types, int distortion_model,
                                     int digital_lens, const float *const *host_matrices, int matrix_count, int matrices_on_device, int audit, const char *arch,
                                     char *defs_out, size_t defs_cap, char *header_out, size_t header_cap, char *name_out, size_t name_cap);
+/* The same for the first launch of a gfw_undistort_clip_lens call (the moving-lens flavour): mesh_lens as that call takes it, or NULL (the contents of a mesh do
+ * not enter the key, only whether frame 0 has one).  A call in which no lens field moves and no frame has a mesh answers as gfw_debug_jit_key_clip_params
+ * with audit = 0. */
+int   gfw_debug_jit_key_clip_lens(int n_frames, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params, const int *pixel_types, int distortion_model,
+                                  int digital_lens, const float *const *host_matrices, int matrix_count, int matrices_on_device, const size_t *mesh_lens, const char *arch,
+                                  char *defs_out, size_t defs_cap, char *header_out, size_t header_cap, char *name_out, size_t name_cap);
 
 /* Identity of the fused kernel's source this library was built from (length and 128-bit hash of the text it embeds for run-time specialisation; the ahead-of-time
  * kernels are compiled from the same files): measurements stored beside the repository (profiles/ *_traffic.json) name the source they were taken on, and bench.py
