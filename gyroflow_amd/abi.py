@@ -115,6 +115,14 @@ class SyncResult(C.Structure):
                 ("value", C.c_double), ("cost", C.c_double)]
 
 
+class PoseAlmeidaCfg(C.Structure):
+    """``gfw_pose_almeida_cfg``: what every pair of an Almeida pose estimation call shares."""
+    _fields_ = [("video_width", C.c_int32), ("video_height", C.c_int32), ("flow_width", C.c_int32), ("flow_height", C.c_int32),
+                ("num_iters", C.c_int32), ("num_samples", C.c_int32), ("inlier_angle_deg", C.c_float), ("reserved", C.c_int32),
+                ("camera_matrix", C.c_double * 9)]
+
+
+POSE_PAIR_POINTS_MAX, POSE_PAIRS_MAX, POSE_ROUNDS_MAX = 4096, 65535, 1024      # gfw_pose_almeida
 SYNC_FINE_CANDIDATES = 200       # the second stage's candidates
 SYNC_PAIR_POINTS_MAX = 4096
 SYNC_GYRO_RANGES_MAX, SYNC_GYRO_EST_MAX, SYNC_GYRO_SAMPLES_MAX, SYNC_GYRO_CANDIDATES_MAX = 65535, 65536, 1 << 22, 2000000      # gfw_sync_gyro_*: per call / per range
@@ -210,6 +218,8 @@ def bind(lib):
     lib.gfw_optim_resample.argtypes = [vp, vp, vp, i32, vp, C.c_int64, vp, vp]; lib.gfw_optim_resample.restype = i32
     lib.gfw_sync_optim_rank.argtypes = [vp, vp, C.c_int64, C.c_double, vp, vp, vp, vp, vp, i32]; lib.gfw_sync_optim_rank.restype = i32
     lib.gfw_sync_optim_points.argtypes = [vp, vp, C.c_int64, C.c_double, i32, vp, i32, vp, vp, vp, vp, vp, i32]; lib.gfw_sync_optim_points.restype = i32
+    lib.gfw_pose_almeida.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(PoseAlmeidaCfg), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_pose_almeida.restype = i32
+    lib.gfw_pose_draws.argtypes = [C.c_uint64, vp, i32, i32, i32, vp, vp, vp]; lib.gfw_pose_draws.restype = i32
     lib.gfw_pack_matrices.argtypes = [vp, i32, vp]; lib.gfw_pack_matrices.restype = i32
     lib.gfw_checksum64.argtypes = [vp, vp, sz, vp]; lib.gfw_checksum64.restype = i32
     lib.gfw_set_frame_checksums.argtypes = [vp, vp, sz]; lib.gfw_set_frame_checksums.restype = i32
@@ -238,7 +248,8 @@ EXPORTS = ["gfw_abi_version", "gfw_list_devices", "gfw_set_device", "gfw_get_inf
            "gfw_debug_jit_key_clip_params", "gfw_undistort_clip_lens", "gfw_debug_jit_key_clip_lens", "gfw_zoom_fovs", "gfw_zoom_smooth",
            "gfw_build_matrices_batch_stab", "gfw_zoom_fovs_stab", "gfw_sync_visual_costs", "gfw_sync_visual_search",
            "gfw_lowpass_gyro", "gfw_sync_gyro_costs", "gfw_sync_gyro_search",
-           "gfw_optim_tables", "gfw_optim_resample", "gfw_sync_optim_rank", "gfw_sync_optim_points"]
+           "gfw_optim_tables", "gfw_optim_resample", "gfw_sync_optim_rank", "gfw_sync_optim_points",
+           "gfw_pose_almeida", "gfw_pose_draws"]
 
 
 def load_library(path=None):

@@ -26,11 +26,13 @@
 #include "gfw_sync.h"
 #include "gfw_sync_gyro.h"
 #include "gfw_sync_optim.h"
+#include "gfw_pose.h"
 #include "gfw_matrices_host.h"
 #include "gfw_zoom_host.h"
 #include "gfw_sync_host.h"
 #include "gfw_sync_gyro_host.h"
 #include "gfw_sync_optim_host.h"
+#include "gfw_pose_host.h"
 #include "gfw_jit.h"
 #include <stdlib.h>
 #include <map>
@@ -120,6 +122,9 @@ struct gfw_ctx {
     // gfw_sync_optim_*: the gyro series as f32, the window, the twiddle table and the trim ranges staged the same way (work space: the visual search's)
     static constexpr int kOptimSlots = 2;
     StagingRing<kOptimSlots> optim_ring;
+    // gfw_pose_almeida: pair firsts, points and draws staged the same way (work space: the visual search's)
+    static constexpr int kPoseSlots = 2;
+    StagingRing<kPoseSlots> pose_ring;
     // context-owned per-row tables built on the device (gfw_build_matrices): a small ring, built on copy_stream so that
     // frame N+1's table is produced while frame N is being warped; events order builder and consumer both ways
     struct BuiltSlot { DevBuf buf; Event built, consumed; };   // buf = rows + 4 doubles of builder scratch
@@ -1023,3 +1028,4 @@ int gfw_undistort_clip_lens(gfw_ctx *c, int n_frames, int nplanes, const gfw_buf
 #include "gfw_api_zoom.inc"
 #include "gfw_api_sync.inc"
 #include "gfw_api_sync_optim.inc"
+#include "gfw_api_pose.inc"

@@ -10,7 +10,7 @@ range is ONE device call, ``Backend.sync_visual_search`` (gfw_sync_visual_search
 The 90 %-of-range acceptance rule (:137) and the range's middle timestamp are applied here.
 
 Not covered: clips with per-frame time offsets, stabiliser data or lens meshes, keyframed lens data or video rotation inside a range,
-suppress_rotation; the optical flow that produces the matched points, pose estimation, rs_sync itself.
+suppress_rotation; the optical flow that produces the matched points, rs_sync itself.
 
     offsets = synchronization.find_offsets_essential(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params, backend)
     initial_offset, search_size = synchronization.initial_offset_fast(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params, backend)
@@ -18,7 +18,14 @@ suppress_rotation; the optical flow that produces the matched points, pose estim
 ``find_offsets`` of essential_matrix.rs:13-91 matches the angular rates pose estimation produced against the gyro's, per range over
 ``2 * search_size`` coarse and 200 fine candidate offsets; here ALL ranges are one device call, ``Backend.sync_gyro_search`` (gfw_sync_gyro_search).  The guards,
 the range cut, the gyro window, the max-angle skip, the two 20 Hz low-pass calls (``warp.lowpass_gyro``), the 90 % rule and the middle timestamp are applied
-here.  The estimated rates are the caller's input: pose estimation is not covered.
+here.  The estimated rates are the caller's input: ``estimated_gyro`` makes them of the rotations of ``estimate_poses_almeida``.
+
+    poses = synchronization.estimate_poses_almeida(compute_params, pairs, backend, seed=0)
+    gyro = synchronization.estimated_gyro({ts_us: pose and pose["euler"]}, fps, lpf, final_pass)
+
+``PoseAlmeida`` (estimate_pose/almeida.rs): one camera rotation per pair of frames from its matched optical-flow points, ALL pairs in one device call,
+``Backend.pose_almeida`` (gfw_pose_almeida).  The reference draws its RANSAC rounds from an unseeded generator; here a seed decides them.  The other three pose
+methods are not covered.
 
     optim = synchronization.OptimSync.new(raw_imu)
     points_ms, rank, ratio = optim.run(target_sync_points, trim_ranges_s, backend)
@@ -166,6 +173,85 @@ def initial_offset_fast(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges
         if offsets:
             return median_offset(o for _, o, _ in offsets), 3000.0
     return sync_params.initial_offset, sync_params.search_size
+
+
+def scaled_axis(rot):
+    """``Rotation3::scaled_axis``: the axis (from the skew part, normalised; none when its norm is not above the f64 epsilon) times the angle acos((trace - 1) / 2)"""
+    m = np.asarray(rot, dtype=np.float64).reshape(3, 3)
+    axis = np.array([m[2, 1] - m[1, 2], m[0, 2] - m[2, 0], m[1, 0] - m[0, 1]])
+    norm = float(np.sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]))
+    if not norm > np.finfo(np.float64).eps:
+        return np.zeros(3)
+    angle = float(np.arccos(min(max((m[0, 0] + m[1, 1] + m[2, 2] - 1.0) / 2.0, -1.0), 1.0)))
+    return axis / norm * angle
+
+
+def pose_inputs(compute_params, flow_size, num_iters=200, num_samples=1000, inlier_angle=0.05):
+    """What gfw_pose_almeida takes for these parameters: (KernelParams, abi.PoseAlmeidaCfg).  The camera matrix is the lens profile's at the clip's size
+    (get_lens_data_at_timestamp(..).0): one call per lens."""
+    cp = compute_params
+    kp = S.base_kernel_params(cp.lens, 1.0, 1, digital_lens_params=list(cp.digital_lens_params),
+                              light_refraction_coefficient=cp.light_refraction_coefficient)      # undistort_points(.., 1.0, 1.0, ..): cpu_undistort.rs:671-683
+    kp.width, kp.height, kp.output_width, kp.output_height = cp.width, cp.height, cp.output_width, cp.output_height
+    cfg = abi.PoseAlmeidaCfg(video_width=cp.width, video_height=cp.height, flow_width=int(flow_size[0]), flow_height=int(flow_size[1]),
+                             num_iters=int(num_iters), num_samples=int(num_samples), inlier_angle_deg=float(inlier_angle))
+    K = (float(kp.f[0]), 0.0, float(kp.c[0]), 0.0, float(kp.f[1]), float(kp.c[1]), 0.0, 0.0, 1.0)
+    for i, v in enumerate(K):
+        cfg.camera_matrix[i] = v
+    return kp, cfg
+
+
+def estimate_poses_almeida(compute_params, pairs, backend, seed=0, flow_size=None, every_nth_frame=1, num_iters=200, num_samples=1000):
+    """``PoseEstimator::process_detected_frames`` (synchronization/mod.rs:110-167) with the Almeida method for all frame pairs in ONE device call
+    (``Backend.pose_almeida``).  ``pairs``: one entry per frame pair in order — None (the optical flow found no lines: no rotation, :141) or
+    (points_a [n][2], points_b [n][2]) optical-flow pixels of an image of ``flow_size`` (default: the clip's size).  The reference draws a round's points from an
+    unseeded generator; here ``seed`` decides them (``warp.pose_draws``).  Returns one entry per pair: None, or dict(rotation f64 [3][3], quat f32 [4] (w, i, j, k),
+    euler = scaled_axis(rotation) * (scaled_fps / every_nth_frame), inliers, round)."""
+    from . import warp
+    cp = compute_params
+    live = [i for i, p in enumerate(pairs) if p is not None]
+    out = [None] * len(pairs)
+    if not live:
+        return out
+    kp, cfg = pose_inputs(cp, flow_size or (cp.width, cp.height), num_iters, num_samples)
+    sets = [pairs[i] for i in live]
+    triples, samples = warp.pose_draws(seed, [len(np.asarray(a).reshape(-1, 2)) for a, _ in sets], cfg.num_iters, cfg.num_samples)
+    quats, rotations, best = backend.pose_almeida(kp, cfg, sets, triples, samples)
+    for k, i in enumerate(live):
+        out[i] = dict(rotation=rotations[k], quat=quats[k], euler=tuple(scaled_axis(rotations[k]) * (cp.scaled_fps / float(every_nth_frame))),
+                      inliers=int(best[k, 0]), round=int(best[k, 1]))
+    return out
+
+
+def estimated_gyro(results, fps, lpf=0.0, final_pass=False):
+    """The host part of ``recalculate_gyro_data`` (synchronization/mod.rs:269-361) -> {timestamp_us: (timestamp_ms, (x, y, z))}, what ``find_offsets_essential``
+    takes.  ``results``: {frame timestamp_us: euler (x, y, z) or None} — every analysed frame, also those without a rotation: a sample sits midway to the NEXT
+    analysed frame.  ``final_pass`` interpolates a missing rotation linearly between its neighbours that have one; ``lpf`` > 0 (Hz) runs gfw_lowpass_gyro."""
+    from . import warp
+    keys = sorted(results)
+    gyro = {}
+    for n, k in enumerate(keys):
+        eul = results[k]
+        if final_pass and eul is None:
+            prev = next((p for p in reversed(keys[:n]) if results[p] is not None), None)
+            nxt = next((p for p in keys[n:] if results[p] is not None), None)
+            if prev is not None and nxt is not None:
+                ratio = float(k - prev) / float(nxt - prev)
+                eul = tuple(a + (b - a) * ratio for a, b in zip(results[prev], results[nxt]))
+        if eul is None:
+            continue
+        ts = float(k) / 1000.0
+        if n + 1 < len(keys):
+            ts += (float(keys[n + 1]) / 1000.0 - ts) / 2.0
+        v = ts * 1000.0
+        ts_us = int(np.floor(abs(v) + 0.5) * (1.0 if v >= 0.0 else -1.0))                                # f64::round: halves away from zero
+        gyro[ts_us] = (ts, (eul[1] * 180.0 / np.pi, eul[0] * 180.0 / np.pi, eul[2] * 180.0 / np.pi))   # x and y swapped, degrees
+    if lpf > 0.0 and fps > 0.0 and gyro:
+        order = sorted(gyro)
+        xyz, _applied = warp.lowpass_gyro(lpf, fps, np.array([gyro[k][1] for k in order], dtype=np.float64))
+        for k, row in zip(order, xyz):
+            gyro[k] = (gyro[k][0], (float(row[0]), float(row[1]), float(row[2])))
+    return gyro
 
 
 class OptimSync:

@@ -469,6 +469,45 @@ class Backend:
         out = (pts[:n_pts.value], rank[:n_w], ratio.value)
         return out + (nms[:n_w],) if details else out
 
+    @staticmethod
+    def _pose_pairs(pairs):
+        """[(points_a [n][2], points_b [n][2])] -> (pair_first, points_a, points_b) as gfw_pose_almeida takes them (kept alive by the caller)"""
+        _, first, pa, pb = Backend._sync_pairs([(0, 0, a, b) for a, b in pairs])
+        return first, pa, pb
+
+    def pose_almeida(self, params, cfg, pairs, triples, samples=None, rounds=False, out_ptrs=None):
+        """PoseAlmeida::estimate_pose (estimate_pose/almeida.rs:23-238) of every frame pair in one device call (gfw_pose_almeida), the random draws given.
+
+        ``params``: the KernelParams `undistort_points` builds; ``cfg``: abi.PoseAlmeidaCfg; ``pairs``: [(points_a [n][2], points_b [n][2])] optical-flow pixels;
+        ``triples``: int32 [n_pairs][num_iters][3]; ``samples``: None (every round's list is 0 .. n-1) or one int32 array [num_iters][min(n, num_samples)] per pair
+        (``pose_draws`` makes both).  Returns (quats f32 [n_pairs][4] (w, i, j, k), rotations f64 [n_pairs][3][3], best int32 [n_pairs][2] (inliers, round)) — with
+        ``rounds`` also every round's inliers int32 [n_pairs][num_iters] and fit f32 [n_pairs][num_iters][4] — or, with ``out_ptrs`` = (quats, rotations, best,
+        round_inliers or None, round_fits or None) device pointers, None: in order on the stream."""
+        first, pa, pb = self._pose_pairs(pairs)
+        n, iters = len(pairs), int(cfg.num_iters)
+        tr = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1)
+        assert tr.size == n * iters * 3, "triples: [n_pairs][num_iters][3]"
+        sf = sm = None
+        if samples is not None:
+            lists = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in samples]
+            assert len(lists) == n
+            sf = np.zeros(n + 1, dtype=np.int32)
+            if n:
+                sf[1:] = np.cumsum([len(s) for s in lists])
+            sm = np.ascontiguousarray(np.concatenate(lists)) if lists else np.zeros(0, dtype=np.int32)
+            if not sm.size:
+                sm = np.zeros(1, dtype=np.int32)
+        p = lambda a: a.ctypes.data if a is not None else None
+        args = (self.ctx, C.byref(params), C.byref(cfg), first.ctypes.data, pa.ctypes.data, pb.ctypes.data, n, tr.ctypes.data if tr.size else None, p(sf), p(sm))
+        if out_ptrs is not None:
+            self._check(self.lib.gfw_pose_almeida(*args, *out_ptrs, 1))
+            return None
+        quats, rot, best = np.zeros((n, 4), dtype=np.float32), np.zeros((n, 3, 3), dtype=np.float64), np.zeros((n, 2), dtype=np.int32)
+        ri, rf = np.zeros((n, iters), dtype=np.int32), np.zeros((n, iters, 4), dtype=np.float32)
+        q = lambda a: a.ctypes.data if a.size else None
+        self._check(self.lib.gfw_pose_almeida(*args, q(quats), q(rot), q(best), q(ri) if rounds else None, q(rf) if rounds else None, 0))
+        return (quats, rot, best, ri, rf) if rounds else (quats, rot, best)
+
     def synchronize(self):
         self._check(self.lib.gfw_synchronize(self.ctx))
 
@@ -532,6 +571,29 @@ def optim_resample(timestamps_ms, xyz, has=None):
         if rc < 0:
             raise GfwError(rc, lib.gfw_last_error().decode())
     return out, rate.value
+
+
+def pose_draws(seed, counts, num_iters, num_samples, lists=True):
+    """The draws of a gfw_pose_almeida call on the host (gfw_pose_draws; no context, no GPU): ``counts`` = the points of each pair ->
+    (triples int32 [n_pairs][num_iters][3], one int32 sample list [num_iters][min(n, num_samples)] per pair, or None without ``lists``).
+    One valid draw per seed from a counter-based generator: not rand's sequence."""
+    n = len(counts)
+    first = np.zeros(n + 1, dtype=np.int32)
+    lens = [min(int(c), int(num_samples)) for c in counts]
+    sf = np.zeros(n + 1, dtype=np.int32)
+    if n:
+        first[1:] = np.cumsum([int(c) for c in counts])
+        sf[1:] = np.cumsum([int(num_iters) * m for m in lens])
+    triples = np.zeros((n, int(num_iters), 3), dtype=np.int32)
+    flat = np.zeros(max(int(sf[-1]), 1), dtype=np.int32)
+    lib = abi.load_library()
+    rc = lib.gfw_pose_draws(int(seed) & (2 ** 64 - 1), first.ctypes.data, n, int(num_iters), int(num_samples), triples.ctypes.data if triples.size else None,
+                            sf.ctypes.data if lists else None, flat.ctypes.data if lists else None)
+    if rc < 0:
+        raise GfwError(rc, lib.gfw_last_error().decode())
+    if not lists:
+        return triples, None
+    return triples, [flat[sf[p]:sf[p + 1]].reshape(int(num_iters), lens[p]).copy() for p in range(n)]
 
 
 def lowpass_gyro(freq, sample_rate, xyz, has=None):

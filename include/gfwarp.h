@@ -615,7 +615,8 @@ int   gfw_zoom_smooth(const double *fov_minimal, int n, double adaptive_zoom_win
  * HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA, a non-zero reserved slot, no tracks.
  * NOT covered: clips with per_frame_time_offsets, camera_stab_data or mesh_correction (in the reference the frame index, and so
  * the mesh, follows `timestamp - offs`); lens data or a video rotation keyframed inside a range; suppress_rotation; optical
- * flow, pose estimation, rs_sync.  (essential_matrix: gfw_sync_gyro_search below; optimsync: gfw_sync_optim_points below.) */
+ * flow, rs_sync.  (essential_matrix: gfw_sync_gyro_search below; optimsync: gfw_sync_optim_points below; pose estimation by the
+ * Almeida method: gfw_pose_almeida below.) */
 typedef struct gfw_sync_search {
     int32_t width, height;            /* params.width / height: the bounds test (`w as f32`) and the readout divisor */
     int32_t horizontal_readout;
@@ -666,7 +667,8 @@ int   gfw_sync_visual_search(gfw_ctx *ctx, const gfw_kernel_params *params, cons
  * GFW_ERR_INVALID_ARGUMENT, the range named in gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative
  * counts, a negative or descending first array, a slice outside its array, a non-finite initial_offset or search_size, a negative
  * search_size, counts over the limits above.  Non-finite sample values are not rejected; the pick among NaN costs is unspecified.
- * NOT covered: pose estimation, optical flow, rs_sync itself.
+ * NOT covered: optical flow, rs_sync itself, pose estimation other than the Almeida method (gfw_pose_almeida below; the series of
+ * estimated samples is made of its rotations by gyroflow::estimated_gyro / gyroflow_amd.synchronization.estimated_gyro).
  *
  * gfw_lowpass_gyro: Lowpass::filter_gyro_forward_backward (filtering.rs:46-74) of xyz [n][3] f64 in place, on the host (no context):
  * biquad's second-order Butterworth low-pass (Q = 1/sqrt 2), transposed direct form II, forward over the series and then backward;
@@ -725,6 +727,54 @@ int   gfw_sync_optim_rank(gfw_ctx *ctx, const double *gyro, int64_t n_samples, d
 int   gfw_sync_optim_points(gfw_ctx *ctx, const double *gyro, int64_t n_samples, double sample_rate, int target_sync_points,
                             const double *trim_ranges_s, int n_trim, double *points_ms, int32_t *n_points, float *rank, float *rank_nms,
                             double *ratio, int out_on_device);
+
+/* ---- synchronization: Almeida pose estimation of a clip's frame pairs in one device call ----
+ * estimate_pose/almeida.rs:23-238 (`PoseAlmeida`, also what `EstimatePoseMethod::from` falls back to): per pair of frames the matched
+ * optical-flow points become one camera rotation — `solve_ypr_ransac` (:194-238) over `solve_ypr_given` (:124-192).  The reference
+ * draws a round's three points and its sample list from an unseeded generator, so it has no reproducible output: here THE DRAWS ARE
+ * INPUTS, and the result is a function of them that tests/_posestmt.py states in f32, operation by operation (nalgebra's quaternion,
+ * Euler-angle and LU forms are restated there from the crate's documented forms).  `Camera::delta` (:58-68) always maps a point at
+ * the same position with lens_correction_amount 1.0, fov 1.0, no shifts and no mesh, so the lens is inverted once per point; every
+ * later delta is one f32 gemv through f32(K * f64(R)) and two divides.
+ *   params     the KernelParams `undistort_points` builds, as for gfw_undistort_points; f / c = the f32 cast of camera_matrix
+ *   pair_first [n_pairs + 1] ascending: pair p owns points pair_first[p] .. pair_first[p + 1] - 1 of points_a / points_b [total][2] f32
+ *              (optical-flow pixels of the first / second frame)
+ *   triples    [n_pairs][num_iters][3] the three distinct points of each round, indices into the pair (ignored for pairs under 3 points)
+ *   samples    NULL: every round's list is 0 .. n-1 (one of the permutations the reference's draw can produce; rejected when a pair has
+ *              more than num_samples points).  Otherwise pair p owns samples[sample_first[p] ..]: [num_iters][min(n, num_samples)]
+ *              indices into the pair, sample_first [n_pairs + 1] ascending with exactly that many entries a pair
+ *   quats      [n_pairs][4] f32 (w, i, j, k): the estimated rotation; rotations [n_pairs][9] f64 row-major: its matrix, computed in f32
+ *              and cast — what estimate_pose returns.  The identity for a pair under 3 points or under 3 best inliers
+ *   best       [n_pairs][2] int32: the inliers of the best round and that round (the FIRST of equal counts; -1 without rounds)
+ *   round_inliers / round_fits   NULL or [n_pairs][num_iters] int32 / [n_pairs][num_iters][4] f32: every round's count and fit
+ *   limits     at most 4096 points in a pair, 65535 pairs, 1024 rounds, 2 GiB staged in all
+ * Four launches for any clip, in order on the context's stream; outputs are host or device memory (out_on_device); with device
+ * outputs an asynchronous context returns without waiting.  n_pairs = 0 succeeds and writes nothing.  Rejected with
+ * GFW_ERR_INVALID_ARGUMENT, the pair named in gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative counts,
+ * a descending pair_first, counts over the limits, an index outside its pair, a triple with a repeated index, a sample_first that does
+ * not match, params->flags with HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA, f / c that are not the f32 cast of camera_matrix,
+ * sizes under 1, a negative or NaN inlier angle, a non-zero reserved slot.
+ * NOT covered: lens data or a refraction coefficient that changes between the pairs of one call (one call per lens); the other three
+ * pose methods (their solvers are not part of the reference tree); optical flow.
+ *
+ * gfw_pose_draws (host only, no context): one valid set of draws per seed — not rand's sequence.  A counter-based generator:
+ * word(seed, pair, round, k) = mix(mix(seed ^ (pair << 32 | round)) + k) with SplitMix64's finaliser as mix, an index below r the high
+ * word of (word >> 32) * r; a triple is three distinct indices, a list the first min(n, num_samples) entries of a Fisher-Yates shuffle
+ * of 0 .. n-1.  samples NULL: triples only.  Pairs under 3 points get zero triples. */
+typedef struct gfw_pose_almeida_cfg {
+    int32_t video_width, video_height;     /* compute_params.width / height */
+    int32_t flow_width, flow_height;       /* FrameResult::frame_size */
+    int32_t num_iters, num_samples;        /* 200, 1000 */
+    float   inlier_angle_deg;              /* 0.05 */
+    int32_t reserved;                      /* 0 */
+    double  camera_matrix[9];              /* get_lens_data_at_timestamp(..).0, row-major */
+} gfw_pose_almeida_cfg;
+int   gfw_pose_almeida(gfw_ctx *ctx, const gfw_kernel_params *params, const gfw_pose_almeida_cfg *cfg,
+                       const int32_t *pair_first, const float *points_a, const float *points_b, int n_pairs,
+                       const int32_t *triples, const int32_t *sample_first, const int32_t *samples,
+                       float *quats, double *rotations, int32_t *best, int32_t *round_inliers, float *round_fits, int out_on_device);
+int   gfw_pose_draws(uint64_t seed, const int32_t *pair_first, int n_pairs, int num_iters, int num_samples,
+                     int32_t *triples, const int32_t *sample_first, int32_t *samples);
 
 /* First-pass audit of the fused kernel (GFW_OPT_KERNEL_VARIANT = 3): counters8 = {certified pixels,
  * certified-but-different-from-exact (must stay 0), queued to the exact path, queue overflows,

@@ -468,6 +468,96 @@ inline SyncParams initial_offset_fast(gfw_ctx *ctx, const std::map<int64_t, Time
     return sync_params;
 }
 
+// ---- synchronization/estimate_pose/almeida.rs over gfw_pose_almeida: `PoseEstimator::process_detected_frames` (synchronization/mod.rs:110-167) with the Almeida
+// method for ALL frame pairs in one device call, and the host part of `recalculate_gyro_data` (:269-361) that turns the rotations into the series
+// find_offsets_essential takes.  `pairs`: one entry per frame pair in order; an entry without points (the optical flow found no lines) has no rotation (:141).
+// The reference draws a round's points from an unseeded generator; here `seed` decides them (gfw_pose_draws).  `params`: the KernelParams undistort_points builds;
+// `cfg`: sizes, rounds, samples, the inlier angle and the camera matrix (f / c of params are its f32 cast).
+struct FlowPair { bool has_points = false; std::vector<std::pair<float, float>> points, next_points; };
+struct PoseResult { bool has_rotation = false; double rotation[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}; float quat[4] = {1, 0, 0, 0}; double euler[3] = {0, 0, 0}; int inliers = 0, round = -1; };
+// Rotation3::scaled_axis: the axis of the skew part (none when its norm is not above the f64 epsilon) times acos((trace - 1) / 2)
+inline std::array<double, 3> scaled_axis(const double *m) {
+    const double ax = m[7] - m[5], ay = m[2] - m[6], az = m[3] - m[1];
+    const double norm = std::sqrt(ax * ax + ay * ay + az * az);
+    if (!(norm > 2.220446049250313e-16)) return {0.0, 0.0, 0.0};
+    const double c = (m[0] + m[4] + m[8] - 1.0) / 2.0, angle = std::acos(c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c));
+    return {ax / norm * angle, ay / norm * angle, az / norm * angle};
+}
+inline std::vector<PoseResult> estimate_poses_almeida(gfw_ctx *ctx, const KernelParams &params, const gfw_pose_almeida_cfg &cfg, const std::vector<FlowPair> &pairs,
+                                                      double scaled_fps, double every_nth_frame = 1.0, uint64_t seed = 0) {
+    std::vector<PoseResult> out(pairs.size());
+    std::vector<size_t> live;
+    std::vector<int32_t> first{0}, sample_first{0};
+    std::vector<float> a, b;
+    for (size_t i = 0; i < pairs.size(); ++i) {
+        const FlowPair &p = pairs[i];
+        if (!p.has_points) continue;
+        if (p.points.size() != p.next_points.size()) throw GyroflowCoreError(GyroflowCoreError::Unknown, "estimate_poses_almeida: a pair's two point sets have one length");
+        for (const auto &pt : p.points) { a.push_back(pt.first); a.push_back(pt.second); }
+        for (const auto &pt : p.next_points) { b.push_back(pt.first); b.push_back(pt.second); }
+        first.push_back((int32_t)(a.size() / 2));
+        sample_first.push_back(sample_first.back() + cfg.num_iters * (int32_t)std::min<size_t>(p.points.size(), (size_t)std::max(cfg.num_samples, 0)));
+        live.push_back(i);
+    }
+    if (live.empty()) return out;
+    if (!ctx) throw GyroflowCoreError(GyroflowCoreError::Unknown, "estimate_poses_almeida: no backend context for the pose estimation");
+    const int n = (int)live.size();
+    std::vector<int32_t> triples((size_t)n * (size_t)std::max(cfg.num_iters, 0) * 3 + 1), samples((size_t)sample_first.back() + 1), best((size_t)n * 2);
+    std::vector<float> quats((size_t)n * 4);
+    std::vector<double> rotations((size_t)n * 9);
+    int rc = gfw_pose_draws(seed, first.data(), n, cfg.num_iters, cfg.num_samples, triples.data(), sample_first.data(), samples.data());
+    if (rc == GFW_OK) rc = gfw_pose_almeida(ctx, &params, &cfg, first.data(), a.data(), b.data(), n, triples.data(), sample_first.data(), samples.data(),
+                                            quats.data(), rotations.data(), best.data(), nullptr, nullptr, 0);
+    if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+    for (int k = 0; k < n; ++k) {
+        PoseResult &r = out[live[(size_t)k]];
+        r.has_rotation = true;
+        std::copy(rotations.begin() + k * 9, rotations.begin() + k * 9 + 9, r.rotation);
+        std::copy(quats.begin() + k * 4, quats.begin() + k * 4 + 4, r.quat);
+        const auto rv = scaled_axis(r.rotation);
+        for (int i = 0; i < 3; ++i) r.euler[i] = rv[(size_t)i] * (scaled_fps / every_nth_frame);      // :146
+        r.inliers = best[(size_t)k * 2]; r.round = best[(size_t)k * 2 + 1];
+    }
+    return out;
+}
+// `results`: every analysed frame's timestamp_us -> its euler, or nullopt without a rotation (a sample sits midway to the NEXT analysed frame, :312-315);
+// final_pass interpolates a missing rotation linearly between its neighbours that have one (:284-305); lpf > 0 (Hz) runs gfw_lowpass_gyro (:349-357)
+inline std::map<int64_t, TimeIMU> estimated_gyro(const std::map<int64_t, std::optional<std::array<double, 3>>> &results, double fps, double lpf = 0.0, bool final_pass = false) {
+    std::map<int64_t, TimeIMU> gyro;
+    for (auto it = results.begin(); it != results.end(); ++it) {
+        std::optional<std::array<double, 3>> eul = it->second;
+        if (final_pass && !eul) {
+            auto prev = results.end(), next = results.end();
+            for (auto p = it; p != results.begin();) { --p; if (p->second) { prev = p; break; } }
+            for (auto p = it; p != results.end(); ++p) if (p->second) { next = p; break; }
+            if (prev != results.end() && next != results.end()) {
+                const double ratio = (double)(it->first - prev->first) / (double)(next->first - prev->first);
+                std::array<double, 3> e;
+                for (size_t i = 0; i < 3; ++i) e[i] = (*prev->second)[i] + ((*next->second)[i] - (*prev->second)[i]) * ratio;
+                eul = e;
+            }
+        }
+        if (!eul) continue;
+        double ts = (double)it->first / 1000.0;
+        const auto nx = std::next(it);
+        if (nx != results.end()) ts += ((double)nx->first / 1000.0 - ts) / 2.0;
+        TimeIMU x;
+        x.timestamp_ms = ts; x.has_gyro = true;
+        const double pi = 3.14159265358979323846;
+        x.gyro[0] = (*eul)[1] * 180.0 / pi; x.gyro[1] = (*eul)[0] * 180.0 / pi; x.gyro[2] = (*eul)[2] * 180.0 / pi;      // x and y swapped (:322-326)
+        gyro[(int64_t)std::round(ts * 1000.0)] = x;
+    }
+    if (lpf > 0.0 && fps > 0.0 && !gyro.empty()) {
+        std::vector<double> xyz;
+        for (const auto &kv : gyro) for (int a = 0; a < 3; ++a) xyz.push_back(kv.second.gyro[a]);
+        const int rc = gfw_lowpass_gyro(lpf, fps, xyz.data(), nullptr, (int)gyro.size());               // a refusal is logged and ignored by the reference
+        if (rc < 0) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+        size_t i = 0;
+        for (auto &kv : gyro) { for (int a = 0; a < 3; ++a) kv.second.gyro[a] = xyz[i * 3 + (size_t)a]; ++i; }
+    }
+    return gyro;
+}
+
 // OptimSync (optimsync.rs:10-226): where in a clip to sync, decided before any optical flow (lib.rs:2054-2060).  `make` is OptimSync::new — the gyro resampled at its
 // average rate on the host (gfw_optim_resample; nullopt without samples, as the reference's None) — and `run` is OptimSync::run in ONE device call
 // (gfw_sync_optim_points): (points in ms, the rank of every window before the masks, ratio = 16 / sample_rate).

@@ -1,0 +1,52 @@
+"""TEST INFRASTRUCTURE: the pose estimation's kernel SOURCE (gyroflow_amd/csrc/gfw_pose.hip) and the entry point's host code (gfw_pose_check, gfw_pose_fill,
+gfw_pose_constants: gfw_pose_host.h) interpreted on the host, the way tests/_emu_sync.py runs gfw_sync.hip: tests/emu/emu_pose_driver.inc behind the unedited source,
+the lanes of a workgroup as cooperative fibers that rendezvous at __syncthreads and at every __ballot.  Not a product path."""
+import ctypes as C
+
+import numpy as np
+
+from gyroflow_amd import warp
+import _emu
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        L = C.CDLL(_emu.build({}, "", top="gfw_pose.hip", n_asm=2, driver="emu_pose_driver.inc", extra_flags=()))
+        vp, i32 = C.c_void_p, C.c_int
+        L.gfw_emu_pose.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_char_p, C.c_size_t]
+        _lib = L
+    return _lib
+
+
+class Refused(ValueError):
+    pass
+
+
+def pose_almeida(params, model, digital, cfg, pairs, triples, samples=None, rounds=True):
+    """gfw_pose_almeida through the host-interpreted kernels -> (quats, rotations, best, round_inliers, round_fits) shaped as Backend.pose_almeida's; raises Refused
+    with the reason where the entry point's own check refuses the arguments"""
+    com = _emu.common_for(_emu._Lenses(model, digital), params)
+    first, pa, pb = warp.Backend._pose_pairs(pairs)
+    n, iters = len(pairs), int(cfg.num_iters)
+    tr = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1)
+    sf = sm = None
+    if samples is not None:
+        lists = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in samples]
+        sf = np.zeros(n + 1, dtype=np.int32)
+        sf[1:] = np.cumsum([len(s) for s in lists])
+        sm = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, dtype=np.int32)]))
+    quats, rot, best = np.full((n, 4), -7.0, dtype=np.float32), np.full((n, 3, 3), -7.0), np.full((n, 2), -7, dtype=np.int32)
+    ri, rf = np.full((n, iters), -7, dtype=np.int32), np.full((n, iters, 4), -7.0, dtype=np.float32)
+    K = np.array([cfg.camera_matrix[i] for i in range(9)], dtype=np.float64)
+    why = C.create_string_buffer(512)
+    p = lambda a: a.ctypes.data if a is not None and a.size else None
+    rc = lib().gfw_emu_pose(C.cast(C.byref(params), C.c_void_p), C.cast(C.byref(com), C.c_void_p), cfg.video_width, cfg.video_height, cfg.flow_width, cfg.flow_height,
+                            iters, cfg.num_samples, cfg.inlier_angle_deg, K.ctypes.data, first.ctypes.data, p(pa), p(pb), n, p(tr), p(sf), sm.ctypes.data if sm is not None else None,
+                            p(quats), p(rot), p(best), p(ri) if rounds else None, p(rf) if rounds else None, why, len(why))
+    if rc == -1:
+        raise Refused(why.value.decode())
+    assert rc == 0, "gfw_emu_pose -> %d" % rc
+    return quats, rot, best, ri, rf
