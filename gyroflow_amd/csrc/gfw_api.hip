@@ -33,6 +33,7 @@
 #include "gfw_sync_gyro_host.h"
 #include "gfw_sync_optim_host.h"
 #include "gfw_pose_host.h"
+#include "gfw_clip_host.h"
 #include "gfw_jit.h"
 #include <stdlib.h>
 #include <map>
@@ -49,8 +50,6 @@ static_assert(offsetof(gfw_kernel_params, digital_lens_params) == 224, "layout")
 static_assert(offsetof(gfw_kernel_params, max_pixel_value) == 304, "layout");
 static_assert(offsetof(gfw_kernel_params, plane_index) == 324, "layout");
 static_assert(offsetof(gfw_kernel_params, ewa_coeffs_p) == 336, "layout");
-
-#define GFW_MESH_MAX 839   /* MAX_BUFFER_SIZE, gyro_source/splines.rs:88-89 */
 
 static thread_local std::string g_last_error;
 static void set_error(const char *fmt, ...) {
@@ -73,7 +72,7 @@ struct FusedShape {
     int dw = 1, dh = 1, interleaved = 0;         // chroma subsampling; plane 1 holds both chroma channels
     int fast1 = 0;                               // the certified first pass
 };
-struct JitKeyMisc { FusedShape shape; int tune_grid = 0, perframe = 0; };      // what jit_for's key holds beside the argument block
+struct JitKeyMisc { FusedShape shape; int tune_grid = 0; ClipFlavour flavour = CLIP_SHARED; };      // what jit_for's key holds beside the argument block
 
 struct gfw_ctx {
     int device = 0;
@@ -581,9 +580,6 @@ static bool int_products_exact(int n_max, int n) {
     return (int64_t)(n_max - 1) * odd < (1 << 24);
 }
 
-// One frame as the entry points take it: gfw_undistort_frame's arguments, a frame of a clip call, the planes a PlaneGroup assembled
-struct FrameIn { int nplanes; const gfw_buffers *planes; const gfw_kernel_params *params; const int *pixel_types; const float *matrices; int matrix_count; const float *mesh; size_t mesh_len;
-                 bool mesh_checked = false; };      // (gfw_undistort_clip_lens validated the mesh before its first frame)
 #include "gfw_api_certificate.inc"
 #include "gfw_api_eligibility.inc"
 #include "gfw_api_clip.inc"
@@ -624,7 +620,7 @@ static int checksum_written(gfw_ctx *c, int nplanes, const gfw_buffers *planes, 
 // What run_planes' stages hand on: the planes as the kernels take them, the frame's tables on the device, its checksum word (gfw_set_frame_checksums; nullptr: off) ...
 struct StagedFrame { GfwPlane pl[8]; const float *d_mat = nullptr, *d_mesh = nullptr; unsigned long long *sum = nullptr; };
 // ... and the kernel that serves it: the fused one (Y, S) or the generic one per plane; the former's specialised build if there is one, which may take the checksum
-struct KernelChoice { bool fused = false; int perframe = 0; GfwYuvArgs Y; FusedShape S; hipFunction_t jf = nullptr; int jgrid = 0; bool sum_taken = false; };
+struct KernelChoice { bool fused = false; ClipFlavour flavour = CLIP_SHARED; GfwYuvArgs Y; FusedShape S; hipFunction_t jf = nullptr; int jgrid = 0; bool sum_taken = false; };
 static const char *fused_backend(const FusedShape &S, bool jit) { return jit ? (S.fast1 ? "yuv_fused_p1_jit" : "yuv_fused_jit") : (S.fast1 ? "yuv_fused_p1" : "yuv_fused"); }
 // Stage 1: validate the call and stage what the kernels read — the checksum word, the matrices, the mesh, host planes
 static int stage_frame(gfw_ctx *c, const FrameIn &F, StagedFrame &G) {
@@ -689,8 +685,8 @@ static int choose_kernel(gfw_ctx *c, const FrameIn &F, const StagedFrame &G, Cli
         const long long lane_rows = (long long)Y.tiles_x * Y.tiles_y * gfw_yuv_rows_per_lane(S.fast1 != 0, 0) * S.dh;
         Y.checksum = (aligned && lane_rows < 8 * 32768ll) ? 1 : 0;
     }
-    K.perframe = clip_flavour(batch);                 // (gfw_undistort_clip_params: the per-frame flavour, whose key blanks the per-frame fields; gfw_undistort_clip_lens: the moving-lens one)
-    K.jf = jit_for(c, Y, S, K.perframe, &K.jgrid);
+    K.flavour = flavour_of(batch);                    // (the kernel's key blanks what the flavour's slots carry)
+    K.jf = jit_for(c, Y, S, K.flavour, &K.jgrid);
     if (!K.jf && S.fast1 && Y.p1_rform) {
         // a table over r is read by specialised builds only: until one is loaded (or for good, without hiprtc and without a cached kernel) the frame takes the
         // ahead-of-time generic-model kernel and its exact first pass — whose tiles are one lane-row tall
@@ -710,16 +706,14 @@ static int join_launch(gfw_ctx *c, const FrameIn &F, const KernelChoice &K, unsi
     const GfwYuvArgs &Y = K.Y;
     // a frame that does not share the pending ones' kernel or first-pass table goes out behind them
     // (a frame that REBUILT the table has already sent them on their way, before the copy: p1_setup — they read the table with the range they were set up for)
-    if (batch->n > 0 && (batch->fn != K.jf || batch->CA.Y.p1_table != Y.p1_table || batch->CA.Y.p1_rho_max != Y.p1_rho_max ||
-                         batch->CA.Y.p1_rho_scale != Y.p1_rho_scale || batch->CA.Y.p1_eps != Y.p1_eps || batch->CA.Y.p1_ew != Y.p1_ew ||
-                         !(batch->perframe ? clip_same_params_pf(batch->CA.Y, Y, batch->lens) : clip_same_params(batch->CA.Y, Y)) || clip_overlaps(batch, F.planes, F.nplanes))) {
+    if (batch->n > 0 && (batch->fn != K.jf || batch->Y.p1_table != Y.p1_table || batch->Y.p1_rho_max != Y.p1_rho_max ||
+                         batch->Y.p1_rho_scale != Y.p1_rho_scale || batch->Y.p1_eps != Y.p1_eps || batch->Y.p1_ew != Y.p1_ew ||
+                         !clip_same_params(batch->Y, Y, batch->flavour) || clip_overlaps(batch->fr, batch->n, batch->first, F.planes, F.nplanes))) {
         const int frc = clip_flush(c, batch); if (frc != GFW_OK) return frc;
     }
-    if (batch->n == 0) { batch->CA.Y = Y; batch->fn = K.jf; batch->grid = K.jgrid; batch->first = F.planes; batch->backend = fused_backend(K.S, true);
+    if (batch->n == 0) { batch->Y = Y; batch->fn = K.jf; batch->grid = K.jgrid; batch->first = F.planes; batch->backend = fused_backend(K.S, true);
                          batch->limit = clip_launch_limit(Y, F.nplanes, batch->n_call); }
-    const GfwFramePer slot = frame_slot(Y);
-    const GfwLensSlot lens = lens_slot(Y, nullptr, F.mesh_len);      // (the mesh: staged with the launch, from the caller's memory)
-    { const int frc = clip_append(c, batch, frame_dyn(Y), K.perframe ? &slot : nullptr, sum, K.perframe >= 2 ? &lens : nullptr, (Y.extras & 32) ? F.mesh : nullptr); if (frc != GFW_OK) return frc; }
+    { const int frc = clip_append(c, batch, clip_frame(Y, F, batch->flavour, true, sum)); if (frc != GFW_OK) return frc; }      // (its mesh: staged with the launch, from the caller's memory)
     if (sum && !K.sum_taken) {                        // (a frame of a launch whose kernel does not take sums: behind the launch it has just joined)
         const int frc = clip_flush(c, batch); if (frc != GFW_OK) return frc;
         return checksum_written(c, F.nplanes, F.planes, F.params, sum);
@@ -727,14 +721,12 @@ static int join_launch(gfw_ctx *c, const FrameIn &F, const KernelChoice &K, unsi
     return GFW_OK;
 }
 // Way out 2: one launch of the fused kernel for this frame alone
-static int launch_fused(gfw_ctx *c, const KernelChoice &K, unsigned long long *sum) {
+static int launch_fused(gfw_ctx *c, const FrameIn &F, const KernelChoice &K, unsigned long long *sum) {
     const FusedShape &S = K.S;
     if (K.jf) {
-        GfwClipArgs CA;
-        CA.Y = K.Y; CA.n_frames = 1; CA.pad_ = 0; CA.fr[0] = frame_dyn(K.Y);
-        const GfwFramePer slot = frame_slot(K.Y);      // (a frame of gfw_undistort_clip_params that cannot join a launch — host buffers, a table of the ring — still takes its call's kernel)
-        const GfwLensSlot lens = lens_slot(K.Y, K.Y.common.mesh, (size_t)K.Y.common.mesh_len);      // (the same for gfw_undistort_clip_lens; its mesh is the context's, uploaded for this frame)
-        const int rc = jit_launch(c, K.jf, K.jgrid, CA, K.perframe ? &slot : nullptr, &sum, K.perframe >= 2 ? &lens : nullptr); if (rc != GFW_OK) return rc;
+        // (a frame of a clip call that cannot join a launch — host buffers, a table of the ring — still takes its call's kernel; its mesh is the context's, uploaded for this frame)
+        const ClipFrame fr = clip_frame(K.Y, F, K.flavour, false, sum);
+        const int rc = clip_launch(c, K.jf, K.jgrid, K.flavour, K.Y, &fr, 1); if (rc != GFW_OK) return rc;
     } else HIP_TRY(gfw_launch_yuv(K.Y, S.kind, S.taps, S.n0, S.dw, S.dh, S.interleaved != 0, S.fast1 != 0, c->stream), GFW_ERR_HIP);
     c->last_backend = fused_backend(S, K.jf != nullptr);
     return GFW_OK;
@@ -808,7 +800,7 @@ static int run_planes(gfw_ctx *c, const FrameIn &F, ClipBatch *batch = nullptr) 
     // the frame's mesh goes to the context's one buffer only now: a frame that joined a launch above brought its mesh along with the launch's staged block
     if (G.d_mesh) HIP_TRY(hipMemcpyAsync(c->d_mesh.ptr, F.mesh, F.mesh_len * sizeof(float), hipMemcpyHostToDevice, c->stream), GFW_ERR_HIP);
     prof_begin(c);
-    { const int rc = K.fused ? launch_fused(c, K, G.sum) : launch_per_plane(c, F, G); if (rc != GFW_OK) return rc; }
+    { const int rc = K.fused ? launch_fused(c, F, K, G.sum) : launch_per_plane(c, F, G); if (rc != GFW_OK) return rc; }
     return finish_frame(c, F, G, K.sum_taken);
 }
 
@@ -833,6 +825,37 @@ static int check_pixel_types(int nplanes, const int *pixel_types) {
     for (int i = 0; i < nplanes; ++i)
         if (pixel_types[i] < 0 || pixel_types[i] >= GFW_PIX_COUNT) { set_error("plane %d: unknown pixel type %d", i, pixel_types[i]); return GFW_ERR_INVALID_ARGUMENT; }
     return GFW_OK;
+}
+// The frame loop of the clip entry points: each frame of the call through run_planes with the call's batch, then the end of the call.  `params`: one set for the
+// call (CLIP_SHARED) or one per frame; `meshes` / `mesh_lens`: per frame, or nullptr
+static int run_clip(gfw_ctx *c, ClipFlavour fl, int n_frames, int nplanes, const gfw_buffers *planes, const gfw_kernel_params *params, const int *pixel_types,
+                    const float *const *matrices, int matrix_count, const float *const *meshes, const size_t *mesh_lens) {
+    ClipBatch batch(fl, n_frames, nplanes, params);
+    for (int f = 0; f < n_frames; ++f) {
+        const gfw_buffers *fp = planes + (size_t)f * nplanes;
+        // A frame of gfw_undistort_clip shaped exactly like the one that opened the pending launch (same descriptions but for the pointers; the parameters are
+        // shared by construction) needs none of the per-frame validation again: its pointers join the launch.  ~10 us -> < 1 us of host time.
+        const GfwFrameDyn &D0 = batch.fr[0].dyn;
+        bool words = true;                            // (the checksum build places an element by its offset: every plane on a 64-bit word, as run_planes checked for the launch's first frame)
+        if (fl == CLIP_SHARED && c->sums && batch.n > 0) for (int i = 0; i < nplanes && i < 4; ++i) words = words && (((uintptr_t)fp[i].output.data + (uintptr_t)(D0.dst[i] - (uint8_t *)batch.first[i].output.data)) & 7) == 0;
+        if (fl == CLIP_SHARED && batch.n > 0 && batch.n < batch.limit && (!c->sums || (batch.Y.checksum && words)) && c->matrices_on_device == 2 && matrices[f] &&
+            clip_same_shape(batch.first, fp, nplanes) && !clip_ring_table(c, matrices[f]) && !clip_overlaps(batch.fr, batch.n, batch.first, fp, nplanes)) {
+            ClipFrame F;                              // (CLIP_SHARED: its pointers and its checksum word)
+            for (int i = 0; i < 4; ++i) {
+                // (the kernel's planes begin at their rects' first pixels: the same offsets the launch's first frame was given — clip_same_shape compared the rects)
+                const ptrdiff_t so = i < nplanes ? D0.src[i] - (const uint8_t *)batch.first[i].input.data : 0, dof = i < nplanes ? D0.dst[i] - (uint8_t *)batch.first[i].output.data : 0;
+                F.dyn.src[i] = i < nplanes ? (const uint8_t *)fp[i].input.data + so : nullptr; F.dyn.dst[i] = i < nplanes ? (uint8_t *)fp[i].output.data + dof : nullptr;
+            }
+            F.dyn.matrices = matrices[f]; F.sum = next_sum(c);
+            const int frc = clip_append(c, &batch, F); if (frc != GFW_OK) return frc;
+            continue;
+        }
+        const size_t ml = (meshes && meshes[f]) ? mesh_lens[f] : 0;
+        FrameIn F{nplanes, fp, fl == CLIP_SHARED ? params : params + (size_t)f * nplanes, pixel_types, matrices[f], matrix_count, ml ? meshes[f] : nullptr, ml};
+        F.mesh_checked = fl == CLIP_MOVING_LENS;      // (gfw_undistort_clip_lens validated every mesh before the first frame)
+        const int rc = run_planes(c, F, &batch); if (rc != GFW_OK) return clip_end(c, &batch, rc);
+    }
+    return clip_end(c, &batch, GFW_OK);
 }
 extern "C" {
 
@@ -929,31 +952,7 @@ int gfw_undistort_clip(gfw_ctx *c, int n_frames, int nplanes, const gfw_buffers 
     { const int prc = check_pixel_types(nplanes, pixel_types); if (prc != GFW_OK) return prc; }
     // the frame loop of a render (rendering/mod.rs:487-547 calls process_pixels once per frame), here on the library side: frames that
     // share the specialised kernel leave in launches of up to GFW_CLIP_MAX frames, everything else exactly as gfw_undistort_frame
-    ClipBatch batch;
-    batch.n_call = n_frames;
-    for (int f = 0; f < n_frames; ++f) {
-        const gfw_buffers *fp = planes + (size_t)f * nplanes;
-        // A frame shaped exactly like the one that opened the pending launch (same descriptions but for the pointers; the parameters are
-        // shared by construction) needs none of the per-frame validation again: its pointers join the launch.  ~10 us -> < 1 us of host time.
-        bool words = true;                            // (the checksum build places an element by its offset: every plane on a 64-bit word, as run_planes checked for the launch's first frame)
-        if (c->sums && batch.n > 0) for (int i = 0; i < nplanes && i < 4; ++i) words = words && (((uintptr_t)fp[i].output.data + (uintptr_t)(batch.CA.fr[0].dst[i] - (uint8_t *)batch.first[i].output.data)) & 7) == 0;
-        if (batch.n > 0 && batch.n < batch.limit && (!c->sums || (batch.CA.Y.checksum && words)) && c->matrices_on_device == 2 && matrices[f] && clip_same_shape(batch.first, fp, nplanes) &&
-            !clip_ring_table(c, matrices[f]) && !clip_overlaps(&batch, fp, nplanes)) {
-            GfwFrameDyn D;
-            for (int i = 0; i < 4; ++i) {
-                // (the kernel's planes begin at their rects' first pixels: the same offsets the launch's first frame was given — clip_same_shape compared the rects)
-                const ptrdiff_t so = i < nplanes ? batch.CA.fr[0].src[i] - (const uint8_t *)batch.first[i].input.data : 0, dof = i < nplanes ? batch.CA.fr[0].dst[i] - (uint8_t *)batch.first[i].output.data : 0;
-                D.src[i] = i < nplanes ? (const uint8_t *)fp[i].input.data + so : nullptr;
-                D.dst[i] = i < nplanes ? (uint8_t *)fp[i].output.data + dof : nullptr;
-            }
-            D.matrices = matrices[f];
-            const int frc = clip_append(c, &batch, D, nullptr, next_sum(c)); if (frc != GFW_OK) return frc;
-            continue;
-        }
-        const int rc = run_planes(c, FrameIn{nplanes, fp, params, pixel_types, matrices[f], matrix_count, nullptr, 0}, &batch);
-        if (rc != GFW_OK) return clip_end(c, &batch, rc);
-    }
-    return clip_end(c, &batch, GFW_OK);
+    return run_clip(c, CLIP_SHARED, n_frames, nplanes, planes, params, pixel_types, matrices, matrix_count, nullptr, nullptr);
 }
 
 // The frame loop of a render whose KernelParams move from frame to frame (FrameTransform::at_timestamp fills them per frame: the adaptive-zoom fov and its
@@ -967,13 +966,7 @@ int gfw_undistort_clip_params(gfw_ctx *c, int n_frames, int nplanes, const gfw_b
     if (nplanes < 1 || nplanes > 8) { set_error("nplanes %d", nplanes); return GFW_ERR_INVALID_ARGUMENT; }
     { const int prc = check_pixel_types(nplanes, pixel_types); if (prc != GFW_OK) return prc; }
     { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
-    ClipBatch batch;
-    clip_params_batch(batch, n_frames, nplanes, params);
-    for (int f = 0; f < n_frames; ++f) {
-        const int rc = run_planes(c, FrameIn{nplanes, planes + (size_t)f * nplanes, params + (size_t)f * nplanes, pixel_types, matrices[f], matrix_count, nullptr, 0}, &batch);
-        if (rc != GFW_OK) return clip_end(c, &batch, rc);
-    }
-    return clip_end(c, &batch, GFW_OK);
+    return run_clip(c, CLIP_PER_FRAME, n_frames, nplanes, planes, params, pixel_types, matrices, matrix_count, nullptr, nullptr);
 }
 
 // The frame loop of a render whose LENS moves from frame to frame as well (FrameTransform::at_timestamp fills f, c, k and r_limit from
@@ -992,8 +985,7 @@ int gfw_undistort_clip_lens(gfw_ctx *c, int n_frames, int nplanes, const gfw_buf
     if (meshes && !mesh_lens) { set_error("meshes without mesh_lens"); return GFW_ERR_INVALID_ARGUMENT; }
     { const int prc = check_pixel_types(nplanes, pixel_types); if (prc != GFW_OK) return prc; }
     // every frame's mesh is validated before anything is staged or launched: the kernels use mesh[0..2] as an offset and as loop bounds.  Consecutive frames that
-    // name the same mesh share the verdict.  In the same pass: does anything of the lens move at all?
-    bool moves = false;
+    // name the same mesh share the verdict.
     for (int f = 0; f < n_frames; ++f) {
         const float *m = meshes ? meshes[f] : nullptr; const size_t ml = meshes ? mesh_lens[f] : 0;
         if (ml != 0 && !m) { set_error("frame %d: mesh of %zu values at a null pointer", f, ml); return GFW_ERR_INVALID_ARGUMENT; }
@@ -1002,22 +994,10 @@ int gfw_undistort_clip_lens(gfw_ctx *c, int n_frames, int nplanes, const gfw_buf
             const int mrc = validate_mesh(m, ml);
             if (mrc != GFW_OK) { const std::string why = g_last_error; set_error("frame %d: %s", f, why.c_str()); return mrc; }
         }
-        const gfw_kernel_params &p = params[(size_t)f * nplanes], &p0 = params[0];
-        moves = moves || (m && ml) || memcmp(p.f, p0.f, sizeof(p.f)) || memcmp(p.c, p0.c, sizeof(p.c)) || memcmp(p.k, p0.k, sizeof(p.k)) ||
-                memcmp(&p.r_limit, &p0.r_limit, sizeof(float)) || memcmp(&p.light_refraction_coefficient, &p0.light_refraction_coefficient, sizeof(float));
     }
-    if (!moves) return gfw_undistort_clip_params(c, n_frames, nplanes, planes, params, pixel_types, matrices, matrix_count);
+    if (!lens_moves(n_frames, nplanes, params, [&](int f) { return meshes && meshes[f] && mesh_lens[f]; })) return gfw_undistort_clip_params(c, n_frames, nplanes, planes, params, pixel_types, matrices, matrix_count);
     { const int frc_ = flush_if_pending(c); if (frc_ != GFW_OK) return frc_; }
-    ClipBatch batch;
-    batch.n_call = n_frames; batch.perframe = true; batch.lens = true;
-    for (int f = 0; f < n_frames; ++f) {
-        const float *m = meshes ? meshes[f] : nullptr; const size_t ml = (meshes && m) ? mesh_lens[f] : 0;
-        FrameIn F{nplanes, planes + (size_t)f * nplanes, params + (size_t)f * nplanes, pixel_types, matrices[f], matrix_count, ml ? m : nullptr, ml};
-        F.mesh_checked = true;
-        const int rc = run_planes(c, F, &batch);
-        if (rc != GFW_OK) return clip_end(c, &batch, rc);
-    }
-    return clip_end(c, &batch, GFW_OK);
+    return run_clip(c, CLIP_MOVING_LENS, n_frames, nplanes, planes, params, pixel_types, matrices, matrix_count, meshes, mesh_lens);
 }
 
 }  // extern "C"

@@ -19,12 +19,12 @@ static int jit_rows(bool fast1) {
     static const int env = [] { const char *e = getenv("GFW_JIT_RB_FAST"); const int v = e ? atoi(e) : 0; return (v >= 1 && v * 4 <= 64) ? v : 0; }();
     return (fast1 && env > 0) ? env : gfw_yuv_rows_per_lane(fast1, 0);
 }
-// perframe: the header of the per-frame flavour (GFW_JIT_PERFRAME, gfw_undistort_clip_params) — translation2d and FILL_WITH_BACKGROUND are not literals there (the
-// kernel reads them from each frame's slot), so they are left out: a use that slipped past the flavour would not compile.  perframe = 2: the moving-lens flavour
-// (gfw_undistort_clip_lens) — f, c, k and r_limit_sq come from each frame's lens slot and are left out in the same way (p1_f / p1_c, the first pass's copies of
-// f and c, are zero: the flavour takes the exact first pass, build_yuv_args sets no certified one up).
-static std::string bake_header(const GfwYuvArgs &Y_in, const FusedShape &S, int perframe = 0) {
-    const bool lens_pf = perframe >= 2;
+// CLIP_PER_FRAME (GFW_JIT_PERFRAME, gfw_undistort_clip_params): translation2d and FILL_WITH_BACKGROUND are not literals there (the kernel reads them from each
+// frame's slot), so they are left out: a use that slipped past the flavour would not compile.  CLIP_MOVING_LENS (gfw_undistort_clip_lens): f, c, k and r_limit_sq
+// come from each frame's lens slot and are left out in the same way (p1_f / p1_c, the first pass's copies of f and c, are zero: the flavour takes the exact first
+// pass, build_yuv_args sets no certified one up).
+static std::string bake_header(const GfwYuvArgs &Y_in, const FusedShape &S, ClipFlavour flavour) {
+    const bool in_slot = flavour >= CLIP_PER_FRAME, in_lens_slot = flavour >= CLIP_MOVING_LENS;      // where the kernel reads the field from
     GfwYuvArgs Y = Y_in;
     Y.tiles_y = tiles_y_of(Y, jit_rows(S.fast1 != 0));                                       // (the launch's own tiling: the argument block carries the ahead-of-time kernels')
     std::string o;
@@ -34,16 +34,16 @@ static std::string bake_header(const GfwYuvArgs &Y_in, const FusedShape &S, int 
     bake_i(o, "hrs", Y.hrs); bake_i(o, "model", Y.model); bake_i(o, "k_all_zero", Y.k_all_zero);
     bake_i(o, "background_mode", Y.background_mode); bake_i(o, "extras", Y.extras); bake_i(o, "ablate", 0);
     bake_i(o, "digital", (Y.extras & 2) ? Y.common.digital : 0);
-    if (!perframe) bake_i(o, "fill_bg", Y.fill_bg);
+    if (!in_slot) bake_i(o, "fill_bg", Y.fill_bg);
     bake_i(o, "rot_on", Y.rot_on); bake_i(o, "fix_range", Y.fix_range); bake_i(o, "checksum", Y.checksum);
     bake_i(o, "hstretch_div", Y.hstretch_div); bake_i(o, "vstretch_div", Y.vstretch_div); bake_f(o, "hstretch", Y.hstretch); bake_f(o, "vstretch", Y.vstretch);
     // (an audit build — GFW_OPT_KERNEL_VARIANT 3 / 4 on a clip whose certified first pass lives in specialised builds only, the radial models' — reads the counters' address from the arguments)
     o += Y.audit ? "#define GFW_BK_audit (A.audit)\n" : "#define GFW_BK_audit ((unsigned long long *)nullptr)\n";
     { char b[64]; snprintf(b, sizeof(b), "#define GFW_P1_RFORM (%d)\n", Y.p1_rform ? 1 : 0); o += b; }
     char nm[48];
-    for (int i = 0; i < 2; ++i) { if (!lens_pf) { snprintf(nm, sizeof(nm), "f_%d", i); bake_f(o, nm, Y.f[i]); snprintf(nm, sizeof(nm), "c_%d", i); bake_f(o, nm, Y.c[i]); }
-                                  if (!perframe) { snprintf(nm, sizeof(nm), "t2_%d", i); bake_f(o, nm, Y.t2[i]); } }
-    if (!lens_pf) {
+    for (int i = 0; i < 2; ++i) { if (!in_lens_slot) { snprintf(nm, sizeof(nm), "f_%d", i); bake_f(o, nm, Y.f[i]); snprintf(nm, sizeof(nm), "c_%d", i); bake_f(o, nm, Y.c[i]); }
+                                  if (!in_slot) { snprintf(nm, sizeof(nm), "t2_%d", i); bake_f(o, nm, Y.t2[i]); } }
+    if (!in_lens_slot) {
         for (int i = 0; i < 4; ++i) { snprintf(nm, sizeof(nm), "k_%d", i); bake_f(o, nm, Y.k[i]); }
         bake_f(o, "r_limit_sq", Y.r_limit_sq);
     }
@@ -99,18 +99,18 @@ static int jit_model_of(const GfwYuvArgs &Y) {
 // Whether an audit (GFW_OPT_KERNEL_VARIANT 3 / 4) takes a specialised audit build (GFW_JIT_AUDIT=1) rather than the ahead-of-time audit instantiations: where the
 // first pass to be audited lives in specialised builds only — a table over r (the radial models), and every launch of the per-frame flavour, whose certificate
 // half-width is each frame's own (its translation2d) and whose kernel no ahead-of-time instantiation is
-static bool jit_audit_build(const gfw_ctx *c, const GfwYuvArgs &Y, int perframe) {
-    return Y.audit && (Y.p1_rform || perframe) && (c->kernel_variant == 3 || c->kernel_variant == 4);
+static bool jit_audit_build(const gfw_ctx *c, const GfwYuvArgs &Y, ClipFlavour flavour) {
+    return Y.audit && (Y.p1_rform || flavour != CLIP_SHARED) && (c->kernel_variant == 3 || c->kernel_variant == 4);
 }
 // The definition list of a specialised build (with the bake header: everything that names the kernel; also behind the gfw_debug_jit_key hooks); `waves_out`: the budget
-static std::vector<std::string> jit_build_defs(const GfwYuvArgs &Y, const FusedShape &S, int perframe, bool audit_build, int *waves_out) {
+static std::vector<std::string> jit_build_defs(const GfwYuvArgs &Y, const FusedShape &S, ClipFlavour flavour, bool audit_build, int *waves_out) {
     const int jit_model = jit_model_of(Y);
     int waves = jit_waves(S, Y.matrix_count, jit_model, Y.extras, Y.checksum);
     // (the per-frame flavour of the lens-correction body keeps one more value of the frame alive through the pixel loop: at eight waves 24 bytes went to scratch
     // on 4K NV12, so it gets seven — as the checksum build does; every other body keeps its constant build's waves: tests/test_kernel_resources_perframe.py)
-    // (the moving-lens flavour, perframe = 2, keeps flavour 1's budget: compiled beside flavour 1 with the exact first pass it shows no scratch where that has none —
+    // (the moving-lens flavour keeps the per-frame flavour's budget: compiled beside flavour 1 with the exact first pass it shows no scratch where that has none —
     // 4K C2 53 registers against 54, the lens-correction body 72 / 72, the mesh body 80 / 80 with less scratch: tests/test_kernel_resources_perlens.py)
-    if (perframe && (Y.extras & 8) && waves == 8) waves = 7;
+    if (flavour != CLIP_SHARED && (Y.extras & 8) && waves == 8) waves = 7;
     char b[64];
     std::vector<std::string> defs;
     snprintf(b, sizeof(b), "GFW_FRAME_KIND=%d", S.kind); defs.push_back(b);
@@ -124,36 +124,33 @@ static std::vector<std::string> jit_build_defs(const GfwYuvArgs &Y, const FusedS
     snprintf(b, sizeof(b), "GFW_JIT_IL=%d", S.interleaved ? 1 : 0); defs.push_back(b);
     snprintf(b, sizeof(b), "GFW_JIT_RB=%d", jit_rows(S.fast1 != 0)); defs.push_back(b);
     snprintf(b, sizeof(b), "GFW_JIT_FAST1=%d", S.fast1 ? 1 : 0); defs.push_back(b);
-    if (perframe) defs.push_back(perframe >= 2 ? "GFW_JIT_PERFRAME=2" : "GFW_JIT_PERFRAME=1");                                // (absent otherwise: the other flavours' definition lists — their cache names — are unchanged)
+    if (flavour != CLIP_SHARED) { snprintf(b, sizeof(b), "GFW_JIT_PERFRAME=%d", (int)flavour); defs.push_back(b); }      // (absent for CLIP_SHARED: its definition lists — the cache names — are what they were before the flavours)
     if (const char *extra = getenv("GFW_JIT_DEFS")) split_defs(extra, defs);             // experiments: further ';'-separated definitions for the build
     if (audit_build) defs.push_back("GFW_JIT_AUDIT=1");
     if (waves_out) *waves_out = waves;
     return defs;
 }
 // The specialised kernel for this frame's arguments, or nullptr (not eligible / not wanted / not ready / failed): the caller then
-// launches the ahead-of-time kernel.  perframe: the per-frame flavour (gfw_undistort_clip_params): its launches take GfwClipArgsPF (gfw_jit_launch_pf), and its
-// key blanks the fields the frames carry in their slots as well — translation2d and the fill flag here, fov / lens-correction amount / margin / feather with `kp` —
-// so that one kernel serves the clip and the kJitAfter count runs on under a moving zoom centre.  perframe = 2: the moving-lens flavour (gfw_undistort_clip_lens):
-// its launches take GfwClipArgsPL (gfw_jit_launch_pl), and its key blanks the lens as well — f, c, k, r_limit_sq here, the refraction coefficient with `kp`, the
-// mesh with `common` — so that the count runs on under a moving lens.  (k_all_zero and every `extras` bit stay in the key: the kernel is compiled for them.)
-static hipFunction_t jit_for(gfw_ctx *c, const GfwYuvArgs &Y, const FusedShape &S, int perframe, int *grid) {
+// launches the ahead-of-time kernel.  `flavour`: of the launch the frame is for — the key blanks the fields the frames carry in that flavour's slots as well
+// (clip_blank_slots), so that one kernel serves the clip and the kJitAfter count runs on under a moving zoom centre (CLIP_PER_FRAME) or a moving lens
+// (CLIP_MOVING_LENS).  (k_all_zero and every `extras` bit stay in the key: the kernel is compiled for them.)
+static hipFunction_t jit_for(gfw_ctx *c, const GfwYuvArgs &Y, const FusedShape &S, ClipFlavour flavour, int *grid) {
     // every frame the fused kernel serves can be specialised: the fisheye model alone or under a digital lens (extras 0 / 2) takes the lean
     // projection (MODEL = 1); everything else the generic-model body with the lens model, the digital lens and the feature bits as literals
     // (MODEL = -1, or -2 with background mode 3 / the Sony mesh) — the run-time switch over 14 lens models folds to the one in use
     // (kernel variants and the audit take the ahead-of-time instantiations — except the audit of a table over r and of a per-frame launch: jit_audit_build)
-    const bool audit_build = jit_audit_build(c, Y, perframe);
+    const bool audit_build = jit_audit_build(c, Y, flavour);
     if (c->jit_mode == 0 || ((c->kernel_variant != 0 || Y.audit) && !audit_build) || Y.ablate) return nullptr;
     // the same clip as the previous frame?  Compared on the argument block itself with its per-frame fields blanked (the header text and the
     // cache lookup cost ~15 us of host time, a frame's worth of validation): header, key and function are rebuilt only when it changes
     GfwYuvArgs K = Y;
+    clip_blank_slots(K, flavour);
     for (int i = 0; i < 4; ++i) { K.pl[i].src = nullptr; K.pl[i].dst = nullptr; K.pl[i].src_len = 0; K.pl[i].dst_len = 0; }
     K.matrices = nullptr; K.p1_table = nullptr; K.p1_rho_max = 0.0f; K.p1_rho_scale = 0.0f; K.p1_eps = 0.0f; K.p1_ew = 0.0f; K.p1_em = 0.0f; K.p1_kmax = 0.0f; K.audit = Y.audit ? (unsigned long long *)1 : nullptr; K.ck_part = nullptr; K.grid_limit = 0;
     memset(K.p1_lat, 0, sizeof(K.p1_lat));
     memset(&K.kp, 0, sizeof(K.kp));
     { const int dig = K.common.digital; memset(&K.common, 0, sizeof(K.common)); K.common.digital = dig; }
-    if (perframe) { K.t2[0] = K.t2[1] = 0.0f; K.fill_bg = 0; }
-    if (perframe >= 2) { memset(K.f, 0, sizeof(K.f)); memset(K.c, 0, sizeof(K.c)); memset(K.k, 0, sizeof(K.k)); K.r_limit_sq = 0.0f; }
-    const JitKeyMisc misc = {S, c->tune_grid, perframe};
+    const JitKeyMisc misc = {S, c->tune_grid, flavour};
     const bool same = c->jit_key_valid && memcmp(&K, &c->jit_key, sizeof(K)) == 0 && memcmp(&misc, &c->jit_key_misc, sizeof(misc)) == 0;
     if (same) {
         if (c->jit_seen < (1 << 30)) ++c->jit_seen;
@@ -162,11 +159,11 @@ static hipFunction_t jit_for(gfw_ctx *c, const GfwYuvArgs &Y, const FusedShape &
     } else {
         jit_reset(c);
         c->jit_key = K; c->jit_key_misc = misc; c->jit_key_valid = true;
-        c->jit_header = bake_header(Y, S, perframe); c->jit_seen = 1;
+        c->jit_header = bake_header(Y, S, flavour); c->jit_seen = 1;
     }
     if (c->jit_mode == 1 && c->jit_seen < gfw_ctx::kJitAfter && !audit_build) return nullptr;          // one or two frames are not a clip
     int waves = 0;
-    const std::vector<std::string> defs = jit_build_defs(Y, S, perframe, audit_build, &waves);
+    const std::vector<std::string> defs = jit_build_defs(Y, S, flavour, audit_build, &waves);
     hipFunction_t fn = gfw_jit_get(c->device, c->arch, defs, c->jit_header, c->jit_mode == 2 || audit_build, &c->jit_info);
     if (!fn) { c->jit_dead = c->jit_info.state == GFW_JIT_FAILED || c->jit_info.state == GFW_JIT_UNAVAILABLE; return nullptr; }
     int g = c->tune_grid > 0 ? c->tune_grid : c->num_cus * waves;

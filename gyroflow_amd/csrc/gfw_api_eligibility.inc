@@ -189,7 +189,7 @@ static bool fused_eligible(const gfw_ctx *c, const FrameIn &F, const GfwPlane *l
     S.taps = p0.interpolation;
     return true;
 }
-static bool clip_lens_flavour(const ClipBatch *b);      // (gfw_api_clip.inc)
+static ClipFlavour flavour_of(const ClipBatch *b);      // (gfw_api_clip.inc)
 static int tiles_y_of(const GfwYuvArgs &Y, int rb) { return (Y.ch + 4 * rb - 1) / (4 * rb); }      // rows of tiles: each 4 x rb rows of the chroma height
 // `pending`: the frames held for a clip launch on this context, sent first if the first pass's table has to be rebuilt (the error returned is that launch's)
 static int build_yuv_args(gfw_ctx *c, const FrameIn &F, const GfwPlane *launches, ClipBatch *pending, GfwYuvArgs &Y, FusedShape &S, bool &served) {
@@ -199,7 +199,7 @@ static int build_yuv_args(gfw_ctx *c, const FrameIn &F, const GfwPlane *launches
     const gfw_kernel_params &p0 = F.params[0];
     bool fast1 = false;
     // (a launch of the moving-lens flavour takes the exact first pass: the certified pass's table, p1_f / p1_c and the envelope are functions of the lens)
-    if (!Y.extras && !clip_lens_flavour(pending) && p0.output_width <= 65535 && p0.output_height <= 65535) {               // deferred pixels are parked as (x | y << 16)
+    if (!Y.extras && flavour_of(pending) != CLIP_MOVING_LENS && p0.output_width <= 65535 && p0.output_height <= 65535) {               // deferred pixels are parked as (x | y << 16)
         const int rc = p1_setup(c, p0, h_matrices, F.matrix_count, pending, Y, fast1); if (rc != GFW_OK) return rc;
     }
     S.fast1 = fast1 ? 1 : 0;

@@ -100,7 +100,7 @@ extern "C" int gfw_debug_jit_key(int nplanes, const gfw_buffers *planes, const g
     c.model = distortion_model; c.digital = digital_lens; c.matrices_on_device = matrices_on_device; c.arch = arch;
     GfwYuvArgs Y; FusedShape S;
     { const int rc = dry_fused_args(c, 1, FrameIn{nplanes, planes, params, pixel_types, h_matrices, matrix_count, nullptr, 0}, nullptr, Y, S); if (rc != GFW_OK) return rc; }
-    return jit_key_out(arch, jit_build_defs(Y, S, false, false, nullptr), bake_header(Y, S), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
+    return jit_key_out(arch, jit_build_defs(Y, S, CLIP_SHARED, false, nullptr), bake_header(Y, S, CLIP_SHARED), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
 }
 
 // The same for the first launch of a gfw_undistort_clip_params call (the per-frame flavour): `planes` / `params` hold n_frames x nplanes entries as that call takes
@@ -114,14 +114,13 @@ extern "C" int gfw_debug_jit_key_clip_params(int n_frames, int nplanes, const gf
         set_error("bad arguments"); return GFW_ERR_INVALID_ARGUMENT; }
     gfw_ctx c;
     c.model = distortion_model; c.digital = digital_lens; c.matrices_on_device = matrices_on_device; c.arch = arch; c.kernel_variant = audit ? 3 : 0;
-    ClipBatch batch;
-    clip_params_batch(batch, n_frames, nplanes, params);
+    ClipBatch batch(CLIP_PER_FRAME, n_frames, nplanes, params);
     GfwYuvArgs Y; FusedShape S;
     { const int rc = dry_fused_args(c, n_frames, FrameIn{nplanes, planes, params, pixel_types, matrices_on_device ? nullptr : host_matrices[0], matrix_count, nullptr, 0}, &batch, Y, S);
       if (rc != GFW_OK) return rc; }
-    const bool audit_build = jit_audit_build(&c, Y, true);
+    const bool audit_build = jit_audit_build(&c, Y, CLIP_PER_FRAME);
     if ((c.kernel_variant != 0 || Y.audit) && !audit_build) return 1;             // (jit_for: the ahead-of-time kernel)
-    return jit_key_out(arch, jit_build_defs(Y, S, true, audit_build, nullptr), bake_header(Y, S, true), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
+    return jit_key_out(arch, jit_build_defs(Y, S, CLIP_PER_FRAME, audit_build, nullptr), bake_header(Y, S, CLIP_PER_FRAME), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
 }
 
 // The same for the first launch of a gfw_undistort_clip_lens call (the moving-lens flavour): `mesh_lens` as that call takes it (NULL: no frame has a mesh; the
@@ -132,25 +131,18 @@ extern "C" int gfw_debug_jit_key_clip_lens(int n_frames, int nplanes, const gfw_
                                            char *defs_out, size_t defs_cap, char *header_out, size_t header_cap, char *name_out, size_t name_cap) {
     if (!planes || !params || !pixel_types || !arch || n_frames < 1 || nplanes < 1 || nplanes > 4 || (!matrices_on_device && (!host_matrices || !host_matrices[0]))) {
         set_error("bad arguments"); return GFW_ERR_INVALID_ARGUMENT; }
-    bool moves = false;
-    for (int f = 0; f < n_frames; ++f) {
-        const gfw_kernel_params &p = params[(size_t)f * nplanes], &p0 = params[0];
-        moves = moves || (mesh_lens && mesh_lens[f]) || memcmp(p.f, p0.f, sizeof(p.f)) || memcmp(p.c, p0.c, sizeof(p.c)) || memcmp(p.k, p0.k, sizeof(p.k)) ||
-                memcmp(&p.r_limit, &p0.r_limit, sizeof(float)) || memcmp(&p.light_refraction_coefficient, &p0.light_refraction_coefficient, sizeof(float));
-    }
-    if (!moves) return gfw_debug_jit_key_clip_params(n_frames, nplanes, planes, params, pixel_types, distortion_model, digital_lens, host_matrices, matrix_count, matrices_on_device, 0, arch,
+    if (!lens_moves(n_frames, nplanes, params, [&](int f) { return mesh_lens && mesh_lens[f]; })) return gfw_debug_jit_key_clip_params(n_frames, nplanes, planes, params, pixel_types, distortion_model, digital_lens, host_matrices, matrix_count, matrices_on_device, 0, arch,
                                                      defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
     const size_t ml0 = mesh_lens ? mesh_lens[0] : 0;
     if (ml0 > GFW_MESH_MAX) { set_error("frame 0: mesh of %zu values", ml0); return GFW_ERR_BUFFER_SIZE_MISMATCH; }
     gfw_ctx c;
     c.model = distortion_model; c.digital = digital_lens; c.matrices_on_device = matrices_on_device; c.arch = arch;
-    ClipBatch batch;
-    batch.n_call = n_frames; batch.perframe = true; batch.lens = true;
+    ClipBatch batch(CLIP_MOVING_LENS, n_frames, nplanes, params);
     GfwYuvArgs Y; FusedShape S;
     static const float no_mesh[GFW_MESH_MAX] = {};      // (fused_eligible asks only whether a mesh is there)
     { const int rc = dry_fused_args(c, n_frames, FrameIn{nplanes, planes, params, pixel_types, matrices_on_device ? nullptr : host_matrices[0], matrix_count, ml0 ? no_mesh : nullptr, ml0}, &batch, Y, S);
       if (rc != GFW_OK) return rc; }
-    return jit_key_out(arch, jit_build_defs(Y, S, 2, false, nullptr), bake_header(Y, S, 2), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
+    return jit_key_out(arch, jit_build_defs(Y, S, CLIP_MOVING_LENS, false, nullptr), bake_header(Y, S, CLIP_MOVING_LENS), defs_out, defs_cap, header_out, header_cap, name_out, name_cap);
 }
 
 extern "C" int gfw_checksum64(gfw_ctx *c, const void *d_buf, size_t bytes, unsigned long long *d_out) {

@@ -15,8 +15,6 @@ hipFunction_t gfw_jit_get(int device, const std::string &arch, const std::vector
                           bool wait, GfwJitInfo *info);
 long gfw_jit_compile_only(const std::string &arch, const std::vector<std::string> &defines, const std::string &bake_header, std::string &log,
                           std::vector<char> *code_out);
-hipError_t gfw_jit_launch(hipFunction_t fn, const GfwClipArgs &C, int grid, hipStream_t s);
-hipError_t gfw_jit_launch_pl(hipFunction_t fn, const GfwClipArgsPL &C, int grid, hipStream_t s);      // the moving-lens flavour (GFW_JIT_PERFRAME=2)
-hipError_t gfw_jit_launch_pf(hipFunction_t fn, const GfwClipArgsPF &C, int grid, hipStream_t s);      // the per-frame flavour (GFW_JIT_PERFRAME)
+hipError_t gfw_jit_launch(hipFunction_t fn, const void *args, size_t bytes, int grid, hipStream_t s);      // args: the kernel's argument block (GfwClipArgs, or the flavour's: gfw_frame.h)
 bool gfw_jit_write_code_object(const std::string &path, const std::vector<char> &code);
 bool gfw_jit_read_symbol(hipFunction_t fn, const char *name, void *dst, size_t bytes);

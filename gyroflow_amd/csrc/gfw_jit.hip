@@ -362,18 +362,7 @@ bool gfw_jit_read_symbol(hipFunction_t fn, const char *name, void *dst, size_t b
     return false;
 }
 
-hipError_t gfw_jit_launch(hipFunction_t fn, const GfwClipArgs &C, int grid, hipStream_t s) {
-    size_t size = sizeof(GfwClipArgs);
-    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<GfwClipArgs *>(&C), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-    return hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 64, 4, 1, 0, s, nullptr, config);
-}
-hipError_t gfw_jit_launch_pl(hipFunction_t fn, const GfwClipArgsPL &C, int grid, hipStream_t s) {
-    size_t size = sizeof(GfwClipArgsPL);
-    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<GfwClipArgsPL *>(&C), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-    return hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 64, 4, 1, 0, s, nullptr, config);
-}
-hipError_t gfw_jit_launch_pf(hipFunction_t fn, const GfwClipArgsPF &C, int grid, hipStream_t s) {
-    size_t size = sizeof(GfwClipArgsPF);
-    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<GfwClipArgsPF *>(&C), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+hipError_t gfw_jit_launch(hipFunction_t fn, const void *args, size_t bytes, int grid, hipStream_t s) {
+    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<void *>(args), HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
     return hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 64, 4, 1, 0, s, nullptr, config);
 }
