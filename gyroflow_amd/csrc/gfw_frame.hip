@@ -96,6 +96,11 @@
                                  // read by the kernel, while source lines are re-read (L1 -> L2 read requests are 4.4 times the source bytes): 42.5 -> 41.9 us per C2 frame,
                                  // five alternating pairs, every "on" run below every "off" run (profiles/r07_row_memops.txt).  0: plain stores (A/B)
 #endif
+#ifndef GFW_PAIR_ROW
+#define GFW_PAIR_ROW 1           // round 8 (specialised builds): the bilinear branch-free row of a lane's pixel PAIR (DW == 2) fetches the second pixel's matrix row only in the lanes whose two rows differ
+                                 // (a real per-lane branch: the three loads under the narrowed exec mask, skipped by a wave without such a lane); the other lanes copy
+                                 // pixel 0's nine floats, which are the same memory.  0: two unconditional fetches (A/B).  profiles/r08_pair_rows.txt
+#endif
 #ifndef GFW_P1_LATTICE
 #define GFW_P1_LATTICE 1         // round 5: the certified first pass evaluated at the nodes of a lattice (every 8th luma column of the wave's first and last row: one node per
                                  // lane, once per tile) and interpolated bilinearly for the pixels, its curvature added to the certificate's half-width (DESIGN.md
@@ -1899,10 +1904,39 @@ __device__ __forceinline__ void gfw_yuv_body(const GfwYuvArgs &A_in, const GfwCl
                             }
                             // (the rows of a lane-row through a 16-row LDS window — one cooperative dwordx4 instead of these six fetches — measured 42.3 = 42.3 us per C2
                             //  frame with 27 % fewer L1 accesses: profiles/r05_c2_memory_path.txt; not kept)
-                            #pragma unroll
-                            for (int i = 0; i < DW; ++i) {
-                                const float *m = reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(matrices) + (uint32_t)row[i] * (uint32_t)(GFW_MAT_STRIDE * sizeof(float)));
-                                ma[i] = *reinterpret_cast<const float4 *>(m); mb[i] = *reinterpret_cast<const float4 *>(m + 4); m8[i] = m[8];
+                            auto row_ptr = [&](int rw) { return reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(matrices) + (uint32_t)rw * (uint32_t)(GFW_MAT_STRIDE * sizeof(float))); };
+                            if constexpr (GFW_PAIR_ROW != 0 && GFW_BAKE && DW == 2 && I == 2) {
+                                // the pair's pixels are horizontal neighbours: their rows differ only where the first pass crosses a half-integer between them (5 % of
+                                // C2's pairs: profiles/r08_pair_rows.txt), and equal rows are the same memory.  The second row is fetched by the lanes whose rows differ,
+                                // under their exec mask, right behind the first row's fetches; the other lanes copy pixel 0's nine floats in a branch of their own, so the
+                                // wait for pixel 0's row stands behind all six fetches.  A wave in which no lane differs, or every lane, skips one side (with one matrix
+                                // the comparison folds).  Bilinear only: under the bicubic and Lanczos4 taps the change measured nothing
+                                // (61.2 = 61.2, 139.2 = 139.3 us per C2 frame), and those builds keep their six fetches as one cluster
+                                // Specialised builds only: ahead of time (matrix_count an argument: nothing folds) C2 measured 66.9 = 66.9 us and the one-matrix NV12 clip
+                                // 17.2 against 17.1, so those kernels keep the parent's code
+                                const float *m = row_ptr(row[0]);
+                                ma[0] = *reinterpret_cast<const float4 *>(m); mb[0] = *reinterpret_cast<const float4 *>(m + 4); m8[0] = m[8];
+                                if (row[1] != row[0]) {
+                                    const float *m1 = row_ptr(row[1]);
+                                    ma[1] = *reinterpret_cast<const float4 *>(m1); mb[1] = *reinterpret_cast<const float4 *>(m1 + 4); m8[1] = m1[8];
+                                } else {
+#if !defined(GFW_HOST_INTERPRETER)
+                                    // (the empty statement keeps the branch: without it the copy moves in front of the `if`, and the second row's fetches wait for the
+                                    //  first's — measured 42.0 against 41.5 us; its operands are whole quads, so that the copies are four v_mov_b64 and one v_mov_b32)
+                                    typedef float Quad __attribute__((ext_vector_type(4)));
+                                    Quad qa = {ma[0].x, ma[0].y, ma[0].z, ma[0].w}, qb = {mb[0].x, mb[0].y, mb[0].z, mb[0].w}; float q8 = m8[0];
+                                    asm volatile("" : "+v"(qa), "+v"(qb), "+v"(q8));
+                                    ma[1] = float4{qa.x, qa.y, qa.z, qa.w}; mb[1] = float4{qb.x, qb.y, qb.z, qb.w}; m8[1] = q8;
+#else
+                                    ma[1] = ma[0]; mb[1] = mb[0]; m8[1] = m8[0];
+#endif
+                                }
+                            } else {
+                                #pragma unroll
+                                for (int i = 0; i < DW; ++i) {
+                                    const float *m = row_ptr(row[i]);
+                                    ma[i] = *reinterpret_cast<const float4 *>(m); mb[i] = *reinterpret_cast<const float4 *>(m + 4); m8[i] = m[8];
+                                }
                             }
                             if (GFW_BAKE && GFW_ABL(32)) {
                                 #pragma unroll
