@@ -27,12 +27,14 @@
 #include "gfw_sync_gyro.h"
 #include "gfw_sync_optim.h"
 #include "gfw_pose.h"
+#include "gfw_flow.h"
 #include "gfw_matrices_host.h"
 #include "gfw_zoom_host.h"
 #include "gfw_sync_host.h"
 #include "gfw_sync_gyro_host.h"
 #include "gfw_sync_optim_host.h"
 #include "gfw_pose_host.h"
+#include "gfw_flow_host.h"
 #include "gfw_clip_host.h"
 #include "gfw_jit.h"
 #include <stdlib.h>
@@ -124,6 +126,9 @@ struct gfw_ctx {
     // gfw_pose_almeida: pair firsts, points and draws staged the same way (work space: the visual search's)
     static constexpr int kPoseSlots = 2;
     StagingRing<kPoseSlots> pose_ring;
+    // gfw_flow_pyrlk: pairs, features and host frames staged the same way (work space: the visual search's)
+    static constexpr int kFlowSlots = 2;
+    StagingRing<kFlowSlots> flow_ring;
     // context-owned per-row tables built on the device (gfw_build_matrices): a small ring, built on copy_stream so that
     // frame N+1's table is produced while frame N is being warped; events order builder and consumer both ways
     struct BuiltSlot { DevBuf buf; Event built, consumed; };   // buf = rows + 4 doubles of builder scratch
@@ -1009,3 +1014,4 @@ int gfw_undistort_clip_lens(gfw_ctx *c, int n_frames, int nplanes, const gfw_buf
 #include "gfw_api_sync.inc"
 #include "gfw_api_sync_optim.inc"
 #include "gfw_api_pose.inc"
+#include "gfw_api_flow.inc"

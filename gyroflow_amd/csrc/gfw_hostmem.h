@@ -83,7 +83,7 @@ struct StagedBlock {
 struct CallOutputs {
     struct Part { void *caller; size_t at, bytes; };
     DevBuf &buf; const bool on_device;
-    static constexpr int kMaxParts = 5;              // the most any call adds: pose estimation (quaternions, rotations, best rounds, round inliers, round fits)
+    static constexpr int kMaxParts = 6;              // the most any call adds: optical flow (next, status, iterations, grid points, grid counts, pair firsts)
     Part parts[kMaxParts]; int n = 0; BlockLayout layout;
     CallOutputs(DevBuf &b, int out_on_device) : buf(b), on_device(out_on_device != 0) {}
     int add(void *caller, size_t bytes) { assert(n < kMaxParts); parts[n] = Part{caller, caller ? layout.add(bytes) : 0, bytes}; return n++; }

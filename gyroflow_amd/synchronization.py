@@ -10,7 +10,7 @@ range is ONE device call, ``Backend.sync_visual_search`` (gfw_sync_visual_search
 The 90 %-of-range acceptance rule (:137) and the range's middle timestamp are applied here.
 
 Not covered: clips with per-frame time offsets, stabiliser data or lens meshes, keyframed lens data or video rotation inside a range,
-suppress_rotation; the optical flow that produces the matched points, rs_sync itself.
+suppress_rotation; rs_sync itself.  (The optical flow that produces the matched points: ``optical_flow_pyrlk`` below.)
 
     offsets = synchronization.find_offsets_essential(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params, backend)
     initial_offset, search_size = synchronization.initial_offset_fast(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params, backend)
@@ -26,6 +26,12 @@ here.  The estimated rates are the caller's input: ``estimated_gyro`` makes them
 ``PoseAlmeida`` (estimate_pose/almeida.rs): one camera rotation per pair of frames from its matched optical-flow points, ALL pairs in one device call,
 ``Backend.pose_almeida`` (gfw_pose_almeida).  The reference draws its RANSAC rounds from an unseeded generator; here a seed decides them.  The other three pose
 methods are not covered.
+
+    matched = synchronization.optical_flow_pyrlk(frames, pairs, features=None, backend=backend)
+
+``OFOpenCVPyrLK::optical_flow_to`` (optical_flow/opencv_pyrlk.rs:63-119): the features of each pair's first frame tracked into its second frame by pyramidal
+Lucas-Kanade, ALL pairs in one device call, ``Backend.flow_pyrlk`` (gfw_flow_pyrlk); without features the points are the grid of opencv_dis.rs:62-119.  Corner
+detection (goodFeaturesToTrack), AKAZE and the DIS dense flow itself are not covered.
 
     optim = synchronization.OptimSync.new(raw_imu)
     points_ms, rank, ratio = optim.run(target_sync_points, trim_ranges_s, backend)
@@ -184,6 +190,20 @@ def scaled_axis(rot):
         return np.zeros(3)
     angle = float(np.arccos(min(max((m[0, 0] + m[1, 1] + m[2, 2] - 1.0) / 2.0, -1.0), 1.0)))
     return axis / norm * angle
+
+
+def optical_flow_pyrlk(frames, pairs, features=None, backend=None, width=None):
+    """``OFOpenCVPyrLK::optical_flow_to`` (optical_flow/opencv_pyrlk.rs:63-119) for all frame pairs in ONE device call (``Backend.flow_pyrlk``).  ``frames``: u8
+    gray planes [n][height][stride] (``width`` defaults to the stride); ``pairs``: [(first frame, second frame)] indices; ``features``: one [..][2] array of pixel
+    positions per frame, or None for the grid points of opencv_dis.rs:62-119 (computed on the device).  Returns one entry per pair: (pts1 f32 [k][2], pts2 f32
+    [k][2]) — the tracked points that pass the reference's filter (:88-100), in feature order — or None when fewer than 10 were kept (:107).  The entries are what
+    ``estimate_poses_almeida`` takes as its ``pairs``."""
+    if backend is None:
+        raise ValueError("optical_flow_pyrlk: no backend for the optical flow")
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    r = backend.flow_pyrlk(frames, frames.shape[2] if width is None else width, pairs, features)
+    first, a, b = r["pair_first"], r["points_a"], r["points_b"]
+    return [(a[first[p]:first[p + 1]], b[first[p]:first[p + 1]]) if first[p + 1] - first[p] >= 10 else None for p in range(len(first) - 1)]
 
 
 def pose_inputs(compute_params, flow_size, num_iters=200, num_samples=1000, inlier_angle=0.05):

@@ -508,6 +508,61 @@ class Backend:
         self._check(self.lib.gfw_pose_almeida(*args, q(quats), q(rot), q(best), q(ri) if rounds else None, q(rf) if rounds else None, 0))
         return (quats, rot, best, ri, rf) if rounds else (quats, rot, best)
 
+    @staticmethod
+    def _flow_features(features):
+        """one [n][2] array per frame -> (feat_first int32 [n_frames + 1], features f32 [total][2]) as gfw_flow_pyrlk takes them (kept alive by the caller)"""
+        lists = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, 2) for f in features]
+        first = np.zeros(len(lists) + 1, dtype=np.int32)
+        if lists:
+            first[1:] = np.cumsum([len(f) for f in lists])
+        pts = np.ascontiguousarray(np.concatenate(lists)) if lists else np.zeros((0, 2), dtype=np.float32)
+        return first, (pts if pts.size else np.zeros((1, 2), dtype=np.float32))
+
+    def flow_pyrlk(self, frames, width, pairs, features=None, iters=False, out_ptrs=None, shape=None, point_mode=None):
+        """`OFOpenCVPyrLK::optical_flow_to` (optical_flow/opencv_pyrlk.rs:63-119) of every frame pair in one device call (gfw_flow_pyrlk): pyramidal Lucas-Kanade
+        tracking of each pair's first-frame features into its second frame, and the filter of the result.
+
+        ``frames``: u8 gray planes as numpy [n][height][stride], or a device pointer (int) with ``shape`` = (n, height, stride); ``width`` <= stride; ``pairs``:
+        [(first frame, second frame)]; ``features``: one f32 [..][2] array per frame (pixels), or None for the grid points of opencv_dis.rs:62-119 computed on the
+        device.  Returns a dict: next f32 [raw][2], status u8 [raw], pair_first int32 [n_pairs + 1], points_a / points_b f32 [kept][2] (what pose_almeida and the
+        visual search take) — with ``iters`` also iters int32 [raw][4], in the grid mode also grid_points f32 [n][nodes][2] and grid_counts int32 [n] — or, with
+        ``out_ptrs`` = (next, status, iters or None, grid_points or None, grid_counts or None, pair_first, points_a, points_b) device pointers (points_a / points_b
+        with room for [raw][2]), the number of raw slots: in order on the stream."""
+        if isinstance(frames, (int, np.integer)):
+            n, height, stride = shape
+            fp, on_device, _keep = int(frames), 1, None
+        else:
+            _keep = np.ascontiguousarray(frames, dtype=np.uint8)
+            assert _keep.ndim == 3, "frames: [n][height][stride]"
+            n, height, stride = _keep.shape
+            fp, on_device = (_keep.ctypes.data if _keep.size else None), 0
+        mode = (1 if features is None else 0) if point_mode is None else int(point_mode)
+        cfg = abi.FlowPyrLKCfg(width=int(width), height=int(height), stride=int(stride), point_mode=mode)
+        pf = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        ff, ft = (None, None) if features is None else self._flow_features(features)
+        p = lambda a: a.ctypes.data if a is not None and a.size else None
+        args = (self.ctx, C.byref(cfg), fp, on_device, int(n), p(pf), len(pf), p(ff), p(ft))
+        raw = flow_raw_slots(width, height, pf, ff if mode == 0 else None) if (mode == 1 or ff is not None) else 0
+        if out_ptrs is not None:
+            self._check(self.lib.gfw_flow_pyrlk(*args, *out_ptrs, 1))
+            return raw
+        grid = mode == 1
+        nodes = flow_grid_nodes(width, height) if grid and width >= 15 else 0
+        room = max(raw, 1)                                       # (an output without slots still is an array of the caller's: at least one element)
+        o = {"next": np.zeros((room, 2), dtype=np.float32), "status": np.zeros(room, dtype=np.uint8), "iters": np.zeros((room, 4), dtype=np.int32),
+             "pair_first": np.zeros(len(pf) + 1, dtype=np.int32), "points_a": np.zeros((room, 2), dtype=np.float32), "points_b": np.zeros((room, 2), dtype=np.float32),
+             "grid_points": np.zeros((n, nodes, 2), dtype=np.float32), "grid_counts": np.zeros(n, dtype=np.int32)}
+        self._check(self.lib.gfw_flow_pyrlk(*args, o["next"].ctypes.data, o["status"].ctypes.data, o["iters"].ctypes.data if iters else None, p(o["grid_points"]) if grid else None,
+                                            p(o["grid_counts"]) if grid else None, o["pair_first"].ctypes.data, o["points_a"].ctypes.data, o["points_b"].ctypes.data, 0))
+        kept = int(o["pair_first"][-1]) if len(pf) else 0
+        o["next"], o["status"], o["iters"] = o["next"][:raw], o["status"][:raw], o["iters"][:raw]
+        o["points_a"], o["points_b"] = o["points_a"][:kept], o["points_b"][:kept]
+        if not iters:
+            del o["iters"]
+        if not grid:
+            del o["grid_points"], o["grid_counts"]
+        return o
+
     def synchronize(self):
         self._check(self.lib.gfw_synchronize(self.ctx))
 
@@ -530,6 +585,20 @@ class Backend:
         mp, mc, _m = _matrix_arg(matrices, matrix_count)
         meshp, meshn, _mesh = _mesh_arg(mesh)
         self._check(self.lib.gfw_undistort_frame(self.ctx, n, barr, parr, tarr, mp, mc, meshp, meshn))
+
+
+def flow_grid_nodes(width, height):
+    """raw slots of a pair in gfw_flow_pyrlk's grid mode: the nodes of `(0..w).step_by(w / 15)` x `(0..h).step_by(w / 15)` (opencv_dis.rs:64, :109-110)"""
+    step = int(width) // 15
+    return ((int(width) + step - 1) // step) * ((int(height) + step - 1) // step)
+
+
+def flow_raw_slots(width, height, pair_frames, feat_first=None):
+    """raw slots of a gfw_flow_pyrlk call: every pair's first-frame features (``feat_first`` [n_frames + 1]), or with None every node of the grid per pair"""
+    pf = np.asarray(pair_frames).reshape(-1, 2)
+    if feat_first is None:
+        return len(pf) * flow_grid_nodes(width, height)
+    return int(sum(int(feat_first[a + 1]) - int(feat_first[a]) for a in pf[:, 0] if 0 <= a < len(feat_first) - 1))
 
 
 def sync_coarse_count(mode, search_size_ms, scaled_fps):

@@ -614,8 +614,8 @@ int   gfw_zoom_smooth(const double *fov_minimal, int n, double adaptive_zoom_win
  * negative counts, a descending pair_first, more than 4096 points in a pair, width^2 + height^2 >= 2^32, params->flags with
  * HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA, a non-zero reserved slot, no tracks.
  * NOT covered: clips with per_frame_time_offsets, camera_stab_data or mesh_correction (in the reference the frame index, and so
- * the mesh, follows `timestamp - offs`); lens data or a video rotation keyframed inside a range; suppress_rotation; optical
- * flow, rs_sync.  (essential_matrix: gfw_sync_gyro_search below; optimsync: gfw_sync_optim_points below; pose estimation by the
+ * the mesh, follows `timestamp - offs`); lens data or a video rotation keyframed inside a range; suppress_rotation; corner detection (goodFeaturesToTrack), AKAZE and the DIS dense flow itself
+ * (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below), rs_sync.  (essential_matrix: gfw_sync_gyro_search below; optimsync: gfw_sync_optim_points below; pose estimation by the
  * Almeida method: gfw_pose_almeida below.) */
 typedef struct gfw_sync_search {
     int32_t width, height;            /* params.width / height: the bounds test (`w as f32`) and the readout divisor */
@@ -667,7 +667,7 @@ int   gfw_sync_visual_search(gfw_ctx *ctx, const gfw_kernel_params *params, cons
  * GFW_ERR_INVALID_ARGUMENT, the range named in gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative
  * counts, a negative or descending first array, a slice outside its array, a non-finite initial_offset or search_size, a negative
  * search_size, counts over the limits above.  Non-finite sample values are not rejected; the pick among NaN costs is unspecified.
- * NOT covered: optical flow, rs_sync itself, pose estimation other than the Almeida method (gfw_pose_almeida below; the series of
+ * NOT covered: corner detection (goodFeaturesToTrack), AKAZE and the DIS dense flow itself (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below), rs_sync itself, pose estimation other than the Almeida method (gfw_pose_almeida below; the series of
  * estimated samples is made of its rotations by gyroflow::estimated_gyro / gyroflow_amd.synchronization.estimated_gyro).
  *
  * gfw_lowpass_gyro: Lowpass::filter_gyro_forward_backward (filtering.rs:46-74) of xyz [n][3] f64 in place, on the host (no context):
@@ -755,7 +755,8 @@ int   gfw_sync_optim_points(gfw_ctx *ctx, const double *gyro, int64_t n_samples,
  * not match, params->flags with HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA, f / c that are not the f32 cast of camera_matrix,
  * sizes under 1, a negative or NaN inlier angle, a non-zero reserved slot.
  * NOT covered: lens data or a refraction coefficient that changes between the pairs of one call (one call per lens); the other three
- * pose methods (their solvers are not part of the reference tree); optical flow.
+ * pose methods (their solvers are not part of the reference tree); corner detection (goodFeaturesToTrack), AKAZE and the DIS dense flow itself (the matched points of the
+ * pyramidal Lucas-Kanade method: gfw_flow_pyrlk below).
  *
  * gfw_pose_draws (host only, no context): one valid set of draws per seed — not rand's sequence.  A counter-based generator:
  * word(seed, pair, round, k) = mix(mix(seed ^ (pair << 32 | round)) + k) with SplitMix64's finaliser as mix, an index below r the high
@@ -775,6 +776,48 @@ int   gfw_pose_almeida(gfw_ctx *ctx, const gfw_kernel_params *params, const gfw_
                        float *quats, double *rotations, int32_t *best, int32_t *round_inliers, float *round_fits, int out_on_device);
 int   gfw_pose_draws(uint64_t seed, const int32_t *pair_first, int n_pairs, int num_iters, int num_samples,
                      int32_t *triples, const int32_t *sample_first, int32_t *samples);
+
+/* ---- synchronization: pyramidal Lucas-Kanade optical flow of a clip's frame pairs in one device call ----
+ * optical_flow/opencv_pyrlk.rs:63-119 (`OFOpenCVPyrLK::optical_flow_to`, the reference's method 1): the given features of each pair's
+ * first frame are tracked into its second frame — calcOpticalFlowPyrLK with window 21 x 21, maxLevel 3, 30 iterations or eps 0.01,
+ * flags 0, minEigThreshold 1e-4 — and the tracked points are filtered (:88-100).  OpenCV's source is not part of the reference tree, so
+ * nothing reference-produced pins the tracker: the contract is tests/_flowstmt.py, the published pyramidal Lucas-Kanade scheme stated
+ * operation by operation with every window sum an INTEGER (fixed-point pixels, derivatives and bilinear samples, exact sums, one
+ * conversion to f32 per sum), which the device equals to the bit.  The statement is first held to tracking a planted motion.
+ *   cfg         width, height (both 24 .. 8192), stride >= width, point_mode, reserved = 0
+ *   frames      n_frames u8 gray planes back to back, frame f at frames + f * stride * height; host memory, or device memory with
+ *               frames_on_device (it must stay valid until the stream has run the call)
+ *   pair_frames [n_pairs][2] (first frame, second frame) indices
+ *   point_mode 0: feat_first [n_frames + 1] ascending, frame f owns features[feat_first[f] .. feat_first[f + 1] - 1] ([..][2] f32 pixels,
+ *               host memory); pair p has the features of its first frame.  A feature that is not finite or lies outside
+ *               [0, w) x [0, h) is not tracked: status 0, next = the feature
+ *   point_mode 1: feat_first / features are ignored; the points are the grid of opencv_dis.rs:62-119 (step = w / 15, the texture
+ *               variance of a max(10, round(0.02 w)) window > 3.0) computed on the device from each frame; every pair has
+ *               nodes = ceil(w / step) * ceil(h / step) raw slots, of which the first grid_counts[first frame] are used (the rest:
+ *               status 0, next 0).  grid_points NULL or [n_frames][nodes][2] f32 (kept nodes first, in the reference's loop order, then
+ *               zeros), grid_counts NULL or [n_frames] int32
+ *   raw outputs over every (pair, feature), pair after pair: next [raw][2] f32, status [raw] u8, iters NULL or [raw][4] int32 (the
+ *               updates made at level 0 .. 3, -1 for a level not built or skipped)
+ *   compacted   out_pair_first [n_pairs + 1] int32 and points_a / points_b [..][2] f32: the pairs' kept points in feature order (status
+ *               1, both points in [0, w) x [0, h)) — exactly gfw_pose_almeida's and gfw_sync_visual_*'s pair_first / points_a /
+ *               points_b.  Room for [raw][2] each; only the kept entries are written.  The "at least 10" rule (:107) is the caller's
+ *   limits      at most 4096 features a frame (grid nodes in mode 1), 65535 pairs, 4096 frames, 2 GiB staged in all
+ * At most seven launches for any clip (three pyramid levels, the grid, the tracker, a scan, the compaction), in order on the context's
+ * stream; outputs are host or device memory (out_on_device); with device outputs an asynchronous context returns
+ * without waiting.  n_pairs = 0 succeeds and writes nothing.  Rejected with GFW_ERR_INVALID_ARGUMENT, the pair or frame named in
+ * gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative counts, a descending feat_first, a frame index out
+ * of range, a pair of a frame with itself, sides outside 24 .. 8192, stride < width, mode 0 without features, counts over the limits,
+ * a non-zero reserved slot.
+ * NOT covered: corner detection (goodFeaturesToTrack), AKAZE, the DIS dense flow itself. */
+typedef struct gfw_flow_pyrlk_cfg {
+    int32_t width, height, stride;         /* of every frame of the call */
+    int32_t point_mode;                    /* 0 the caller's features, 1 the grid points */
+    int32_t reserved;                      /* 0 */
+} gfw_flow_pyrlk_cfg;
+int   gfw_flow_pyrlk(gfw_ctx *ctx, const gfw_flow_pyrlk_cfg *cfg, const void *frames, int frames_on_device, int n_frames,
+                     const int32_t *pair_frames, int n_pairs, const int32_t *feat_first, const float *features,
+                     float *next, uint8_t *status, int32_t *iters, float *grid_points, int32_t *grid_counts,
+                     int32_t *out_pair_first, float *points_a, float *points_b, int out_on_device);
 
 /* First-pass audit of the fused kernel (GFW_OPT_KERNEL_VARIANT = 3): counters8 = {certified pixels,
  * certified-but-different-from-exact (must stay 0), queued to the exact path, queue overflows,

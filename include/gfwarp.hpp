@@ -520,6 +520,40 @@ inline std::vector<PoseResult> estimate_poses_almeida(gfw_ctx *ctx, const Kernel
     }
     return out;
 }
+// ---- synchronization/optical_flow/opencv_pyrlk.rs:63-119 over gfw_flow_pyrlk: `OFOpenCVPyrLK::optical_flow_to` for ALL frame pairs in one device call.  `frames`:
+// n u8 gray planes back to back (host memory), `pairs` (first frame, second frame); `features`: one list per frame, or empty for the grid points of
+// opencv_dis.rs:62-119 (computed on the device).  One FlowPair per pair, in feature order; has_points only with at least 10 kept points (:107) — what
+// estimate_poses_almeida takes.
+inline std::vector<FlowPair> optical_flow_pyrlk(gfw_ctx *ctx, const uint8_t *frames, int n_frames, int width, int height, int stride, const std::vector<std::pair<int, int>> &pairs,
+                                                const std::vector<std::vector<std::pair<float, float>>> &features = {}) {
+    std::vector<FlowPair> out(pairs.size());
+    if (pairs.empty()) return out;
+    if (!ctx) throw GyroflowCoreError(GyroflowCoreError::Unknown, "optical_flow_pyrlk: no backend context for the optical flow");
+    const bool grid = features.empty();
+    if (!grid && (int)features.size() != n_frames) throw GyroflowCoreError(GyroflowCoreError::Unknown, "optical_flow_pyrlk: one feature list per frame");
+    gfw_flow_pyrlk_cfg cfg = {width, height, stride, grid ? 1 : 0, 0};
+    std::vector<int32_t> pf, first{0};
+    std::vector<float> feats;
+    for (const auto &p : pairs) { pf.push_back(p.first); pf.push_back(p.second); }
+    for (const auto &f : features) { for (const auto &pt : f) { feats.push_back(pt.first); feats.push_back(pt.second); } first.push_back((int32_t)(feats.size() / 2)); }
+    size_t raw = 0;
+    const int step = width >= 15 ? width / 15 : 1;
+    const size_t nodes = (size_t)((width + step - 1) / step) * (size_t)((height + step - 1) / step);
+    for (const auto &p : pairs) raw += grid ? nodes : (p.first >= 0 && p.first < n_frames ? features[(size_t)p.first].size() : 0);
+    std::vector<float> next(raw * 2 + 2), a(raw * 2 + 2), b(raw * 2 + 2);
+    std::vector<uint8_t> status(raw + 1);
+    std::vector<int32_t> pair_first(pairs.size() + 1);
+    feats.push_back(0.0f);
+    const int rc = gfw_flow_pyrlk(ctx, &cfg, frames, 0, n_frames, pf.data(), (int)pairs.size(), grid ? nullptr : first.data(), grid ? nullptr : feats.data(),
+                                  next.data(), status.data(), nullptr, nullptr, nullptr, pair_first.data(), a.data(), b.data(), 0);
+    if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+    for (size_t p = 0; p < pairs.size(); ++p) {
+        if (pair_first[p + 1] - pair_first[p] < 10) continue;
+        out[p].has_points = true;
+        for (int k = pair_first[p]; k < pair_first[p + 1]; ++k) { out[p].points.push_back({a[(size_t)k * 2], a[(size_t)k * 2 + 1]}); out[p].next_points.push_back({b[(size_t)k * 2], b[(size_t)k * 2 + 1]}); }
+    }
+    return out;
+}
 // `results`: every analysed frame's timestamp_us -> its euler, or nullopt without a rotation (a sample sits midway to the NEXT analysed frame, :312-315);
 // final_pass interpolates a missing rotation linearly between its neighbours that have one (:284-305); lpf > 0 (Hz) runs gfw_lowpass_gyro (:349-357)
 inline std::map<int64_t, TimeIMU> estimated_gyro(const std::map<int64_t, std::optional<std::array<double, 3>>> &results, double fps, double lpf = 0.0, bool final_pass = false) {
