@@ -127,6 +127,14 @@ class FlowPyrLKCfg(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("point_mode", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CornersCfg(C.Structure):
+    """``gfw_corners_cfg``: what every frame of a Shi-Tomasi corner-detection call shares."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("max_corners", C.c_int32), ("quality", C.c_float), ("min_distance", C.c_float),
+                ("max_workspace_mb", C.c_int32), ("reserved", C.c_int32)]
+
+
+CORNERS_MAX, CORNERS_FRAMES_MAX, CORNERS_SIDE_MIN, CORNERS_SIDE_MAX, CORNERS_WORKSPACE_MB = 4096, 4096, 3, 8192, 512      # gfw_corners_shi_tomasi
+CORNERS_RING_SLOTS = 2           # staging slots of gfw_corners_shi_tomasi
 FLOW_FEATURES_MAX, FLOW_PAIRS_MAX, FLOW_FRAMES_MAX, FLOW_SIDE_MIN, FLOW_SIDE_MAX = 4096, 65535, 4096, 24, 8192      # gfw_flow_pyrlk
 FLOW_RING_SLOTS = 2              # staging slots of gfw_flow_pyrlk
 POSE_PAIR_POINTS_MAX, POSE_PAIRS_MAX, POSE_ROUNDS_MAX = 4096, 65535, 1024      # gfw_pose_almeida
@@ -228,6 +236,7 @@ def bind(lib):
     lib.gfw_pose_almeida.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(PoseAlmeidaCfg), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_pose_almeida.restype = i32
     lib.gfw_pose_draws.argtypes = [C.c_uint64, vp, i32, i32, i32, vp, vp, vp]; lib.gfw_pose_draws.restype = i32
     lib.gfw_flow_pyrlk.argtypes = [vp, C.POINTER(FlowPyrLKCfg), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_flow_pyrlk.restype = i32
+    lib.gfw_corners_shi_tomasi.argtypes = [vp, C.POINTER(CornersCfg), vp, i32, i32, vp, vp, vp, vp, vp, i32]; lib.gfw_corners_shi_tomasi.restype = i32
     lib.gfw_pack_matrices.argtypes = [vp, i32, vp]; lib.gfw_pack_matrices.restype = i32
     lib.gfw_checksum64.argtypes = [vp, vp, sz, vp]; lib.gfw_checksum64.restype = i32
     lib.gfw_set_frame_checksums.argtypes = [vp, vp, sz]; lib.gfw_set_frame_checksums.restype = i32
@@ -257,7 +266,7 @@ EXPORTS = ["gfw_abi_version", "gfw_list_devices", "gfw_set_device", "gfw_get_inf
            "gfw_build_matrices_batch_stab", "gfw_zoom_fovs_stab", "gfw_sync_visual_costs", "gfw_sync_visual_search",
            "gfw_lowpass_gyro", "gfw_sync_gyro_costs", "gfw_sync_gyro_search",
            "gfw_optim_tables", "gfw_optim_resample", "gfw_sync_optim_rank", "gfw_sync_optim_points",
-           "gfw_pose_almeida", "gfw_pose_draws", "gfw_flow_pyrlk"]
+           "gfw_pose_almeida", "gfw_pose_draws", "gfw_flow_pyrlk", "gfw_corners_shi_tomasi"]
 
 
 def load_library(path=None):

@@ -28,6 +28,7 @@
 #include "gfw_sync_optim.h"
 #include "gfw_pose.h"
 #include "gfw_flow.h"
+#include "gfw_corners.h"
 #include "gfw_matrices_host.h"
 #include "gfw_zoom_host.h"
 #include "gfw_sync_host.h"
@@ -35,6 +36,7 @@
 #include "gfw_sync_optim_host.h"
 #include "gfw_pose_host.h"
 #include "gfw_flow_host.h"
+#include "gfw_corners_host.h"
 #include "gfw_clip_host.h"
 #include "gfw_jit.h"
 #include <stdlib.h>
@@ -129,6 +131,9 @@ struct gfw_ctx {
     // gfw_flow_pyrlk: pairs, features and host frames staged the same way (work space: the visual search's)
     static constexpr int kFlowSlots = 2;
     StagingRing<kFlowSlots> flow_ring;
+    // gfw_corners_shi_tomasi: the frames' maxima and candidate counts (zeros) and host frames staged the same way (work space: the visual search's)
+    static constexpr int kCornersSlots = 2;
+    StagingRing<kCornersSlots> corners_ring;
     // context-owned per-row tables built on the device (gfw_build_matrices): a small ring, built on copy_stream so that
     // frame N+1's table is produced while frame N is being warped; events order builder and consumer both ways
     struct BuiltSlot { DevBuf buf; Event built, consumed; };   // buf = rows + 4 doubles of builder scratch
@@ -1015,3 +1020,4 @@ int gfw_undistort_clip_lens(gfw_ctx *c, int n_frames, int nplanes, const gfw_buf
 #include "gfw_api_sync_optim.inc"
 #include "gfw_api_pose.inc"
 #include "gfw_api_flow.inc"
+#include "gfw_api_corners.inc"

@@ -30,8 +30,13 @@ methods are not covered.
     matched = synchronization.optical_flow_pyrlk(frames, pairs, features=None, backend=backend)
 
 ``OFOpenCVPyrLK::optical_flow_to`` (optical_flow/opencv_pyrlk.rs:63-119): the features of each pair's first frame tracked into its second frame by pyramidal
-Lucas-Kanade, ALL pairs in one device call, ``Backend.flow_pyrlk`` (gfw_flow_pyrlk); without features the points are the grid of opencv_dis.rs:62-119.  Corner
-detection (goodFeaturesToTrack), AKAZE and the DIS dense flow itself are not covered.
+Lucas-Kanade, ALL pairs in one device call, ``Backend.flow_pyrlk`` (gfw_flow_pyrlk); without features the points are the grid of opencv_dis.rs:62-119.  AKAZE
+and the DIS dense flow itself are not covered.
+
+    features = synchronization.detect_features_pyrlk(frames, backend)
+
+``OFOpenCVPyrLK::detect_features`` (optical_flow/opencv_pyrlk.rs:25-42): the Shi-Tomasi corners of ALL frames in one device call,
+``Backend.corners_shi_tomasi`` (gfw_corners_shi_tomasi) — the ``features`` of ``optical_flow_pyrlk``.
 
     optim = synchronization.OptimSync.new(raw_imu)
     points_ms, rank, ratio = optim.run(target_sync_points, trim_ranges_s, backend)
@@ -204,6 +209,18 @@ def optical_flow_pyrlk(frames, pairs, features=None, backend=None, width=None):
     r = backend.flow_pyrlk(frames, frames.shape[2] if width is None else width, pairs, features)
     first, a, b = r["pair_first"], r["points_a"], r["points_b"]
     return [(a[first[p]:first[p + 1]], b[first[p]:first[p + 1]]) if first[p + 1] - first[p] >= 10 else None for p in range(len(first) - 1)]
+
+
+def detect_features_pyrlk(frames, backend=None, width=None):
+    """``OFOpenCVPyrLK::detect_features`` (optical_flow/opencv_pyrlk.rs:25-42) for all frames in ONE device call (``Backend.corners_shi_tomasi``) with the
+    reference's parameters, good_features_to_track(img, 200, 0.01, 10.0, ..).  ``frames``: u8 gray planes [n][height][stride] (``width`` defaults to the stride).
+    Returns one f32 [k][2] array of pixel positions per frame, in pick order: exactly the ``features`` argument of ``optical_flow_pyrlk``."""
+    if backend is None:
+        raise ValueError("detect_features_pyrlk: no backend for the corner detection")
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    r = backend.corners_shi_tomasi(frames, frames.shape[2] if width is None else width, max_corners=200, quality=0.01, min_distance=10.0)
+    first, feats = r["feat_first"], r["features"]
+    return [feats[first[f]:first[f + 1]] for f in range(len(first) - 1)]
 
 
 def pose_inputs(compute_params, flow_size, num_iters=200, num_samples=1000, inlier_angle=0.05):

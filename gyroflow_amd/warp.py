@@ -563,6 +563,43 @@ class Backend:
             del o["grid_points"], o["grid_counts"]
         return o
 
+    def corners_shi_tomasi(self, frames, width, max_corners=200, quality=0.01, min_distance=10.0, scores=False, packed=True, max_workspace_mb=0, out_ptrs=None, shape=None):
+        """`OFOpenCVPyrLK::detect_features` (optical_flow/opencv_pyrlk.rs:25-42: good_features_to_track(img, 200, 0.01, 10.0, ..)) of every frame in one device call
+        (gfw_corners_shi_tomasi): Shi-Tomasi corners by the minimum eigenvalue of the 3 x 3 gradient covariance, thresholded at ``quality`` of the frame's maximum,
+        picked in descending order at least ``min_distance`` apart.
+
+        ``frames``: u8 gray planes as numpy [n][height][stride], or a device pointer (int) with ``shape`` = (n, height, stride); ``width`` <= stride.  Returns a dict:
+        corners f32 [n][max_corners][2] (kept first, in pick order, then zeros), counts int32 [n] — with ``scores`` also scores f32 [n][max_corners], with ``packed``
+        also feat_first int32 [n + 1] and features f32 [kept][2], what flow_pyrlk takes as its features — or, with ``out_ptrs`` = (corners, scores or None, counts,
+        feat_first or None, features or None) device pointers (features with room for [n * max_corners][2]), None: in order on the stream."""
+        if isinstance(frames, (int, np.integer)):
+            n, height, stride = shape
+            fp, on_device, _keep = int(frames), 1, None
+        else:
+            _keep = np.ascontiguousarray(frames, dtype=np.uint8)
+            assert _keep.ndim == 3, "frames: [n][height][stride]"
+            n, height, stride = _keep.shape
+            fp, on_device = (_keep.ctypes.data if _keep.size else None), 0
+        cfg = abi.CornersCfg(width=int(width), height=int(height), stride=int(stride), max_corners=int(max_corners), quality=float(quality), min_distance=float(min_distance),
+                             max_workspace_mb=int(max_workspace_mb))
+        args = (self.ctx, C.byref(cfg), fp, on_device, int(n))
+        if out_ptrs is not None:
+            self._check(self.lib.gfw_corners_shi_tomasi(*args, *out_ptrs, 1))
+            return None
+        room = max(int(n) * max(int(max_corners), 0), 1)             # (an output without slots still is an array of the caller's: at least one element)
+        o = {"corners": np.zeros((room, 2), dtype=np.float32), "scores": np.zeros(room, dtype=np.float32), "counts": np.zeros(max(n, 1), dtype=np.int32),
+             "feat_first": np.zeros(n + 1, dtype=np.int32), "features": np.zeros((room, 2), dtype=np.float32)}
+        self._check(self.lib.gfw_corners_shi_tomasi(*args, o["corners"].ctypes.data, o["scores"].ctypes.data if scores else None, o["counts"].ctypes.data,
+                                                    o["feat_first"].ctypes.data if packed else None, o["features"].ctypes.data if packed else None, 0))
+        m = max(int(max_corners), 0)
+        o["corners"], o["scores"], o["counts"] = o["corners"][:n * m].reshape(n, m, 2), o["scores"][:n * m].reshape(n, m), o["counts"][:n]
+        o["features"] = o["features"][:int(o["feat_first"][-1])]
+        if not scores:
+            del o["scores"]
+        if not packed:
+            del o["feat_first"], o["features"]
+        return o
+
     def synchronize(self):
         self._check(self.lib.gfw_synchronize(self.ctx))
 

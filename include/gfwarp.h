@@ -614,8 +614,8 @@ int   gfw_zoom_smooth(const double *fov_minimal, int n, double adaptive_zoom_win
  * negative counts, a descending pair_first, more than 4096 points in a pair, width^2 + height^2 >= 2^32, params->flags with
  * HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA, a non-zero reserved slot, no tracks.
  * NOT covered: clips with per_frame_time_offsets, camera_stab_data or mesh_correction (in the reference the frame index, and so
- * the mesh, follows `timestamp - offs`); lens data or a video rotation keyframed inside a range; suppress_rotation; corner detection (goodFeaturesToTrack), AKAZE and the DIS dense flow itself
- * (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below), rs_sync.  (essential_matrix: gfw_sync_gyro_search below; optimsync: gfw_sync_optim_points below; pose estimation by the
+ * the mesh, follows `timestamp - offs`); lens data or a video rotation keyframed inside a range; suppress_rotation; AKAZE and the DIS dense flow itself
+ * (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below; its corner detection: gfw_corners_shi_tomasi below), rs_sync.  (essential_matrix: gfw_sync_gyro_search below; optimsync: gfw_sync_optim_points below; pose estimation by the
  * Almeida method: gfw_pose_almeida below.) */
 typedef struct gfw_sync_search {
     int32_t width, height;            /* params.width / height: the bounds test (`w as f32`) and the readout divisor */
@@ -667,7 +667,7 @@ int   gfw_sync_visual_search(gfw_ctx *ctx, const gfw_kernel_params *params, cons
  * GFW_ERR_INVALID_ARGUMENT, the range named in gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative
  * counts, a negative or descending first array, a slice outside its array, a non-finite initial_offset or search_size, a negative
  * search_size, counts over the limits above.  Non-finite sample values are not rejected; the pick among NaN costs is unspecified.
- * NOT covered: corner detection (goodFeaturesToTrack), AKAZE and the DIS dense flow itself (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below), rs_sync itself, pose estimation other than the Almeida method (gfw_pose_almeida below; the series of
+ * NOT covered: AKAZE and the DIS dense flow itself (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below; its corner detection: gfw_corners_shi_tomasi below), rs_sync itself, pose estimation other than the Almeida method (gfw_pose_almeida below; the series of
  * estimated samples is made of its rotations by gyroflow::estimated_gyro / gyroflow_amd.synchronization.estimated_gyro).
  *
  * gfw_lowpass_gyro: Lowpass::filter_gyro_forward_backward (filtering.rs:46-74) of xyz [n][3] f64 in place, on the host (no context):
@@ -755,8 +755,8 @@ int   gfw_sync_optim_points(gfw_ctx *ctx, const double *gyro, int64_t n_samples,
  * not match, params->flags with HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA, f / c that are not the f32 cast of camera_matrix,
  * sizes under 1, a negative or NaN inlier angle, a non-zero reserved slot.
  * NOT covered: lens data or a refraction coefficient that changes between the pairs of one call (one call per lens); the other three
- * pose methods (their solvers are not part of the reference tree); corner detection (goodFeaturesToTrack), AKAZE and the DIS dense flow itself (the matched points of the
- * pyramidal Lucas-Kanade method: gfw_flow_pyrlk below).
+ * pose methods (their solvers are not part of the reference tree); AKAZE and the DIS dense flow itself (the matched points of the
+ * pyramidal Lucas-Kanade method: gfw_flow_pyrlk below, its features: gfw_corners_shi_tomasi below).
  *
  * gfw_pose_draws (host only, no context): one valid set of draws per seed — not rand's sequence.  A counter-based generator:
  * word(seed, pair, round, k) = mix(mix(seed ^ (pair << 32 | round)) + k) with SplitMix64's finaliser as mix, an index below r the high
@@ -808,7 +808,7 @@ int   gfw_pose_draws(uint64_t seed, const int32_t *pair_first, int n_pairs, int 
  * gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative counts, a descending feat_first, a frame index out
  * of range, a pair of a frame with itself, sides outside 24 .. 8192, stride < width, mode 0 without features, counts over the limits,
  * a non-zero reserved slot.
- * NOT covered: corner detection (goodFeaturesToTrack), AKAZE, the DIS dense flow itself. */
+ * NOT covered: AKAZE, the DIS dense flow itself.  (Corner detection, goodFeaturesToTrack: gfw_corners_shi_tomasi below.) */
 typedef struct gfw_flow_pyrlk_cfg {
     int32_t width, height, stride;         /* of every frame of the call */
     int32_t point_mode;                    /* 0 the caller's features, 1 the grid points */
@@ -818,6 +818,49 @@ int   gfw_flow_pyrlk(gfw_ctx *ctx, const gfw_flow_pyrlk_cfg *cfg, const void *fr
                      const int32_t *pair_frames, int n_pairs, const int32_t *feat_first, const float *features,
                      float *next, uint8_t *status, int32_t *iters, float *grid_points, int32_t *grid_counts,
                      int32_t *out_pair_first, float *points_a, float *points_b, int out_on_device);
+
+/* ---- synchronization: Shi-Tomasi corner detection of a clip's frames in one device call ----
+ * optical_flow/opencv_pyrlk.rs:25-42 (`OFOpenCVPyrLK::detect_features`, the first link of the reference's method 1): the features of a
+ * frame are good_features_to_track(img, 200, 0.01, 10.0, no mask, blockSize 3, useHarris false, 0.04).  OpenCV's source is not part of
+ * the reference tree, so nothing reference-produced pins the detector: the contract is tests/_cornerstmt.py, the published Shi-Tomasi /
+ * goodFeaturesToTrack scheme stated operation by operation, which the device equals to the bit:
+ *   Dx, Dy     the 3 x 3 Sobel of the u8 image as int32 on reflect-101 indices (-1 -> 1, n -> n - 2)
+ *   S          the 3 x 3 unnormalised box sums of Dx^2, Dx Dy, Dy^2, the PRODUCT maps reflected (reflect-101), as OpenCV filters `cov`;
+ *              every sum is an exact integer below 2^24
+ *   e          (a + c) - sqrtf((a - c)^2 + b^2) with a = Sxx * 0.5, c = Syy * 0.5, b = Sxy in f32, one rounding per operation; OpenCV's
+ *              scale 1 / (12 * 255) is dropped (the selection depends only on e relative to the frame's maximum): scores are this e
+ *   threshold  t = max(max over all pixels of e, 0) * quality; candidates are the interior pixels (1 .. n - 2) with e > t and e >= all
+ *              eight neighbours (plateaus count in full)
+ *   pick       in descending order of the key bits(e) << 32 | (y * width + x) (on a tie the larger pixel index first) a candidate is
+ *              accepted unless an accepted one lies closer than min_distance: (float)(dx^2 + dy^2) < min_distance * min_distance;
+ *              min_distance < 1 accepts everything; at most max_corners.  A corner is (float x, float y), in pick order
+ *   cfg        width, height (both 3 .. 8192), stride >= width (the padding is not read), max_corners 1 .. 4096, quality in (0, 1],
+ *              min_distance in [0, 1024], max_workspace_mb (below), reserved = 0
+ *   frames     n_frames u8 gray planes back to back, frame f at frames + f * stride * height; host memory, or device memory with
+ *              frames_on_device (it must stay valid until the stream has run the call) — gfw_flow_pyrlk's contract
+ *   corners    [n_frames][max_corners][2] f32: the kept corners first, in pick order, then zeros
+ *   scores     NULL or [n_frames][max_corners] f32; counts [n_frames] int32
+ *   feat_first [n_frames + 1] int32 and features [..][2] f32 (room for [n_frames * max_corners][2], only the kept entries written): the
+ *              packed form gfw_flow_pyrlk takes in point mode 0.  Both NULL or both given
+ * A frame's candidate list has room for EVERY interior pixel (8 bytes each; a plateau image makes all of them candidates): no overflow
+ * path exists.  The call's frames are therefore dealt into batches whose lists fit max_workspace_mb MiB of device work space (0: 512,
+ * which holds one frame of 8192 x 8192); a value too small for ONE frame is rejected with the need named.  Launches: two per batch plus
+ * two (the scan and the pack of feat_first / features, only where they are asked for), in order on the context's stream; the pick of a
+ * frame takes at most max_corners rounds of ceil(candidates / 256) steps.  Outputs are host or device memory (out_on_device); with device
+ * outputs an asynchronous context returns without waiting.  n_frames = 0 succeeds and writes nothing.  Rejected with
+ * GFW_ERR_INVALID_ARGUMENT, the reason in gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative counts, sides
+ * or stride out of range, max_corners / quality / min_distance out of range or not finite, a negative max_workspace_mb, a non-zero
+ * reserved slot, more than 4096 frames, host frames over 2 GiB in all.
+ * NOT covered: a mask, the Harris response (the reference passes neither); AKAZE, the DIS dense flow itself. */
+typedef struct gfw_corners_cfg {
+    int32_t width, height, stride;      /* of every frame; sides 3 .. 8192, stride >= width */
+    int32_t max_corners;                /* 1 .. 4096 (gfw_flow_pyrlk's features-a-frame limit); the reference: 200 */
+    float   quality, min_distance;      /* the reference: 0.01, 10.0; quality finite in (0, 1], min_distance finite in [0, 1024] */
+    int32_t max_workspace_mb;           /* 0 = default (512); the candidate lists of a batch */
+    int32_t reserved;                   /* 0 */
+} gfw_corners_cfg;
+int   gfw_corners_shi_tomasi(gfw_ctx *ctx, const gfw_corners_cfg *cfg, const void *frames, int frames_on_device, int n_frames,
+                             float *corners, float *scores, int32_t *counts, int32_t *feat_first, float *features, int out_on_device);
 
 /* First-pass audit of the fused kernel (GFW_OPT_KERNEL_VARIANT = 3): counters8 = {certified pixels,
  * certified-but-different-from-exact (must stay 0), queued to the exact path, queue overflows,

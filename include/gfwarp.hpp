@@ -554,6 +554,22 @@ inline std::vector<FlowPair> optical_flow_pyrlk(gfw_ctx *ctx, const uint8_t *fra
     }
     return out;
 }
+// ---- synchronization/optical_flow/opencv_pyrlk.rs:25-42 over gfw_corners_shi_tomasi: `OFOpenCVPyrLK::detect_features` for ALL frames in one device call with the
+// reference's parameters, good_features_to_track(img, 200, 0.01, 10.0, ..).  `frames`: n u8 gray planes back to back (host memory).  One list per frame, in pick
+// order: exactly the `features` of optical_flow_pyrlk.
+inline std::vector<std::vector<std::pair<float, float>>> detect_features_pyrlk(gfw_ctx *ctx, const uint8_t *frames, int n_frames, int width, int height, int stride) {
+    std::vector<std::vector<std::pair<float, float>>> out((size_t)(n_frames > 0 ? n_frames : 0));
+    if (n_frames == 0) return out;
+    if (!ctx) throw GyroflowCoreError(GyroflowCoreError::Unknown, "detect_features_pyrlk: no backend context for the corner detection");
+    gfw_corners_cfg cfg = {width, height, stride, 200, 0.01f, 10.0f, 0, 0};
+    std::vector<float> corners(out.size() * 200 * 2 + 2);
+    std::vector<int32_t> counts(out.size() + 1);
+    const int rc = gfw_corners_shi_tomasi(ctx, &cfg, frames, 0, n_frames, corners.data(), nullptr, counts.data(), nullptr, nullptr, 0);
+    if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+    for (size_t f = 0; f < out.size(); ++f)
+        for (int k = 0; k < counts[f]; ++k) out[f].push_back({corners[(f * 200 + (size_t)k) * 2], corners[(f * 200 + (size_t)k) * 2 + 1]});
+    return out;
+}
 // `results`: every analysed frame's timestamp_us -> its euler, or nullopt without a rotation (a sample sits midway to the NEXT analysed frame, :312-315);
 // final_pass interpolates a missing rotation linearly between its neighbours that have one (:284-305); lpf > 0 (Hz) runs gfw_lowpass_gyro (:349-357)
 inline std::map<int64_t, TimeIMU> estimated_gyro(const std::map<int64_t, std::optional<std::array<double, 3>>> &results, double fps, double lpf = 0.0, bool final_pass = false) {

@@ -1,0 +1,28 @@
+"""gfw_corners_shi_tomasi's host code (gyroflow_amd/csrc/gfw_corners_host.h: the check with its reasons, the plan and its batches, the staging) in a stand-alone
+program (tests/cpp/test_corners_host.cpp) built with AddressSanitizer and UBSan: the host pass of the project's compiler only, no device, no library, nothing
+loaded into Python.  The program holds the staged block to its plan; the sanitizers hold every access."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    assert os.path.exists(HIPCC), "hipcc not found"
+    out = str(tmp_path_factory.mktemp("cpp") / "test_corners_host")
+    r = subprocess.run([HIPCC, "-x", "hip", "--offload-arch=gfx950", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
+                        "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                        os.path.join(ROOT, "tests", "cpp", "test_corners_host.cpp"), "-o", out], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    return out
+
+
+def test_corners_host_code_under_asan_and_ubsan(exe):
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "corners host code ok" in r.stdout
