@@ -133,10 +133,17 @@ class CornersCfg(C.Structure):
                 ("max_workspace_mb", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FlowDisCfg(C.Structure):
+    """``gfw_flow_dis_cfg``: what every frame of a DIS dense optical-flow call shares."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("finest_scale", C.c_int32), ("variational_iters", C.c_int32), ("reserved", C.c_int32)]
+
+
 CORNERS_MAX, CORNERS_FRAMES_MAX, CORNERS_SIDE_MIN, CORNERS_SIDE_MAX, CORNERS_WORKSPACE_MB = 4096, 4096, 3, 8192, 512      # gfw_corners_shi_tomasi
 CORNERS_RING_SLOTS = 2           # staging slots of gfw_corners_shi_tomasi
 FLOW_FEATURES_MAX, FLOW_PAIRS_MAX, FLOW_FRAMES_MAX, FLOW_SIDE_MIN, FLOW_SIDE_MAX = 4096, 65535, 4096, 24, 8192      # gfw_flow_pyrlk
 FLOW_RING_SLOTS = 2              # staging slots of gfw_flow_pyrlk
+DIS_NODES_MAX, DIS_PAIRS_MAX, DIS_FRAMES_MAX, DIS_SIDE_MAX = 4096, 65535, 4096, 8192      # gfw_flow_dis
+DIS_RING_SLOTS = 2               # staging slots of gfw_flow_dis
 POSE_PAIR_POINTS_MAX, POSE_PAIRS_MAX, POSE_ROUNDS_MAX = 4096, 65535, 1024      # gfw_pose_almeida
 SYNC_FINE_CANDIDATES = 200       # the second stage's candidates
 SYNC_PAIR_POINTS_MAX = 4096
@@ -236,6 +243,7 @@ def bind(lib):
     lib.gfw_pose_almeida.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(PoseAlmeidaCfg), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_pose_almeida.restype = i32
     lib.gfw_pose_draws.argtypes = [C.c_uint64, vp, i32, i32, i32, vp, vp, vp]; lib.gfw_pose_draws.restype = i32
     lib.gfw_flow_pyrlk.argtypes = [vp, C.POINTER(FlowPyrLKCfg), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_flow_pyrlk.restype = i32
+    lib.gfw_flow_dis.argtypes = [vp, C.POINTER(FlowDisCfg), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_flow_dis.restype = i32
     lib.gfw_corners_shi_tomasi.argtypes = [vp, C.POINTER(CornersCfg), vp, i32, i32, vp, vp, vp, vp, vp, i32]; lib.gfw_corners_shi_tomasi.restype = i32
     lib.gfw_pack_matrices.argtypes = [vp, i32, vp]; lib.gfw_pack_matrices.restype = i32
     lib.gfw_checksum64.argtypes = [vp, vp, sz, vp]; lib.gfw_checksum64.restype = i32
@@ -266,7 +274,7 @@ EXPORTS = ["gfw_abi_version", "gfw_list_devices", "gfw_set_device", "gfw_get_inf
            "gfw_build_matrices_batch_stab", "gfw_zoom_fovs_stab", "gfw_sync_visual_costs", "gfw_sync_visual_search",
            "gfw_lowpass_gyro", "gfw_sync_gyro_costs", "gfw_sync_gyro_search",
            "gfw_optim_tables", "gfw_optim_resample", "gfw_sync_optim_rank", "gfw_sync_optim_points",
-           "gfw_pose_almeida", "gfw_pose_draws", "gfw_flow_pyrlk", "gfw_corners_shi_tomasi"]
+           "gfw_pose_almeida", "gfw_pose_draws", "gfw_flow_pyrlk", "gfw_corners_shi_tomasi", "gfw_flow_dis"]
 
 
 def load_library(path=None):

@@ -29,6 +29,7 @@
 #include "gfw_pose.h"
 #include "gfw_flow.h"
 #include "gfw_corners.h"
+#include "gfw_dis.h"
 #include "gfw_matrices_host.h"
 #include "gfw_zoom_host.h"
 #include "gfw_sync_host.h"
@@ -37,6 +38,7 @@
 #include "gfw_pose_host.h"
 #include "gfw_flow_host.h"
 #include "gfw_corners_host.h"
+#include "gfw_dis_host.h"
 #include "gfw_clip_host.h"
 #include "gfw_jit.h"
 #include <stdlib.h>
@@ -134,6 +136,9 @@ struct gfw_ctx {
     // gfw_corners_shi_tomasi: the frames' maxima and candidate counts (zeros) and host frames staged the same way (work space: the visual search's)
     static constexpr int kCornersSlots = 2;
     StagingRing<kCornersSlots> corners_ring;
+    // gfw_flow_dis: pairs and host frames staged the same way (work space: the visual search's)
+    static constexpr int kDisSlots = 2;
+    StagingRing<kDisSlots> dis_ring;
     // context-owned per-row tables built on the device (gfw_build_matrices): a small ring, built on copy_stream so that
     // frame N+1's table is produced while frame N is being warped; events order builder and consumer both ways
     struct BuiltSlot { DevBuf buf; Event built, consumed; };   // buf = rows + 4 doubles of builder scratch
@@ -1021,3 +1026,4 @@ int gfw_undistort_clip_lens(gfw_ctx *c, int n_frames, int nplanes, const gfw_buf
 #include "gfw_api_pose.inc"
 #include "gfw_api_flow.inc"
 #include "gfw_api_corners.inc"
+#include "gfw_api_dis.inc"

@@ -31,7 +31,12 @@ methods are not covered.
 
 ``OFOpenCVPyrLK::optical_flow_to`` (optical_flow/opencv_pyrlk.rs:63-119): the features of each pair's first frame tracked into its second frame by pyramidal
 Lucas-Kanade, ALL pairs in one device call, ``Backend.flow_pyrlk`` (gfw_flow_pyrlk); without features the points are the grid of opencv_dis.rs:62-119.  AKAZE
-and the DIS dense flow itself are not covered.
+is not covered.
+
+    matched = synchronization.optical_flow_dis(frames, pairs, backend=backend)
+
+``OFOpenCVDis`` (optical_flow/opencv_dis.rs, the reference's DEFAULT method 2): the DIS dense flow of ALL pairs in one device call, ``Backend.flow_dis``
+(gfw_flow_dis), read at the grid points.  Its variational refinement is not built.
 
     features = synchronization.detect_features_pyrlk(frames, backend)
 
@@ -207,6 +212,21 @@ def optical_flow_pyrlk(frames, pairs, features=None, backend=None, width=None):
         raise ValueError("optical_flow_pyrlk: no backend for the optical flow")
     frames = np.ascontiguousarray(frames, dtype=np.uint8)
     r = backend.flow_pyrlk(frames, frames.shape[2] if width is None else width, pairs, features)
+    first, a, b = r["pair_first"], r["points_a"], r["points_b"]
+    return [(a[first[p]:first[p + 1]], b[first[p]:first[p + 1]]) if first[p + 1] - first[p] >= 10 else None for p in range(len(first) - 1)]
+
+
+def optical_flow_dis(frames, pairs, backend=None, width=None, finest_scale=2):
+    """``OFOpenCVDis::optical_flow_to`` (optical_flow/opencv_dis.rs, the reference's default method 2) for all frame pairs in ONE device call
+    (``Backend.flow_dis``): the DIS dense flow with the parameters of DISOpticalFlow_PRESET_FAST — WITHOUT its variational refinement, which is not built — read at
+    the grid points of :62-119.  ``frames``: u8 gray planes [n][height][stride] (``width`` defaults to the stride); ``pairs``: [(first frame, second frame)]
+    indices; ``finest_scale``: 2 as the reference, or 1 for a flow of half the pixel.  Returns one entry per pair: (pts1 f32 [k][2], pts2 f32 [k][2]) — every node
+    the grid keeps in the first frame and where the flow takes it, unfiltered as in the reference (:113-117) — or None when fewer than 10 nodes were kept (:126).
+    The entries are what ``estimate_poses_almeida`` takes as its ``pairs``."""
+    if backend is None:
+        raise ValueError("optical_flow_dis: no backend for the optical flow")
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    r = backend.flow_dis(frames, frames.shape[2] if width is None else width, pairs, finest_scale=finest_scale)
     first, a, b = r["pair_first"], r["points_a"], r["points_b"]
     return [(a[first[p]:first[p + 1]], b[first[p]:first[p + 1]]) if first[p + 1] - first[p] >= 10 else None for p in range(len(first) - 1)]
 

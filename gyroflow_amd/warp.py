@@ -563,6 +563,46 @@ class Backend:
             del o["grid_points"], o["grid_counts"]
         return o
 
+    def flow_dis(self, frames, width, pairs, finest_scale=2, flow=False, out_ptrs=None, shape=None, variational_iters=0):
+        """`OFOpenCVDis` (optical_flow/opencv_dis.rs, the reference's default method 2) of every frame pair in one device call (gfw_flow_dis): the DIS dense flow
+        with the parameters of DISOpticalFlow_PRESET_FAST, WITHOUT its variational refinement (``variational_iters`` must be 0), read at the grid points of
+        opencv_dis.rs:62-119.
+
+        ``frames``: u8 gray planes as numpy [n][height][stride], or a device pointer (int) with ``shape`` = (n, height, stride); ``width`` <= stride; ``pairs``:
+        [(first frame, second frame)]; ``finest_scale`` 2 (the reference's) or 1.  Returns a dict: grid_points f32 [n][nodes][2], grid_counts int32 [n], pair_first
+        int32 [n_pairs + 1], points_a / points_b f32 [total][2] (every kept node of each pair's first frame and where the flow takes it: what pose_almeida and the
+        visual search take) — with ``flow`` also flow f32 [n_pairs][height >> finest_scale][width >> finest_scale][2], the finest level's dense field — or, with
+        ``out_ptrs`` = (grid_points or None, grid_counts or None, flow or None, pair_first, points_a, points_b) device pointers (points_a / points_b with room for
+        [n_pairs * nodes][2]), the number of those slots: in order on the stream."""
+        if isinstance(frames, (int, np.integer)):
+            n, height, stride = shape
+            fp, on_device, _keep = int(frames), 1, None
+        else:
+            _keep = np.ascontiguousarray(frames, dtype=np.uint8)
+            assert _keep.ndim == 3, "frames: [n][height][stride]"
+            n, height, stride = _keep.shape
+            fp, on_device = (_keep.ctypes.data if _keep.size else None), 0
+        cfg = abi.FlowDisCfg(width=int(width), height=int(height), stride=int(stride), finest_scale=int(finest_scale), variational_iters=int(variational_iters))
+        pf = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        p = lambda a: a.ctypes.data if a is not None and a.size else None
+        args = (self.ctx, C.byref(cfg), fp, on_device, int(n), p(pf), len(pf))
+        nodes = flow_grid_nodes(width, height) if width >= 15 else 0
+        if out_ptrs is not None:
+            self._check(self.lib.gfw_flow_dis(*args, *out_ptrs, 1))
+            return len(pf) * nodes
+        room = max(len(pf) * nodes, 1)                           # (an output without slots still is an array of the caller's: at least one element)
+        fs = int(finest_scale) if int(finest_scale) in (1, 2) else 2
+        o = {"grid_points": np.zeros((n, nodes, 2), dtype=np.float32), "grid_counts": np.zeros(n, dtype=np.int32),
+             "flow": np.zeros((len(pf) if flow else 0, int(height) >> fs, int(width) >> fs, 2), dtype=np.float32),
+             "pair_first": np.zeros(len(pf) + 1, dtype=np.int32), "points_a": np.zeros((room, 2), dtype=np.float32), "points_b": np.zeros((room, 2), dtype=np.float32)}
+        self._check(self.lib.gfw_flow_dis(*args, p(o["grid_points"]), p(o["grid_counts"]), p(o["flow"]) if flow else None, o["pair_first"].ctypes.data,
+                                          o["points_a"].ctypes.data, o["points_b"].ctypes.data, 0))
+        total = int(o["pair_first"][-1]) if len(pf) else 0
+        o["points_a"], o["points_b"] = o["points_a"][:total], o["points_b"][:total]
+        if not flow:
+            del o["flow"]
+        return o
+
     def corners_shi_tomasi(self, frames, width, max_corners=200, quality=0.01, min_distance=10.0, scores=False, packed=True, max_workspace_mb=0, out_ptrs=None, shape=None):
         """`OFOpenCVPyrLK::detect_features` (optical_flow/opencv_pyrlk.rs:25-42: good_features_to_track(img, 200, 0.01, 10.0, ..)) of every frame in one device call
         (gfw_corners_shi_tomasi): Shi-Tomasi corners by the minimum eigenvalue of the 3 x 3 gradient covariance, thresholded at ``quality`` of the frame's maximum,

@@ -614,7 +614,7 @@ int   gfw_zoom_smooth(const double *fov_minimal, int n, double adaptive_zoom_win
  * negative counts, a descending pair_first, more than 4096 points in a pair, width^2 + height^2 >= 2^32, params->flags with
  * HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA, a non-zero reserved slot, no tracks.
  * NOT covered: clips with per_frame_time_offsets, camera_stab_data or mesh_correction (in the reference the frame index, and so
- * the mesh, follows `timestamp - offs`); lens data or a video rotation keyframed inside a range; suppress_rotation; AKAZE and the DIS dense flow itself
+ * the mesh, follows `timestamp - offs`); lens data or a video rotation keyframed inside a range; suppress_rotation; AKAZE
  * (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below; its corner detection: gfw_corners_shi_tomasi below), rs_sync.  (essential_matrix: gfw_sync_gyro_search below; optimsync: gfw_sync_optim_points below; pose estimation by the
  * Almeida method: gfw_pose_almeida below.) */
 typedef struct gfw_sync_search {
@@ -667,7 +667,7 @@ int   gfw_sync_visual_search(gfw_ctx *ctx, const gfw_kernel_params *params, cons
  * GFW_ERR_INVALID_ARGUMENT, the range named in gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative
  * counts, a negative or descending first array, a slice outside its array, a non-finite initial_offset or search_size, a negative
  * search_size, counts over the limits above.  Non-finite sample values are not rejected; the pick among NaN costs is unspecified.
- * NOT covered: AKAZE and the DIS dense flow itself (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below; its corner detection: gfw_corners_shi_tomasi below), rs_sync itself, pose estimation other than the Almeida method (gfw_pose_almeida below; the series of
+ * NOT covered: AKAZE (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below; its corner detection: gfw_corners_shi_tomasi below; the DIS dense flow: gfw_flow_dis below), rs_sync itself, pose estimation other than the Almeida method (gfw_pose_almeida below; the series of
  * estimated samples is made of its rotations by gyroflow::estimated_gyro / gyroflow_amd.synchronization.estimated_gyro).
  *
  * gfw_lowpass_gyro: Lowpass::filter_gyro_forward_backward (filtering.rs:46-74) of xyz [n][3] f64 in place, on the host (no context):
@@ -755,7 +755,7 @@ int   gfw_sync_optim_points(gfw_ctx *ctx, const double *gyro, int64_t n_samples,
  * not match, params->flags with HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA, f / c that are not the f32 cast of camera_matrix,
  * sizes under 1, a negative or NaN inlier angle, a non-zero reserved slot.
  * NOT covered: lens data or a refraction coefficient that changes between the pairs of one call (one call per lens); the other three
- * pose methods (their solvers are not part of the reference tree); AKAZE and the DIS dense flow itself (the matched points of the
+ * pose methods (their solvers are not part of the reference tree); AKAZE (the DIS dense flow: gfw_flow_dis below; the matched points of the
  * pyramidal Lucas-Kanade method: gfw_flow_pyrlk below, its features: gfw_corners_shi_tomasi below).
  *
  * gfw_pose_draws (host only, no context): one valid set of draws per seed — not rand's sequence.  A counter-based generator:
@@ -808,7 +808,8 @@ int   gfw_pose_draws(uint64_t seed, const int32_t *pair_first, int n_pairs, int 
  * gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative counts, a descending feat_first, a frame index out
  * of range, a pair of a frame with itself, sides outside 24 .. 8192, stride < width, mode 0 without features, counts over the limits,
  * a non-zero reserved slot.
- * NOT covered: AKAZE, the DIS dense flow itself.  (Corner detection, goodFeaturesToTrack: gfw_corners_shi_tomasi below.) */
+ * NOT covered: AKAZE.  (Corner detection, goodFeaturesToTrack: gfw_corners_shi_tomasi below; the DIS dense flow, the reference's
+ * default method 2, without its variational refinement: gfw_flow_dis below.) */
 typedef struct gfw_flow_pyrlk_cfg {
     int32_t width, height, stride;         /* of every frame of the call */
     int32_t point_mode;                    /* 0 the caller's features, 1 the grid points */
@@ -851,7 +852,8 @@ int   gfw_flow_pyrlk(gfw_ctx *ctx, const gfw_flow_pyrlk_cfg *cfg, const void *fr
  * GFW_ERR_INVALID_ARGUMENT, the reason in gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative counts, sides
  * or stride out of range, max_corners / quality / min_distance out of range or not finite, a negative max_workspace_mb, a non-zero
  * reserved slot, more than 4096 frames, host frames over 2 GiB in all.
- * NOT covered: a mask, the Harris response (the reference passes neither); AKAZE, the DIS dense flow itself. */
+ * NOT covered: a mask, the Harris response (the reference passes neither); AKAZE.  (The DIS dense flow, without its variational
+ * refinement: gfw_flow_dis below.) */
 typedef struct gfw_corners_cfg {
     int32_t width, height, stride;      /* of every frame; sides 3 .. 8192, stride >= width */
     int32_t max_corners;                /* 1 .. 4096 (gfw_flow_pyrlk's features-a-frame limit); the reference: 200 */
@@ -861,6 +863,52 @@ typedef struct gfw_corners_cfg {
 } gfw_corners_cfg;
 int   gfw_corners_shi_tomasi(gfw_ctx *ctx, const gfw_corners_cfg *cfg, const void *frames, int frames_on_device, int n_frames,
                              float *corners, float *scores, int32_t *counts, int32_t *feat_first, float *features, int out_on_device);
+
+/* ---- synchronization: DIS dense optical flow of a clip's frame pairs in one device call ----
+ * optical_flow/opencv_dis.rs (`OFOpenCVDis`, the reference's DEFAULT method 2: stabilization_params.rs:174): the dense inverse search
+ * flow (Kroeger et al., "Fast Optical Flow using Dense Inverse Search") of every pair with the parameters of
+ * DISOpticalFlow_PRESET_FAST (:59) — patch 8, patch stride 4, 16 descent iterations, finest scale 2, mean-normalised patches, spatial
+ * propagation — read at the grid points of :62-119 (gfw_flow_pyrlk's point mode 1, unchanged).  VARIATIONAL REFINEMENT IS NOT PART OF
+ * IT: the preset runs 5 iterations of it; cfg.variational_iters must be 0 until a later unit adds it, with no change of this interface.
+ * OpenCV's source is not part of the reference tree, so nothing reference-produced pins the flow: the contract is tests/_disstmt.py, the
+ * published scheme stated operation by operation with every sum over a patch's 64 pixels an INTEGER (integer gradients, fixed-point
+ * bilinear samples, exact sums, one conversion to f32 per sum), which the device equals to the bit.  The statement is first held to a
+ * planted motion: every interior node within the pose estimator's inlier angle of its analytic destination.  OpenCV's raster-order
+ * propagation depends on its thread count and is not reproduced: three synchronous passes a level (descend; left and top neighbour,
+ * descend; right and bottom neighbour, descend), so no result depends on an order of execution.
+ *   cfg         width, height, stride >= width, finest_scale 1 | 2 (the reference: 2; 1 halves the flow's pixel), variational_iters = 0,
+ *               reserved = 0.  Scales coarsest .. finest_scale are processed, coarsest = min(int(log2(max(w, h) / 32) + 0.5),
+ *               int(log2(min(w, h) / 8))); a size with coarsest < finest_scale is rejected.  Sides up to 8192
+ *   frames      n_frames u8 gray planes back to back, frame f at frames + f * stride * height; host memory, or device memory with
+ *               frames_on_device (it must stay valid until the stream has run the call) — gfw_flow_pyrlk's contract
+ *   pair_frames [n_pairs][2] (first frame, second frame) indices
+ *   grid_points NULL or [n_frames][nodes][2] f32 (kept nodes first, in the reference's loop order, then zeros), grid_counts NULL or
+ *               [n_frames] int32, nodes = ceil(w / step) * ceil(h / step), step = w / 15: as gfw_flow_pyrlk's
+ *   flow        NULL or [n_pairs][h_f][w_f][2] f32, w_f = width >> finest_scale, h_f alike: the finest level's dense field, in that
+ *               level's pixels
+ *   result      out_pair_first [n_pairs + 1] int32 and points_a / points_b [..][2] f32: for EVERY node (i, j) the grid keeps in the
+ *               pair's first frame, in grid order, a = (i, j) and b = a + 2^finest_scale * the field at ((i + 0.5) / 2^finest_scale
+ *               - 0.5, ..) — the DIS arm filters nothing (:113-117), not even a b outside the frame — exactly gfw_pose_almeida's and
+ *               gfw_sync_visual_*'s pair_first / points_a / points_b.  Room for [n_pairs * nodes][2] each; only the returned entries
+ *               are written.  The "at least 10" rule (:126) is the caller's
+ *   limits      at most 4096 grid nodes a frame, 65535 pairs, 4096 frames, 2 GiB staged in all, 16 GiB of device work space
+ * Launches, whatever the number of pairs and frames: 3 + coarsest + 4 (coarsest - finest_scale + 1) — the pyramid levels, the grid, per
+ * level three passes and the dense field, a scan, the node sampling; 24 for 1280 x 720 at finest_scale 2 — in order on the context's
+ * stream; outputs are host or device memory (out_on_device); with device outputs an asynchronous context returns without waiting.
+ * n_pairs = 0 succeeds and writes nothing.  Rejected with GFW_ERR_INVALID_ARGUMENT, the pair or frame named in gfw_last_error(),
+ * outputs untouched: null arguments for non-zero counts, negative counts, a frame index out of range, a pair of a frame with itself,
+ * stride < width, a size with coarsest < finest_scale (the size named), a finest_scale other than 1 or 2, a non-zero variational_iters
+ * or reserved slot, counts over the limits.
+ * NOT covered: variational refinement; AKAZE. */
+typedef struct gfw_flow_dis_cfg {
+    int32_t width, height, stride;         /* of every frame of the call */
+    int32_t finest_scale;                  /* 1 | 2 */
+    int32_t variational_iters;             /* 0 */
+    int32_t reserved;                      /* 0 */
+} gfw_flow_dis_cfg;
+int   gfw_flow_dis(gfw_ctx *ctx, const gfw_flow_dis_cfg *cfg, const void *frames, int frames_on_device, int n_frames,
+                   const int32_t *pair_frames, int n_pairs, float *grid_points, int32_t *grid_counts, float *flow,
+                   int32_t *out_pair_first, float *points_a, float *points_b, int out_on_device);
 
 /* First-pass audit of the fused kernel (GFW_OPT_KERNEL_VARIANT = 3): counters8 = {certified pixels,
  * certified-but-different-from-exact (must stay 0), queued to the exact path, queue overflows,
