@@ -138,12 +138,23 @@ class FlowDisCfg(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("finest_scale", C.c_int32), ("variational_iters", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FlowVarrefCfg(C.Structure):
+    """``gfw_flow_varref_cfg``: the variational refinement of a gfw_flow_dis_refined call (the defaults: the preset's values to the builder's best knowledge)."""
+    _fields_ = [("fixed_point_iters", C.c_int32), ("sor_iters", C.c_int32), ("alpha", C.c_float), ("delta", C.c_float), ("gamma", C.c_float), ("omega", C.c_float),
+                ("reserved", C.c_int32 * 2)]
+
+
+def varref_cfg(fixed_point_iters=5, sor_iters=5, alpha=20.0, delta=5.0, gamma=10.0, omega=1.6):
+    return FlowVarrefCfg(fixed_point_iters=int(fixed_point_iters), sor_iters=int(sor_iters), alpha=alpha, delta=delta, gamma=gamma, omega=omega)
+
+
 CORNERS_MAX, CORNERS_FRAMES_MAX, CORNERS_SIDE_MIN, CORNERS_SIDE_MAX, CORNERS_WORKSPACE_MB = 4096, 4096, 3, 8192, 512      # gfw_corners_shi_tomasi
 CORNERS_RING_SLOTS = 2           # staging slots of gfw_corners_shi_tomasi
 FLOW_FEATURES_MAX, FLOW_PAIRS_MAX, FLOW_FRAMES_MAX, FLOW_SIDE_MIN, FLOW_SIDE_MAX = 4096, 65535, 4096, 24, 8192      # gfw_flow_pyrlk
 FLOW_RING_SLOTS = 2              # staging slots of gfw_flow_pyrlk
 DIS_NODES_MAX, DIS_PAIRS_MAX, DIS_FRAMES_MAX, DIS_SIDE_MAX = 4096, 65535, 4096, 8192      # gfw_flow_dis
-DIS_RING_SLOTS = 2               # staging slots of gfw_flow_dis
+DIS_RING_SLOTS = 2               # staging slots of gfw_flow_dis and gfw_flow_dis_refined
+VARREF_ITERS_MAX, VARREF_PLANES = 64, 17          # gfw_flow_dis_refined: fixed-point / SOR iterations; work-space floats per pixel and pair of the finest level
 POSE_PAIR_POINTS_MAX, POSE_PAIRS_MAX, POSE_ROUNDS_MAX = 4096, 65535, 1024      # gfw_pose_almeida
 SYNC_FINE_CANDIDATES = 200       # the second stage's candidates
 SYNC_PAIR_POINTS_MAX = 4096
@@ -244,6 +255,7 @@ def bind(lib):
     lib.gfw_pose_draws.argtypes = [C.c_uint64, vp, i32, i32, i32, vp, vp, vp]; lib.gfw_pose_draws.restype = i32
     lib.gfw_flow_pyrlk.argtypes = [vp, C.POINTER(FlowPyrLKCfg), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_flow_pyrlk.restype = i32
     lib.gfw_flow_dis.argtypes = [vp, C.POINTER(FlowDisCfg), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_flow_dis.restype = i32
+    lib.gfw_flow_dis_refined.argtypes = [vp, C.POINTER(FlowDisCfg), C.POINTER(FlowVarrefCfg), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_flow_dis_refined.restype = i32
     lib.gfw_corners_shi_tomasi.argtypes = [vp, C.POINTER(CornersCfg), vp, i32, i32, vp, vp, vp, vp, vp, i32]; lib.gfw_corners_shi_tomasi.restype = i32
     lib.gfw_pack_matrices.argtypes = [vp, i32, vp]; lib.gfw_pack_matrices.restype = i32
     lib.gfw_checksum64.argtypes = [vp, vp, sz, vp]; lib.gfw_checksum64.restype = i32
@@ -274,7 +286,7 @@ EXPORTS = ["gfw_abi_version", "gfw_list_devices", "gfw_set_device", "gfw_get_inf
            "gfw_build_matrices_batch_stab", "gfw_zoom_fovs_stab", "gfw_sync_visual_costs", "gfw_sync_visual_search",
            "gfw_lowpass_gyro", "gfw_sync_gyro_costs", "gfw_sync_gyro_search",
            "gfw_optim_tables", "gfw_optim_resample", "gfw_sync_optim_rank", "gfw_sync_optim_points",
-           "gfw_pose_almeida", "gfw_pose_draws", "gfw_flow_pyrlk", "gfw_corners_shi_tomasi", "gfw_flow_dis"]
+           "gfw_pose_almeida", "gfw_pose_draws", "gfw_flow_pyrlk", "gfw_corners_shi_tomasi", "gfw_flow_dis", "gfw_flow_dis_refined"]
 
 
 def load_library(path=None):

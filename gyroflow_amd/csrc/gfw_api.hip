@@ -30,6 +30,7 @@
 #include "gfw_flow.h"
 #include "gfw_corners.h"
 #include "gfw_dis.h"
+#include "gfw_varref.h"
 #include "gfw_matrices_host.h"
 #include "gfw_zoom_host.h"
 #include "gfw_sync_host.h"
@@ -39,6 +40,7 @@
 #include "gfw_flow_host.h"
 #include "gfw_corners_host.h"
 #include "gfw_dis_host.h"
+#include "gfw_varref_host.h"
 #include "gfw_clip_host.h"
 #include "gfw_jit.h"
 #include <stdlib.h>
@@ -1027,3 +1029,4 @@ int gfw_undistort_clip_lens(gfw_ctx *c, int n_frames, int nplanes, const gfw_buf
 #include "gfw_api_flow.inc"
 #include "gfw_api_corners.inc"
 #include "gfw_api_dis.inc"
+#include "gfw_api_varref.inc"

@@ -1,7 +1,7 @@
 // gfw_dis.h — DIS dense optical flow of a clip's frame pairs on the device (gfw_dis.hip): the reference's default optical-flow method 2
 // (src/core/synchronization/optical_flow/opencv_dis.rs: DISOpticalFlow_PRESET_FAST — patch 8, patch stride 4, 16 descent iterations, finest scale 2, mean-normalised
 // patches, spatial propagation), stated in fixed point (tests/_disstmt.py), sampled at the grid points of opencv_dis.rs:62-119 (gfw_flow.hip's grid kernel).
-// Variational refinement is NOT part of it.
+// Variational refinement is NOT part of it: it is gfw_varref.h's, launched behind each level's dense field by gfw_flow_dis_refined.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -68,7 +68,7 @@ inline GfwDisPlan gfw_dis_plan(const GfwDisInputs &I) {
 // -> true, or false with the reason (the pair or frame named) in `err`
 inline bool gfw_dis_check(const GfwDisInputs &I, char *err, size_t cap) {
     if (I.reserved) { snprintf(err, cap, "bad DIS flow configuration: the reserved slot must be 0"); return false; }
-    if (I.variational_iters) { snprintf(err, cap, "bad DIS flow configuration: variational_iters %d (variational refinement is not built: it must be 0)", I.variational_iters); return false; }
+    if (I.variational_iters) { snprintf(err, cap, "bad DIS flow configuration: variational_iters %d (it must be 0 here: variational refinement is gfw_flow_dis_refined's, counted in its gfw_flow_varref_cfg)", I.variational_iters); return false; }
     if (I.finest != 1 && I.finest != 2) { snprintf(err, cap, "bad DIS flow configuration: finest_scale %d (1 or 2)", I.finest); return false; }
     if (I.n_frames < 0 || I.n_pairs < 0) { snprintf(err, cap, "bad DIS flow arguments (negative count: %d frames, %d pairs)", I.n_frames, I.n_pairs); return false; }
     if (I.width < 1 || I.width > GFW_DIS_SIDE_MAX || I.height < 1 || I.height > GFW_DIS_SIDE_MAX) {

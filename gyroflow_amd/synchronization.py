@@ -36,7 +36,7 @@ is not covered.
     matched = synchronization.optical_flow_dis(frames, pairs, backend=backend)
 
 ``OFOpenCVDis`` (optical_flow/opencv_dis.rs, the reference's DEFAULT method 2): the DIS dense flow of ALL pairs in one device call, ``Backend.flow_dis``
-(gfw_flow_dis), read at the grid points.  Its variational refinement is not built.
+(gfw_flow_dis), read at the grid points; with its variational refinement: gfw_flow_dis_refined (``variational_iters``).
 
     features = synchronization.detect_features_pyrlk(frames, backend)
 
@@ -216,17 +216,18 @@ def optical_flow_pyrlk(frames, pairs, features=None, backend=None, width=None):
     return [(a[first[p]:first[p + 1]], b[first[p]:first[p + 1]]) if first[p + 1] - first[p] >= 10 else None for p in range(len(first) - 1)]
 
 
-def optical_flow_dis(frames, pairs, backend=None, width=None, finest_scale=2):
+def optical_flow_dis(frames, pairs, backend=None, width=None, finest_scale=2, variational_iters=0):
     """``OFOpenCVDis::optical_flow_to`` (optical_flow/opencv_dis.rs, the reference's default method 2) for all frame pairs in ONE device call
-    (``Backend.flow_dis``): the DIS dense flow with the parameters of DISOpticalFlow_PRESET_FAST — WITHOUT its variational refinement, which is not built — read at
-    the grid points of :62-119.  ``frames``: u8 gray planes [n][height][stride] (``width`` defaults to the stride); ``pairs``: [(first frame, second frame)]
+    (``Backend.flow_dis``): the DIS dense flow with the parameters of DISOpticalFlow_PRESET_FAST, read at the grid points of :62-119.  ``variational_iters``: the
+    fixed-point iterations of the preset's variational refinement on every level (gfw_flow_dis_refined).  THE REFERENCE'S PRESET IS 5; the default here stays 0,
+    the unrefined flow, as before the refinement existed.  ``frames``: u8 gray planes [n][height][stride] (``width`` defaults to the stride); ``pairs``: [(first frame, second frame)]
     indices; ``finest_scale``: 2 as the reference, or 1 for a flow of half the pixel.  Returns one entry per pair: (pts1 f32 [k][2], pts2 f32 [k][2]) — every node
     the grid keeps in the first frame and where the flow takes it, unfiltered as in the reference (:113-117) — or None when fewer than 10 nodes were kept (:126).
     The entries are what ``estimate_poses_almeida`` takes as its ``pairs``."""
     if backend is None:
         raise ValueError("optical_flow_dis: no backend for the optical flow")
     frames = np.ascontiguousarray(frames, dtype=np.uint8)
-    r = backend.flow_dis(frames, frames.shape[2] if width is None else width, pairs, finest_scale=finest_scale)
+    r = backend.flow_dis(frames, frames.shape[2] if width is None else width, pairs, finest_scale=finest_scale, variational_iters=variational_iters)
     first, a, b = r["pair_first"], r["points_a"], r["points_b"]
     return [(a[first[p]:first[p + 1]], b[first[p]:first[p + 1]]) if first[p + 1] - first[p] >= 10 else None for p in range(len(first) - 1)]
 

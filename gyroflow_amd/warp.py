@@ -563,10 +563,11 @@ class Backend:
             del o["grid_points"], o["grid_counts"]
         return o
 
-    def flow_dis(self, frames, width, pairs, finest_scale=2, flow=False, out_ptrs=None, shape=None, variational_iters=0):
+    def flow_dis(self, frames, width, pairs, finest_scale=2, flow=False, out_ptrs=None, shape=None, variational_iters=0, varref=None):
         """`OFOpenCVDis` (optical_flow/opencv_dis.rs, the reference's default method 2) of every frame pair in one device call (gfw_flow_dis): the DIS dense flow
-        with the parameters of DISOpticalFlow_PRESET_FAST, WITHOUT its variational refinement (``variational_iters`` must be 0), read at the grid points of
-        opencv_dis.rs:62-119.
+        with the parameters of DISOpticalFlow_PRESET_FAST, read at the grid points of opencv_dis.rs:62-119.  ``variational_iters`` = 0 (the default) is the flow
+        WITHOUT the preset's variational refinement; n > 0 goes to gfw_flow_dis_refined with n fixed-point iterations on every level (the preset: 5) and the
+        other parameters of ``varref`` (an ``abi.FlowVarrefCfg``; None: ``abi.varref_cfg()``, the preset's values to the builder's best knowledge).
 
         ``frames``: u8 gray planes as numpy [n][height][stride], or a device pointer (int) with ``shape`` = (n, height, stride); ``width`` <= stride; ``pairs``:
         [(first frame, second frame)]; ``finest_scale`` 2 (the reference's) or 1.  Returns a dict: grid_points f32 [n][nodes][2], grid_counts int32 [n], pair_first
@@ -582,21 +583,26 @@ class Backend:
             assert _keep.ndim == 3, "frames: [n][height][stride]"
             n, height, stride = _keep.shape
             fp, on_device = (_keep.ctypes.data if _keep.size else None), 0
-        cfg = abi.FlowDisCfg(width=int(width), height=int(height), stride=int(stride), finest_scale=int(finest_scale), variational_iters=int(variational_iters))
+        cfg = abi.FlowDisCfg(width=int(width), height=int(height), stride=int(stride), finest_scale=int(finest_scale))
         pf = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
         p = lambda a: a.ctypes.data if a is not None and a.size else None
-        args = (self.ctx, C.byref(cfg), fp, on_device, int(n), p(pf), len(pf))
+        if int(variational_iters) == 0 and varref is None:
+            call, args = self.lib.gfw_flow_dis, (self.ctx, C.byref(cfg), fp, on_device, int(n), p(pf), len(pf))
+        else:
+            ref = abi.varref_cfg() if varref is None else abi.FlowVarrefCfg.from_buffer_copy(varref)
+            ref.fixed_point_iters = int(variational_iters)
+            call, args = self.lib.gfw_flow_dis_refined, (self.ctx, C.byref(cfg), C.byref(ref), fp, on_device, int(n), p(pf), len(pf))
         nodes = flow_grid_nodes(width, height) if width >= 15 else 0
         if out_ptrs is not None:
-            self._check(self.lib.gfw_flow_dis(*args, *out_ptrs, 1))
+            self._check(call(*args, *out_ptrs, 1))
             return len(pf) * nodes
         room = max(len(pf) * nodes, 1)                           # (an output without slots still is an array of the caller's: at least one element)
         fs = int(finest_scale) if int(finest_scale) in (1, 2) else 2
         o = {"grid_points": np.zeros((n, nodes, 2), dtype=np.float32), "grid_counts": np.zeros(n, dtype=np.int32),
              "flow": np.zeros((len(pf) if flow else 0, int(height) >> fs, int(width) >> fs, 2), dtype=np.float32),
              "pair_first": np.zeros(len(pf) + 1, dtype=np.int32), "points_a": np.zeros((room, 2), dtype=np.float32), "points_b": np.zeros((room, 2), dtype=np.float32)}
-        self._check(self.lib.gfw_flow_dis(*args, p(o["grid_points"]), p(o["grid_counts"]), p(o["flow"]) if flow else None, o["pair_first"].ctypes.data,
-                                          o["points_a"].ctypes.data, o["points_b"].ctypes.data, 0))
+        self._check(call(*args, p(o["grid_points"]), p(o["grid_counts"]), p(o["flow"]) if flow else None, o["pair_first"].ctypes.data,
+                    o["points_a"].ctypes.data, o["points_b"].ctypes.data, 0))
         total = int(o["pair_first"][-1]) if len(pf) else 0
         o["points_a"], o["points_b"] = o["points_a"][:total], o["points_b"][:total]
         if not flow:

@@ -809,7 +809,7 @@ int   gfw_pose_draws(uint64_t seed, const int32_t *pair_first, int n_pairs, int 
  * of range, a pair of a frame with itself, sides outside 24 .. 8192, stride < width, mode 0 without features, counts over the limits,
  * a non-zero reserved slot.
  * NOT covered: AKAZE.  (Corner detection, goodFeaturesToTrack: gfw_corners_shi_tomasi below; the DIS dense flow, the reference's
- * default method 2, without its variational refinement: gfw_flow_dis below.) */
+ * default method 2: gfw_flow_dis below, with its variational refinement gfw_flow_dis_refined.) */
 typedef struct gfw_flow_pyrlk_cfg {
     int32_t width, height, stride;         /* of every frame of the call */
     int32_t point_mode;                    /* 0 the caller's features, 1 the grid points */
@@ -852,8 +852,8 @@ int   gfw_flow_pyrlk(gfw_ctx *ctx, const gfw_flow_pyrlk_cfg *cfg, const void *fr
  * GFW_ERR_INVALID_ARGUMENT, the reason in gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative counts, sides
  * or stride out of range, max_corners / quality / min_distance out of range or not finite, a negative max_workspace_mb, a non-zero
  * reserved slot, more than 4096 frames, host frames over 2 GiB in all.
- * NOT covered: a mask, the Harris response (the reference passes neither); AKAZE.  (The DIS dense flow, without its variational
- * refinement: gfw_flow_dis below.) */
+ * NOT covered: a mask, the Harris response (the reference passes neither); AKAZE.  (The DIS dense flow: gfw_flow_dis below, with its variational
+ * refinement gfw_flow_dis_refined.) */
 typedef struct gfw_corners_cfg {
     int32_t width, height, stride;      /* of every frame; sides 3 .. 8192, stride >= width */
     int32_t max_corners;                /* 1 .. 4096 (gfw_flow_pyrlk's features-a-frame limit); the reference: 200 */
@@ -869,7 +869,9 @@ int   gfw_corners_shi_tomasi(gfw_ctx *ctx, const gfw_corners_cfg *cfg, const voi
  * flow (Kroeger et al., "Fast Optical Flow using Dense Inverse Search") of every pair with the parameters of
  * DISOpticalFlow_PRESET_FAST (:59) — patch 8, patch stride 4, 16 descent iterations, finest scale 2, mean-normalised patches, spatial
  * propagation — read at the grid points of :62-119 (gfw_flow_pyrlk's point mode 1, unchanged).  VARIATIONAL REFINEMENT IS NOT PART OF
- * IT: the preset runs 5 iterations of it; cfg.variational_iters must be 0 until a later unit adds it, with no change of this interface.
+ * IT: the preset runs 5 iterations of it; cfg.variational_iters must be 0.  The refinement is gfw_flow_dis_refined below, a call of its
+ * own with a configuration of its own: this interface, its rejection of a non-zero variational_iters and its kernels are pinned by
+ * their tests as they were built, and the refinement's parameters (six of them) have no room in the one slot left here.
  * OpenCV's source is not part of the reference tree, so nothing reference-produced pins the flow: the contract is tests/_disstmt.py, the
  * published scheme stated operation by operation with every sum over a patch's 64 pixels an INTEGER (integer gradients, fixed-point
  * bilinear samples, exact sums, one conversion to f32 per sum), which the device equals to the bit.  The statement is first held to a
@@ -899,7 +901,7 @@ int   gfw_corners_shi_tomasi(gfw_ctx *ctx, const gfw_corners_cfg *cfg, const voi
  * outputs untouched: null arguments for non-zero counts, negative counts, a frame index out of range, a pair of a frame with itself,
  * stride < width, a size with coarsest < finest_scale (the size named), a finest_scale other than 1 or 2, a non-zero variational_iters
  * or reserved slot, counts over the limits.
- * NOT covered: variational refinement; AKAZE. */
+ * NOT covered: variational refinement (gfw_flow_dis_refined below); AKAZE. */
 typedef struct gfw_flow_dis_cfg {
     int32_t width, height, stride;         /* of every frame of the call */
     int32_t finest_scale;                  /* 1 | 2 */
@@ -909,6 +911,35 @@ typedef struct gfw_flow_dis_cfg {
 int   gfw_flow_dis(gfw_ctx *ctx, const gfw_flow_dis_cfg *cfg, const void *frames, int frames_on_device, int n_frames,
                    const int32_t *pair_frames, int n_pairs, float *grid_points, int32_t *grid_counts, float *flow,
                    int32_t *out_pair_first, float *points_a, float *points_b, int out_on_device);
+
+/* ---- synchronization: DIS dense optical flow WITH its variational refinement, the reference's preset as a whole ----
+ * gfw_flow_dis (above) with the refinement DISOpticalFlow_PRESET_FAST runs on every pyramid level: directly behind a level's dense
+ * field, the field is refined in place — the Brox-style energy (brightness constancy, gradient constancy, smoothness) as Kroeger et
+ * al. use it, linearised fixed_point_iters times, each linear system relaxed by sor_iters red-black SOR iterations — and the next
+ * finer level's start values, the nodes and `flow` read the refined field.  The contract is tests/_varrefstmt.py, the scheme stated
+ * operation by operation in f32 (every operator rounds once, sums in a fixed order, the second image warped once per level by
+ * gfw_flow_dis's fixed-point sampler), which the device equals to the bit.  It is first held to what refinement is for: on the planted
+ * motions every pair's mean interior node error falls and its worst does not rise (tests/test_varref_statement.py).
+ * THE DEFAULTS — alpha 20, delta 5, gamma 10, 5 fixed-point and 5 SOR iterations, omega 1.6, and the fixed zeta 0.1, eps 0.001 — ARE
+ * THE VALUES OpenCV's DIS IMPLEMENTATION SETS TO THE BUILDER'S BEST KNOWLEDGE: OpenCV's source is not part of the reference tree and
+ * nothing in this tree confirms them.  OpenCV's own buffers, its floating-point warp and its thread striping are not reproduced.
+ *   cfg         gfw_flow_dis's, variational_iters = 0 here too: the count lives in ref.  A non-zero one is rejected with both named
+ *   ref         fixed_point_iters 0 .. 64 (the preset: 5; 0 issues no refinement launch and equals gfw_flow_dis to the bit), sor_iters
+ *               1 .. 64, alpha (smoothness), delta (brightness constancy), gamma (gradient constancy) finite and > 0, omega finite
+ *               in (0, 2), reserved = 0
+ *   everything else: gfw_flow_dis's arguments, contracts, limits and rejections.  The refinement adds 17 floats per pixel and pair of
+ *   the finest level to the device work space; both together stay under 16 GiB.
+ * Launches: gfw_flow_dis's, plus per level 2 + fixed_point_iters (1 + 2 sor_iters) — 57 at 5 / 5; 252 instead of 24 for 1280 x 720
+ * at finest_scale 2 — whatever the number of pairs. */
+typedef struct gfw_flow_varref_cfg {
+    int32_t fixed_point_iters, sor_iters;  /* the preset: 5, 5 */
+    float   alpha, delta, gamma, omega;    /* 20, 5, 10, 1.6 */
+    int32_t reserved[2];                   /* 0 */
+} gfw_flow_varref_cfg;
+int   gfw_flow_dis_refined(gfw_ctx *ctx, const gfw_flow_dis_cfg *cfg, const gfw_flow_varref_cfg *ref, const void *frames,
+                           int frames_on_device, int n_frames, const int32_t *pair_frames, int n_pairs, float *grid_points,
+                           int32_t *grid_counts, float *flow, int32_t *out_pair_first, float *points_a, float *points_b,
+                           int out_on_device);
 
 /* First-pass audit of the fused kernel (GFW_OPT_KERNEL_VARIANT = 3): counters8 = {certified pixels,
  * certified-but-different-from-exact (must stay 0), queued to the exact path, queue overflows,

@@ -555,12 +555,13 @@ inline std::vector<FlowPair> optical_flow_pyrlk(gfw_ctx *ctx, const uint8_t *fra
     return out;
 }
 // ---- synchronization/optical_flow/opencv_dis.rs over gfw_flow_dis: `OFOpenCVDis::optical_flow_to` (the reference's DEFAULT method 2) for ALL frame pairs in one
-// device call: the DIS dense flow with the parameters of DISOpticalFlow_PRESET_FAST — WITHOUT its variational refinement, which is not built — read at the grid points
-// of :62-119.  `frames`: n u8 gray planes back to back (host memory), `pairs` (first frame, second frame); finest_scale 2 as the reference, or 1.  One FlowPair per
+// device call: the DIS dense flow with the parameters of DISOpticalFlow_PRESET_FAST read at the grid points of :62-119.  `variational_iters`: the fixed-point
+// iterations of the preset's variational refinement on every level (gfw_flow_dis_refined, its other parameters at their defaults); the reference's preset is 5, the
+// default here stays 0, the unrefined gfw_flow_dis.  `frames`: n u8 gray planes back to back (host memory), `pairs` (first frame, second frame); finest_scale 2 as the reference, or 1.  One FlowPair per
 // pair: every node the grid keeps in the first frame and where the flow takes it, unfiltered (:113-117); has_points only with at least 10 nodes (:126) — what
 // estimate_poses_almeida takes.
 inline std::vector<FlowPair> optical_flow_dis(gfw_ctx *ctx, const uint8_t *frames, int n_frames, int width, int height, int stride, const std::vector<std::pair<int, int>> &pairs,
-                                              int finest_scale = 2) {
+                                              int finest_scale = 2, int variational_iters = 0) {
     std::vector<FlowPair> out(pairs.size());
     if (pairs.empty()) return out;
     if (!ctx) throw GyroflowCoreError(GyroflowCoreError::Unknown, "optical_flow_dis: no backend context for the optical flow");
@@ -571,7 +572,10 @@ inline std::vector<FlowPair> optical_flow_dis(gfw_ctx *ctx, const uint8_t *frame
     const size_t room = pairs.size() * (size_t)((width + step - 1) / step) * (size_t)((height + step - 1) / step);
     std::vector<float> a(room * 2 + 2), b(room * 2 + 2);
     std::vector<int32_t> pair_first(pairs.size() + 1);
-    const int rc = gfw_flow_dis(ctx, &cfg, frames, 0, n_frames, pf.data(), (int)pairs.size(), nullptr, nullptr, nullptr, pair_first.data(), a.data(), b.data(), 0);
+    const gfw_flow_varref_cfg ref = {variational_iters, 5, 20.0f, 5.0f, 10.0f, 1.6f, {0, 0}};
+    const int rc = variational_iters == 0
+        ? gfw_flow_dis(ctx, &cfg, frames, 0, n_frames, pf.data(), (int)pairs.size(), nullptr, nullptr, nullptr, pair_first.data(), a.data(), b.data(), 0)
+        : gfw_flow_dis_refined(ctx, &cfg, &ref, frames, 0, n_frames, pf.data(), (int)pairs.size(), nullptr, nullptr, nullptr, pair_first.data(), a.data(), b.data(), 0);
     if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
     for (size_t p = 0; p < pairs.size(); ++p) {
         if (pair_first[p + 1] - pair_first[p] < 10) continue;

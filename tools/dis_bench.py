@@ -6,7 +6,10 @@ tracked by pyramidal Lucas-Kanade.
 The frames are tools/flow_bench.py's: crops of one analytic texture shifted by whole pixels from frame to frame, 2 .. 7 px a pair, so the true flow is known.
 The first `--check` pairs are compared with the numpy statement of the tests (tests/_disstmt.py) to the bit.  Nothing is timed against the reference, which runs
 OpenCV per frame on a thread pool and cannot be built here.
-usage: dis_bench.py [--groups N] [--frames N] [--width W] [--height H] [--finest 1|2] [--reps R] [--check N] [--out FILE]   (GFW_LIBRARY selects an A/B build.)"""
+--variational N (N > 0): in the same run, after each unrefined measurement, gfw_flow_dis_refined with N fixed-point iterations a level (the preset: 5; the other
+parameters at their defaults) on the same clip — wall, time on the stream, the ratio to the unrefined call of that run, the launches — its first `--check` pairs
+compared with tests/_varrefstmt.py to the bit.
+usage: dis_bench.py [--groups N] [--frames N] [--width W] [--height H] [--finest 1|2] [--reps R] [--check N] [--variational N] [--out FILE]   (GFW_LIBRARY selects an A/B build.)"""
 import argparse
 import json
 import os
@@ -22,6 +25,7 @@ import numpy as np  # noqa: E402
 
 from gyroflow_amd import abi, synthetic as S, warp  # noqa: E402
 import _disstmt as DS  # noqa: E402
+import _varrefstmt as VS  # noqa: E402
 import flow_bench as FB  # noqa: E402
 
 DIS_ORDER = ("grid_points", "grid_counts", "flow", "pair_first", "points_a", "points_b")
@@ -51,6 +55,7 @@ def main():
     ap.add_argument("--finest", type=int, default=2)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--check", type=int, default=1)
+    ap.add_argument("--variational", type=int, default=0)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -71,6 +76,14 @@ def main():
         t0 = time.perf_counter()
         want = DS.flow_dis(frames, pairs[:args.check], args.finest)
         stmt_s = (time.perf_counter() - t0) / max(args.check, 1)
+        if args.variational:
+            be.flow_dis(d_frames.data_ptr(), args.width, pairs, args.finest, shape=frames.shape, variational_iters=args.variational)      # warm-up: the larger work space
+            ref = VS.DEFAULT._replace(fixed_point_iters=args.variational)
+            want_ref = VS.flow_dis_refined(frames, pairs[:args.check], args.finest, ref)
+            levels = DS.coarsest_scale(args.width, args.height) - args.finest + 1
+            result["variational_iters"] = args.variational
+            result["launches"] = {"unrefined": 3 + DS.coarsest_scale(args.width, args.height) + 4 * levels,
+                                  "refined": 3 + DS.coarsest_scale(args.width, args.height) + (4 + 2 + ref.fixed_point_iters * (1 + 2 * ref.sor_iters)) * levels}
         z = lambda shape, t: torch.zeros(shape, dtype=t, device=dev)
         dis_outs = {"grid_points": None, "grid_counts": None, "flow": None, "pair_first": z(len(pairs) + 1, torch.int32), "points_a": z((room, 2), torch.float32),
                     "points_b": z((room, 2), torch.float32)}
@@ -99,6 +112,23 @@ def main():
                    "device_output_equals_host_output": dis_outs["points_b"].cpu().numpy()[:int(first[-1])].tobytes() == got["points_b"].tobytes(),
                    "points": int(first[-1]), "median_error_px": float(np.median(err)), "p99_error_px": float(np.percentile(err, 99)),
                    "pyrlk_kept": int(lf[-1]), "pyrlk_median_error_px": float(np.median(lk_err))}
+            if args.variational:
+                t0 = time.perf_counter()
+                rgot = be.flow_dis(d_frames.data_ptr(), args.width, pairs, args.finest, flow=rep == 0, shape=frames.shape, variational_iters=args.variational)
+                rwall = time.perf_counter() - t0
+                ref_ms = streamed(be, dev, lambda: be.flow_dis(d_frames.data_ptr(), args.width, pairs, args.finest, variational_iters=args.variational,
+                                                               out_ptrs=tuple(None if dis_outs[n] is None else dis_outs[n].data_ptr() for n in DIS_ORDER), shape=frames.shape))
+                rfirst = rgot["pair_first"]
+                rerr = np.concatenate([np.linalg.norm((rgot["points_b"][rfirst[p]:rfirst[p + 1]] - rgot["points_a"][rfirst[p]:rfirst[p + 1]]) - true[p], axis=1) for p in range(len(pairs))])
+                rsame = rgot["points_a"][:k].tobytes() == want_ref["points_a"].tobytes() and rgot["points_b"][:k].tobytes() == want_ref["points_b"].tobytes() and \
+                    rfirst[:args.check + 1].tobytes() == want_ref["pair_first"].tobytes() and (rep != 0 or rgot["flow"][:args.check].tobytes() == want_ref["flow"].tobytes())
+                run.update(refined_wall_s=rwall, refined_stream_ms=ref_ms, refined_over_unrefined=ref_ms / dis_ms, refined_equals_statement=bool(rsame),
+                           refined_device_output_equals_host_output=dis_outs["points_b"].cpu().numpy()[:int(rfirst[-1])].tobytes() == rgot["points_b"].tobytes(),
+                           refined_median_error_px=float(np.median(rerr)), refined_p99_error_px=float(np.percentile(rerr, 99)))
+                print("run %d: gfw_flow_dis_refined, %d fixed-point iterations a level: %.3f ms wall with host outputs, %.3f ms on the stream = %.3f x the unrefined call "
+                      "(+ %.3f ms), %d launches instead of %d | device = statement on %d pairs: %s | error against the true shift: median %.4f px, 99 %% %.4f px" %
+                      (rep, args.variational, rwall * 1e3, ref_ms, ref_ms / dis_ms, ref_ms - dis_ms, result["launches"]["refined"], result["launches"]["unrefined"], args.check,
+                       rsame, run["refined_median_error_px"], run["refined_p99_error_px"]), flush=True)
             result["runs"].append(run)
             print("run %d: gfw_flow_dis of %d pairs at %d x %d, finest scale %d: %.3f ms wall with host outputs, %.3f ms on the stream | gfw_flow_pyrlk on the same grid "
                   "(%d nodes a frame): %.3f ms wall, %.3f ms on the stream | the numpy statement %.2f s a pair | device = statement on %d pairs: %s | %d points, error "
@@ -107,7 +137,8 @@ def main():
                    run["median_error_px"], run["p99_error_px"], run["pyrlk_kept"], run["pyrlk_median_error_px"]), flush=True)
     finally:
         be.close()
-    ok = all(r["device_equals_statement"] and r["device_output_equals_host_output"] for r in result["runs"])
+    ok = all(r["device_equals_statement"] and r["device_output_equals_host_output"] and r.get("refined_equals_statement", True) and
+             r.get("refined_device_output_equals_host_output", True) for r in result["runs"])
     print(json.dumps(result))
     if args.out:
         with open(args.out, "w") as fo:
