@@ -122,6 +122,18 @@ class PoseAlmeidaCfg(C.Structure):
                 ("camera_matrix", C.c_double * 9)]
 
 
+class PoseEssentialCfg(C.Structure):
+    """``gfw_pose_essential_cfg``: what every pair of an essential-matrix pose estimation call shares."""
+    _fields_ = [("video_width", C.c_int32), ("video_height", C.c_int32), ("flow_width", C.c_int32), ("flow_height", C.c_int32),
+                ("num_iters", C.c_int32), ("min_front", C.c_int32), ("inlier_threshold", C.c_double), ("reserved", C.c_int32 * 2),
+                ("camera_matrix", C.c_double * 9)]
+
+    def __init__(self, *a, **kw):
+        kw.setdefault("inlier_threshold", 1e-6)
+        kw.setdefault("min_front", 10)
+        super().__init__(*a, **kw)
+
+
 class FlowPyrLKCfg(C.Structure):
     """``gfw_flow_pyrlk_cfg``: what every frame of a pyramidal Lucas-Kanade optical-flow call shares."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("point_mode", C.c_int32), ("reserved", C.c_int32)]
@@ -155,7 +167,8 @@ FLOW_RING_SLOTS = 2              # staging slots of gfw_flow_pyrlk
 DIS_NODES_MAX, DIS_PAIRS_MAX, DIS_FRAMES_MAX, DIS_SIDE_MAX = 4096, 65535, 4096, 8192      # gfw_flow_dis
 DIS_RING_SLOTS = 2               # staging slots of gfw_flow_dis and gfw_flow_dis_refined
 VARREF_ITERS_MAX, VARREF_PLANES = 64, 17          # gfw_flow_dis_refined: fixed-point / SOR iterations; work-space floats per pixel and pair of the finest level
-POSE_PAIR_POINTS_MAX, POSE_PAIRS_MAX, POSE_ROUNDS_MAX = 4096, 65535, 1024      # gfw_pose_almeida
+POSE_PAIR_POINTS_MAX, POSE_PAIRS_MAX, POSE_ROUNDS_MAX = 4096, 65535, 1024      # gfw_pose_almeida, gfw_pose_essential
+POSE_DRAWS_K_MAX = 16            # gfw_pose_draws_k: distinct indices of a round
 SYNC_FINE_CANDIDATES = 200       # the second stage's candidates
 SYNC_PAIR_POINTS_MAX = 4096
 SYNC_GYRO_RANGES_MAX, SYNC_GYRO_EST_MAX, SYNC_GYRO_SAMPLES_MAX, SYNC_GYRO_CANDIDATES_MAX = 65535, 65536, 1 << 22, 2000000      # gfw_sync_gyro_*: per call / per range
@@ -253,6 +266,8 @@ def bind(lib):
     lib.gfw_sync_optim_points.argtypes = [vp, vp, C.c_int64, C.c_double, i32, vp, i32, vp, vp, vp, vp, vp, i32]; lib.gfw_sync_optim_points.restype = i32
     lib.gfw_pose_almeida.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(PoseAlmeidaCfg), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_pose_almeida.restype = i32
     lib.gfw_pose_draws.argtypes = [C.c_uint64, vp, i32, i32, i32, vp, vp, vp]; lib.gfw_pose_draws.restype = i32
+    lib.gfw_pose_essential.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(PoseEssentialCfg), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_pose_essential.restype = i32
+    lib.gfw_pose_draws_k.argtypes = [C.c_uint64, vp, i32, i32, i32, vp]; lib.gfw_pose_draws_k.restype = i32
     lib.gfw_flow_pyrlk.argtypes = [vp, C.POINTER(FlowPyrLKCfg), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_flow_pyrlk.restype = i32
     lib.gfw_flow_dis.argtypes = [vp, C.POINTER(FlowDisCfg), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_flow_dis.restype = i32
     lib.gfw_flow_dis_refined.argtypes = [vp, C.POINTER(FlowDisCfg), C.POINTER(FlowVarrefCfg), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_flow_dis_refined.restype = i32
@@ -286,7 +301,7 @@ EXPORTS = ["gfw_abi_version", "gfw_list_devices", "gfw_set_device", "gfw_get_inf
            "gfw_build_matrices_batch_stab", "gfw_zoom_fovs_stab", "gfw_sync_visual_costs", "gfw_sync_visual_search",
            "gfw_lowpass_gyro", "gfw_sync_gyro_costs", "gfw_sync_gyro_search",
            "gfw_optim_tables", "gfw_optim_resample", "gfw_sync_optim_rank", "gfw_sync_optim_points",
-           "gfw_pose_almeida", "gfw_pose_draws", "gfw_flow_pyrlk", "gfw_corners_shi_tomasi", "gfw_flow_dis", "gfw_flow_dis_refined"]
+           "gfw_pose_almeida", "gfw_pose_draws", "gfw_pose_essential", "gfw_pose_draws_k", "gfw_flow_pyrlk", "gfw_corners_shi_tomasi", "gfw_flow_dis", "gfw_flow_dis_refined"]
 
 
 def load_library(path=None):

@@ -27,6 +27,7 @@
 #include "gfw_sync_gyro.h"
 #include "gfw_sync_optim.h"
 #include "gfw_pose.h"
+#include "gfw_pose_essential.h"
 #include "gfw_flow.h"
 #include "gfw_corners.h"
 #include "gfw_dis.h"
@@ -37,6 +38,7 @@
 #include "gfw_sync_gyro_host.h"
 #include "gfw_sync_optim_host.h"
 #include "gfw_pose_host.h"
+#include "gfw_pose_essential_host.h"
 #include "gfw_flow_host.h"
 #include "gfw_corners_host.h"
 #include "gfw_dis_host.h"
@@ -129,7 +131,7 @@ struct gfw_ctx {
     // gfw_sync_optim_*: the gyro series as f32, the window, the twiddle table and the trim ranges staged the same way (work space: the visual search's)
     static constexpr int kOptimSlots = 2;
     StagingRing<kOptimSlots> optim_ring;
-    // gfw_pose_almeida: pair firsts, points and draws staged the same way (work space: the visual search's)
+    // gfw_pose_almeida and gfw_pose_essential: pair firsts, points and draws staged the same way (work space: the visual search's)
     static constexpr int kPoseSlots = 2;
     StagingRing<kPoseSlots> pose_ring;
     // gfw_flow_pyrlk: pairs, features and host frames staged the same way (work space: the visual search's)
@@ -1026,6 +1028,7 @@ int gfw_undistort_clip_lens(gfw_ctx *c, int n_frames, int nplanes, const gfw_buf
 #include "gfw_api_sync.inc"
 #include "gfw_api_sync_optim.inc"
 #include "gfw_api_pose.inc"
+#include "gfw_api_pose_essential.inc"
 #include "gfw_api_flow.inc"
 #include "gfw_api_corners.inc"
 #include "gfw_api_dis.inc"

@@ -1,0 +1,71 @@
+// gfw_api_pose_essential.inc — part of gfw_api.hip (textually included): gfw_pose_essential and gfw_pose_draws_k.  What they check and stage is gfw_pose_essential_host.h's.
+
+// Essential-matrix pose estimation of every frame pair of a call (gfw_pose_essential.hip).  See include/gfwarp.h for the argument contract.
+extern "C" int gfw_pose_essential(gfw_ctx *c, const gfw_kernel_params *p, const gfw_pose_essential_cfg *cfg, const int32_t *pair_first, const float *points_a,
+                                  const float *points_b, int n_pairs, const int32_t *octets, float *quats, double *rotations, double *essential, int32_t *best,
+                                  int32_t *round_inliers, double *round_fits, int out_on_device) {
+    if (!c || !p || !cfg) { set_error("bad pose arguments (null context / params / configuration)"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (cfg->reserved[0] || cfg->reserved[1]) { set_error("bad pose configuration: the reserved slots must be 0"); return GFW_ERR_INVALID_ARGUMENT; }
+    if (cfg->video_width < 1 || cfg->video_height < 1 || cfg->flow_width < 1 || cfg->flow_height < 1 || !(cfg->inlier_threshold >= 0.0) || cfg->min_front < 0) {
+        set_error("bad pose configuration: video %d x %d, optical flow %d x %d, inlier threshold %g, min_front %d", cfg->video_width, cfg->video_height, cfg->flow_width, cfg->flow_height, cfg->inlier_threshold, cfg->min_front);
+        return GFW_ERR_INVALID_ARGUMENT; }
+    if (p->flags & (256 | 512 | 1024)) {                                     // HAS_IBIS_DATA | HAS_MESH_DATA | HAS_FPD_DATA
+        set_error("pose estimation does not cover per-frame IBIS/OIS shifts, lens meshes or focal-plane distortion data (flags 0x%x)", p->flags);
+        return GFW_ERR_INVALID_ARGUMENT; }
+    const double *K = cfg->camera_matrix;
+    if (p->f[0] != (float)K[0] || p->f[1] != (float)K[4] || p->c[0] != (float)K[2] || p->c[1] != (float)K[5]) {
+        set_error("the kernel parameters' f (%g, %g) / c (%g, %g) are not the f32 cast of camera_matrix (%g, %g) / (%g, %g)", (double)p->f[0], (double)p->f[1], (double)p->c[0], (double)p->c[1], K[0], K[4], K[2], K[5]);
+        return GFW_ERR_INVALID_ARGUMENT; }
+    const GfwPoseEssInputs I = {pair_first, points_a, points_b, n_pairs, octets, cfg->num_iters};
+    char why[256];
+    if (!gfw_pose_ess_check(I, why, sizeof(why))) { set_error("%s", why); return GFW_ERR_INVALID_ARGUMENT; }
+    if (n_pairs == 0) return GFW_OK;
+    if (!quats || !rotations || !essential || !best) { set_error("bad pose arguments (a null quats / rotations / essential / best array)"); return GFW_ERR_INVALID_ARGUMENT; }
+    const GfwPoseEssLayout S = gfw_pose_ess_layout(I);
+    if (S.total > ((size_t)1 << 31)) { set_error("the call stages %zu bytes (%d pairs x %d rounds): at most 2 GiB", S.total, n_pairs, cfg->num_iters); return GFW_ERR_INVALID_ARGUMENT; }
+    API_TRY(enter_device(c));
+    // pairs, points and draws through pinned memory in one copy: it is enqueued, the caller's arrays are free on return
+    GfwPoseEssArgs A;
+    memset(&A, 0, sizeof(A));
+    StagedBlock B;
+    HIP_TRY(c->pose_ring.acquire(S.total, c->stream, &B.slot), GFW_ERR_HIP);
+    gfw_pose_ess_fill(S, I, B.h(), B.d(), A);
+    gfw_pose_ess_constants(cfg->video_width, cfg->video_height, cfg->flow_width, cfg->flow_height, cfg->inlier_threshold, cfg->min_front, A);
+    HIP_TRY(B.upload(S.total, c->stream), GFW_ERR_HIP);
+    const size_t rounds = (size_t)n_pairs * (size_t)cfg->num_iters, total = (size_t)A.total;
+    CallOutputs O(c->d_out, out_on_device);
+    const int o_quats = O.add(quats, sizeof(float) * 4 * (size_t)n_pairs);
+    const int o_rot = O.add(rotations, sizeof(double) * 9 * (size_t)n_pairs);
+    const int o_ess = O.add(essential, sizeof(double) * 9 * (size_t)n_pairs);
+    const int o_best = O.add(best, sizeof(int32_t) * 4 * (size_t)n_pairs);
+    const int o_counts = O.add(round_inliers, sizeof(int32_t) * rounds);
+    const int o_fits = O.add(round_fits, sizeof(double) * 9 * rounds);
+    HIP_TRY(O.reserve(), GFW_ERR_HIP);
+    // device work space: what the prepare stage leaves per point, and the rounds' fits and counts where the caller does not ask for them
+    BlockLayout W;
+    const size_t w_und = W.add(sizeof(float4) * total), w_fits = W.add(sizeof(double) * 9 * rounds), w_counts = W.add(sizeof(int32_t) * rounds);
+    HIP_TRY(c->d_sync_work.ensure(W.total + 16), GFW_ERR_HIP);
+    char *wk = (char *)c->d_sync_work.ptr;
+    A.und = (float4 *)(wk + w_und);
+    A.fits = round_fits ? (double *)O.dev(o_fits) : (double *)(wk + w_fits);
+    A.counts = round_inliers ? (int32_t *)O.dev(o_counts) : (int32_t *)(wk + w_counts);
+    A.quats = (float *)O.dev(o_quats); A.rotations = (double *)O.dev(o_rot); A.essential = (double *)O.dev(o_ess); A.best = (int32_t *)O.dev(o_best);
+    GfwCommon C;
+    fill_common(c, p, nullptr, nullptr, 0, C);
+    HIP_TRY(gfw_launch_pose_ess_prepare(*p, C, A, c->stream), GFW_ERR_HIP);
+    HIP_TRY(gfw_launch_pose_ess_fit(A, c->stream), GFW_ERR_HIP);
+    HIP_TRY(gfw_launch_pose_ess_count(A, c->stream), GFW_ERR_HIP);
+    HIP_TRY(gfw_launch_pose_ess_pick(A, c->stream), GFW_ERR_HIP);
+    HIP_TRY(B.free_again(c->stream), GFW_ERR_HIP);                          // behind the last launch that reads the slot's device side
+    c->last_backend = "pose_essential";
+    HIP_TRY(O.finish(c->stream, c->synchronous), GFW_ERR_HIP);
+    return GFW_OK;
+}
+
+// k distinct indices a round (gfw_pose_draws_k_host): host only, no context
+extern "C" int gfw_pose_draws_k(uint64_t seed, const int32_t *pair_first, int n_pairs, int num_iters, int k, int32_t *tuples) {
+    if (!gfw_pose_draws_k_host(seed, pair_first, n_pairs, num_iters, k, tuples)) {
+        set_error("bad pose draw arguments (a negative count, a null array, a descending pair_first, a pair above %d points, or k outside 1 .. %d)", GFW_POSE_PAIR_MAX, GFW_POSE_DRAWS_K_MAX);
+        return GFW_ERR_INVALID_ARGUMENT; }
+    return GFW_OK;
+}

@@ -136,3 +136,31 @@ inline bool gfw_pose_draws_host(uint64_t seed, const int32_t *pair_first, int n_
     }
     return true;
 }
+
+#define GFW_POSE_DRAWS_K_MAX 16     // distinct indices of a round
+// gfw_pose_draws_k: the generator above for k distinct indices a round (the octets of gfw_pose_essential are k = 8).  Draw j is the
+// r-th of the n - j indices not drawn yet, r = below(stream, j, n - j): r steps past every earlier draw in ascending order.  At k = 3 these are gfw_pose_draws'
+// triples to the bit.  A pair under k points gets zeros.
+inline bool gfw_pose_draws_k_host(uint64_t seed, const int32_t *pair_first, int n_pairs, int num_iters, int k, int32_t *tuples) {
+    if (n_pairs < 0 || num_iters < 0 || k < 1 || k > GFW_POSE_DRAWS_K_MAX || (n_pairs && !pair_first) || (n_pairs && num_iters && !tuples)) return false;
+    for (int p = 0; p < n_pairs; ++p) if (pair_first[p + 1] < pair_first[p] || pair_first[p + 1] - pair_first[p] > GFW_POSE_PAIR_MAX) return false;
+    for (int p = 0; p < n_pairs; ++p) {
+        const int n = pair_first[p + 1] - pair_first[p];
+        for (int it = 0; it < num_iters; ++it) {
+            const uint64_t stream = gfw_pose_mix(seed ^ (((uint64_t)(uint32_t)p << 32) | (uint32_t)it));
+            int32_t *t = tuples + ((size_t)p * num_iters + it) * k;
+            int32_t sorted[GFW_POSE_DRAWS_K_MAX];
+            for (int j = 0; j < k; ++j) t[j] = 0;
+            if (n < k) continue;
+            for (int j = 0; j < k; ++j) {
+                int r = (int)gfw_pose_below(stream, (uint64_t)j, (uint32_t)(n - j));
+                int at = 0;
+                for (; at < j && r >= sorted[at]; ++at) ++r;                          // past the earlier draws, ascending
+                for (int m = j; m > at; --m) sorted[m] = sorted[m - 1];
+                sorted[at] = r;
+                t[j] = r;
+            }
+        }
+    }
+    return true;
+}

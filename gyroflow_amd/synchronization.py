@@ -24,8 +24,16 @@ here.  The estimated rates are the caller's input: ``estimated_gyro`` makes them
     gyro = synchronization.estimated_gyro({ts_us: pose and pose["euler"]}, fps, lpf, final_pass)
 
 ``PoseAlmeida`` (estimate_pose/almeida.rs): one camera rotation per pair of frames from its matched optical-flow points, ALL pairs in one device call,
-``Backend.pose_almeida`` (gfw_pose_almeida).  The reference draws its RANSAC rounds from an unseeded generator; here a seed decides them.  The other three pose
-methods are not covered.
+``Backend.pose_almeida`` (gfw_pose_almeida).  The reference draws its RANSAC rounds from an unseeded generator; here a seed decides them.
+
+    poses = synchronization.estimate_poses_essential(compute_params, pairs, backend, seed=0)
+    poses = synchronization.estimate_poses(pose_method, compute_params, pairs, backend, seed=0)
+
+Pose methods 0 (``PoseFindEssentialMat``) and 2 (``PoseEightPoint``, estimate_pose/mod.rs:27-36) both map to ``Backend.pose_essential`` (gfw_pose_essential):
+the rotation part of an essential matrix fitted to the pair's undistorted bearings — for pairs whose camera also moved, which Almeida's rotation-only model
+does not explain.  Their solvers (OpenCV's findEssentialMat / recoverPose, the arrsac and eight-point crates) are not in the reference tree: neither OpenCV's
+LMedS nor ARRSAC is reproduced; what runs is the eight-point scheme in a RANSAC loop that tests/_posessstmt.py states.  ``estimate_poses`` dispatches on the
+method as ``EstimatePoseMethod::from`` does (1 and unknown: Almeida); method 3 (``PoseFindHomography``) is not covered.
 
     matched = synchronization.optical_flow_pyrlk(frames, pairs, features=None, backend=backend)
 
@@ -279,6 +287,49 @@ def estimate_poses_almeida(compute_params, pairs, backend, seed=0, flow_size=Non
         out[i] = dict(rotation=rotations[k], quat=quats[k], euler=tuple(scaled_axis(rotations[k]) * (cp.scaled_fps / float(every_nth_frame))),
                       inliers=int(best[k, 0]), round=int(best[k, 1]))
     return out
+
+
+def pose_essential_inputs(compute_params, flow_size, num_iters=200, inlier_threshold=1e-6, min_front=10):
+    """What gfw_pose_essential takes for these parameters: (KernelParams, abi.PoseEssentialCfg), as ``pose_inputs`` makes them for gfw_pose_almeida."""
+    kp, almeida = pose_inputs(compute_params, flow_size, num_iters)
+    cfg = abi.PoseEssentialCfg(video_width=almeida.video_width, video_height=almeida.video_height, flow_width=almeida.flow_width, flow_height=almeida.flow_height,
+                               num_iters=int(num_iters), inlier_threshold=float(inlier_threshold), min_front=int(min_front))
+    for i in range(9):
+        cfg.camera_matrix[i] = almeida.camera_matrix[i]
+    return kp, cfg
+
+
+def estimate_poses_essential(compute_params, pairs, backend, seed=0, flow_size=None, every_nth_frame=1, num_iters=200, inlier_threshold=1e-6):
+    """``PoseEstimator::process_detected_frames`` (synchronization/mod.rs:110-167) with pose method 0 or 2 for all frame pairs in ONE device call
+    (``Backend.pose_essential``).  ``pairs`` as ``estimate_poses_almeida`` takes them; ``seed`` decides the rounds' eight points (``warp.pose_draws_k``).  Returns
+    one entry per pair: None (no points, or no rotation found: under 8 points, under 8 inliers, or too few of them in front of both cameras), or
+    dict(rotation f64 [3][3], quat f32 [4] (w, i, j, k), euler = scaled_axis(rotation) * (scaled_fps / every_nth_frame), inliers, round, front)."""
+    from . import warp
+    cp = compute_params
+    live = [i for i, p in enumerate(pairs) if p is not None]
+    out = [None] * len(pairs)
+    if not live:
+        return out
+    kp, cfg = pose_essential_inputs(cp, flow_size or (cp.width, cp.height), num_iters, inlier_threshold)
+    sets = [pairs[i] for i in live]
+    octets = warp.pose_draws_k(seed, [len(np.asarray(a).reshape(-1, 2)) for a, _ in sets], cfg.num_iters, 8)
+    quats, rotations, _essential, best = backend.pose_essential(kp, cfg, sets, octets)
+    for k, i in enumerate(live):
+        if best[k, 3]:
+            out[i] = dict(rotation=rotations[k], quat=quats[k], euler=tuple(scaled_axis(rotations[k]) * (cp.scaled_fps / float(every_nth_frame))),
+                          inliers=int(best[k, 0]), round=int(best[k, 1]), front=int(best[k, 2]))
+    return out
+
+
+def estimate_poses(pose_method, compute_params, pairs, backend, **kw):
+    """The pose method of a sync (estimate_pose/mod.rs:27-36): 0 (`PoseFindEssentialMat`) and 2 (`PoseEightPoint`) -> ``estimate_poses_essential``; 1 and every
+    unknown value -> ``estimate_poses_almeida``, as `EstimatePoseMethod::from` falls back; 3 (`PoseFindHomography`) is not covered."""
+    method = int(pose_method)
+    if method == 3:
+        raise NotImplementedError("pose method 3 (PoseFindHomography) is not covered")
+    if method in (0, 2):
+        return estimate_poses_essential(compute_params, pairs, backend, **kw)
+    return estimate_poses_almeida(compute_params, pairs, backend, **kw)
 
 
 def estimated_gyro(results, fps, lpf=0.0, final_pass=False):

@@ -508,6 +508,29 @@ class Backend:
         self._check(self.lib.gfw_pose_almeida(*args, q(quats), q(rot), q(best), q(ri) if rounds else None, q(rf) if rounds else None, 0))
         return (quats, rot, best, ri, rf) if rounds else (quats, rot, best)
 
+    def pose_essential(self, params, cfg, pairs, octets, rounds=False, out_ptrs=None):
+        """Essential-matrix pose estimation (pose methods 0 and 2 of estimate_pose/mod.rs:27-36) of every frame pair in one device call (gfw_pose_essential), the
+        random draws given: the rotation part of an essential matrix fitted to the pair's undistorted bearings.  Neither OpenCV's LMedS nor ARRSAC is reproduced.
+
+        ``params``: the KernelParams `undistort_points` builds; ``cfg``: abi.PoseEssentialCfg; ``pairs``: [(points_a [n][2], points_b [n][2])] optical-flow pixels;
+        ``octets``: int32 [n_pairs][num_iters][8] (``pose_draws_k`` makes them).  Returns (quats f32 [n_pairs][4] (w, i, j, k), rotations f64 [n_pairs][3][3],
+        essential f64 [n_pairs][9], best int32 [n_pairs][4] (inliers, round, front, found)) — with ``rounds`` also every round's inliers int32 [n_pairs][num_iters]
+        and fit f64 [n_pairs][num_iters][9] — or, with ``out_ptrs`` = (quats, rotations, essential, best, round_inliers or None, round_fits or None) device
+        pointers, None: in order on the stream."""
+        first, pa, pb = self._pose_pairs(pairs)
+        n, iters = len(pairs), int(cfg.num_iters)
+        oc = np.ascontiguousarray(octets, dtype=np.int32).reshape(-1)
+        assert oc.size == n * iters * 8, "octets: [n_pairs][num_iters][8]"
+        args = (self.ctx, C.byref(params), C.byref(cfg), first.ctypes.data, pa.ctypes.data, pb.ctypes.data, n, oc.ctypes.data if oc.size else None)
+        if out_ptrs is not None:
+            self._check(self.lib.gfw_pose_essential(*args, *out_ptrs, 1))
+            return None
+        quats, rot, ess, best = np.zeros((n, 4), dtype=np.float32), np.zeros((n, 3, 3)), np.zeros((n, 9)), np.zeros((n, 4), dtype=np.int32)
+        ri, rf = np.zeros((n, iters), dtype=np.int32), np.zeros((n, iters, 9))
+        q = lambda a: a.ctypes.data if a.size else None
+        self._check(self.lib.gfw_pose_essential(*args, q(quats), q(rot), q(ess), q(best), q(ri) if rounds else None, q(rf) if rounds else None, 0))
+        return (quats, rot, ess, best, ri, rf) if rounds else (quats, rot, ess, best)
+
     @staticmethod
     def _flow_features(features):
         """one [n][2] array per frame -> (feat_first int32 [n_frames + 1], features f32 [total][2]) as gfw_flow_pyrlk takes them (kept alive by the caller)"""
@@ -746,6 +769,21 @@ def pose_draws(seed, counts, num_iters, num_samples, lists=True):
     if not lists:
         return triples, None
     return triples, [flat[sf[p]:sf[p + 1]].reshape(int(num_iters), lens[p]).copy() for p in range(n)]
+
+
+def pose_draws_k(seed, counts, num_iters, k=8):
+    """k distinct indices a round and pair on the host (gfw_pose_draws_k; no context, no GPU): ``counts`` = the points of each pair -> int32 [n_pairs][num_iters][k]
+    (zeros for a pair under k points).  gfw_pose_draws' generator: at k = 3 its triples to the bit.  The octets of ``Backend.pose_essential`` are k = 8."""
+    n = len(counts)
+    first = np.zeros(n + 1, dtype=np.int32)
+    if n:
+        first[1:] = np.cumsum([int(c) for c in counts])
+    tuples = np.zeros((n, int(num_iters), int(k)), dtype=np.int32)
+    lib = abi.load_library()
+    rc = lib.gfw_pose_draws_k(int(seed) & (2 ** 64 - 1), first.ctypes.data, n, int(num_iters), int(k), tuples.ctypes.data if tuples.size else None)
+    if rc < 0:
+        raise GfwError(rc, lib.gfw_last_error().decode())
+    return tuples
 
 
 def lowpass_gyro(freq, sample_rate, xyz, has=None):

@@ -616,7 +616,7 @@ int   gfw_zoom_smooth(const double *fov_minimal, int n, double adaptive_zoom_win
  * NOT covered: clips with per_frame_time_offsets, camera_stab_data or mesh_correction (in the reference the frame index, and so
  * the mesh, follows `timestamp - offs`); lens data or a video rotation keyframed inside a range; suppress_rotation; AKAZE
  * (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below; its corner detection: gfw_corners_shi_tomasi below), rs_sync.  (essential_matrix: gfw_sync_gyro_search below; optimsync: gfw_sync_optim_points below; pose estimation by the
- * Almeida method: gfw_pose_almeida below.) */
+ * Almeida method: gfw_pose_almeida below; by an essential matrix, pose methods 0 and 2: gfw_pose_essential below.) */
 typedef struct gfw_sync_search {
     int32_t width, height;            /* params.width / height: the bounds test (`w as f32`) and the readout divisor */
     int32_t horizontal_readout;
@@ -667,8 +667,8 @@ int   gfw_sync_visual_search(gfw_ctx *ctx, const gfw_kernel_params *params, cons
  * GFW_ERR_INVALID_ARGUMENT, the range named in gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative
  * counts, a negative or descending first array, a slice outside its array, a non-finite initial_offset or search_size, a negative
  * search_size, counts over the limits above.  Non-finite sample values are not rejected; the pick among NaN costs is unspecified.
- * NOT covered: AKAZE (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below; its corner detection: gfw_corners_shi_tomasi below; the DIS dense flow: gfw_flow_dis below), rs_sync itself, pose estimation other than the Almeida method (gfw_pose_almeida below; the series of
- * estimated samples is made of its rotations by gyroflow::estimated_gyro / gyroflow_amd.synchronization.estimated_gyro).
+ * NOT covered: AKAZE (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below; its corner detection: gfw_corners_shi_tomasi below; the DIS dense flow: gfw_flow_dis below), rs_sync itself, pose estimation by a homography (method 3; the Almeida method: gfw_pose_almeida below; methods 0 and 2, an essential matrix: gfw_pose_essential below; the series of
+ * estimated samples is made of their rotations by gyroflow::estimated_gyro / gyroflow_amd.synchronization.estimated_gyro).
  *
  * gfw_lowpass_gyro: Lowpass::filter_gyro_forward_backward (filtering.rs:46-74) of xyz [n][3] f64 in place, on the host (no context):
  * biquad's second-order Butterworth low-pass (Q = 1/sqrt 2), transposed direct form II, forward over the series and then backward;
@@ -754,8 +754,8 @@ int   gfw_sync_optim_points(gfw_ctx *ctx, const double *gyro, int64_t n_samples,
  * a descending pair_first, counts over the limits, an index outside its pair, a triple with a repeated index, a sample_first that does
  * not match, params->flags with HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA, f / c that are not the f32 cast of camera_matrix,
  * sizes under 1, a negative or NaN inlier angle, a non-zero reserved slot.
- * NOT covered: lens data or a refraction coefficient that changes between the pairs of one call (one call per lens); the other three
- * pose methods (their solvers are not part of the reference tree); AKAZE (the DIS dense flow: gfw_flow_dis below; the matched points of the
+ * NOT covered: lens data or a refraction coefficient that changes between the pairs of one call (one call per lens); pose method 3
+ * (`PoseFindHomography`; methods 0 and 2 map to gfw_pose_essential below, which reproduces neither OpenCV's LMedS nor ARRSAC); AKAZE (the DIS dense flow: gfw_flow_dis below; the matched points of the
  * pyramidal Lucas-Kanade method: gfw_flow_pyrlk below, its features: gfw_corners_shi_tomasi below).
  *
  * gfw_pose_draws (host only, no context): one valid set of draws per seed — not rand's sequence.  A counter-based generator:
@@ -776,6 +776,60 @@ int   gfw_pose_almeida(gfw_ctx *ctx, const gfw_kernel_params *params, const gfw_
                        float *quats, double *rotations, int32_t *best, int32_t *round_inliers, float *round_fits, int out_on_device);
 int   gfw_pose_draws(uint64_t seed, const int32_t *pair_first, int n_pairs, int num_iters, int num_samples,
                      int32_t *triples, const int32_t *sample_first, int32_t *samples);
+
+/* ---- synchronization: essential-matrix pose estimation of a clip's frame pairs in one device call ----
+ * estimate_pose/mod.rs:27-36: pose methods 0 (`PoseFindEssentialMat`) and 2 (`PoseEightPoint`) fit an essential matrix to the
+ * undistorted points of a pair and return its rotation part — what a pair needs whose camera also MOVED (parallax that no rotation
+ * explains: gfw_pose_almeida's model is rotation only).  Both methods map to this call.  Their solvers are NOT part of the reference
+ * tree — OpenCV's findEssentialMat (LMedS) / recoverPose, and the `arrsac` and `eight-point` crates — and NEITHER IS REPRODUCED: no
+ * LMedS, no ARRSAC, no five-point solver.  What runs is the published scheme both stand on, stated operation by operation in
+ * tests/_posessstmt.py with THE DRAWS AS INPUTS; the device equals that statement to the bit, and the statement is held to recovering
+ * a planted camera motion.  Nothing reference-produced is compared.  All arithmetic behind the lens inverse is f64 (+ - * / sqrt).
+ *   prepare    `undistort_points_for_optical_flow` (cpu_undistort.rs:642-650): the lens inverse of every point of both frames, identity
+ *              rotation, no P, correction amount 1.0, fov 1.0; a point without an inverse becomes (-1e6, -1e6) (:855) and takes part
+ *              like any other.  The f32 (x, y) give the f64 normalised point (x, y, 1) and its unit bearing (eight_point.rs:29-34).
+ *              (The point is scaled to the video's size in front of the unscaled K, as gfw_pose_almeida does it; the reference scales K.)
+ *   fit        per (pair, round): M = sum of kron(b2, b1) kron(b2, b1)^T over the round's 8 points; E = the eigenvector of M's smallest
+ *              eigenvalue by a cyclic Jacobi iteration (10 sweeps, (p, q) in row order, a rotation skipped where the off-diagonal is 0)
+ *   score      a point is an inlier where the squared Sampson distance of the normalised points under E is <= inlier_threshold
+ *              (1e-6: the last of the reference's three ARRSAC thresholds, 1 px at a focal length of 1000 px)
+ *   pick       the FIRST round of maximal count; its inliers in point order; M over them, folded in list order; one more solve; the SVD
+ *              of E through the Jacobi eigenvectors of E^T E; the two rotations U W V^T and U W^T V^T, both of determinant +1; per
+ *              rotation and sign of t = +-u3 the inliers whose two depths are positive; a rotation's score is the larger of its two
+ *              counts; the higher score wins, equal scores go to the larger trace (the smaller angle: eight_point.rs:50-55)
+ *   no rotation   a pair under 8 points, a best round under 8 inliers, or a winning score under min_front (10:
+ *              find_essential_mat.rs:43): found = 0, the rotation is the identity, the quaternion (1, 0, 0, 0)
+ *   octets     [n_pairs][num_iters][8] the eight distinct points of each round, indices into the pair (ignored for pairs under 8 points)
+ *   quats      [n_pairs][4] f32 (w, i, j, k); rotations [n_pairs][9] f64 row-major; essential [n_pairs][9] f64: the refit E (zeros
+ *              where the best round has under 8 inliers); best [n_pairs][4] int32: inliers, round (-1 without rounds), front count, found
+ *   round_inliers / round_fits   NULL or [n_pairs][num_iters] int32 / [n_pairs][num_iters][9] f64: every round's count and E
+ *   limits     at most 4096 points in a pair, 65535 pairs, 1024 rounds, 2 GiB staged in all
+ * Four launches for any clip, in order on the context's stream; outputs are host or device memory (out_on_device); with device
+ * outputs an asynchronous context returns without waiting.  n_pairs = 0 succeeds and writes nothing.  Rejected with
+ * GFW_ERR_INVALID_ARGUMENT, the pair named in gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative counts,
+ * a descending pair_first, counts over the limits, an octet index outside its pair or repeated within its octet, params->flags with
+ * HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA, f / c that are not the f32 cast of camera_matrix, sizes under 1, a negative or NaN
+ * threshold, a negative min_front, a non-zero reserved slot.
+ * NOT covered: what gfw_pose_almeida does not cover; pose method 3 (`PoseFindHomography`); the translation (its direction is +-u3 of
+ * `essential`, its length is not observable).
+ *
+ * gfw_pose_draws_k (host only, no context): gfw_pose_draws' counter-based generator for k distinct indices a round (1 <= k <= 16):
+ * draw j is the r-th of the indices not drawn yet, r the uniform index below n - j of counter j.  At k = 3 these are gfw_pose_draws'
+ * triples to the bit.  tuples [n_pairs][num_iters][k]; a pair under k points gets zeros. */
+typedef struct gfw_pose_essential_cfg {
+    int32_t video_width, video_height;     /* compute_params.width / height */
+    int32_t flow_width, flow_height;       /* FrameResult::frame_size */
+    int32_t num_iters;                     /* 200 */
+    int32_t min_front;                     /* 10 */
+    double  inlier_threshold;              /* 1e-6 */
+    int32_t reserved[2];                   /* 0 */
+    double  camera_matrix[9];              /* get_lens_data_at_timestamp(..).0, row-major */
+} gfw_pose_essential_cfg;
+int   gfw_pose_essential(gfw_ctx *ctx, const gfw_kernel_params *params, const gfw_pose_essential_cfg *cfg,
+                         const int32_t *pair_first, const float *points_a, const float *points_b, int n_pairs,
+                         const int32_t *octets, float *quats, double *rotations, double *essential, int32_t *best,
+                         int32_t *round_inliers, double *round_fits, int out_on_device);
+int   gfw_pose_draws_k(uint64_t seed, const int32_t *pair_first, int n_pairs, int num_iters, int k, int32_t *tuples);
 
 /* ---- synchronization: pyramidal Lucas-Kanade optical flow of a clip's frame pairs in one device call ----
  * optical_flow/opencv_pyrlk.rs:63-119 (`OFOpenCVPyrLK::optical_flow_to`, the reference's method 1): the given features of each pair's

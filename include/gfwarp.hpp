@@ -520,6 +520,48 @@ inline std::vector<PoseResult> estimate_poses_almeida(gfw_ctx *ctx, const Kernel
     }
     return out;
 }
+// ---- pose methods 0 (`PoseFindEssentialMat`) and 2 (`PoseEightPoint`) of estimate_pose/mod.rs:27-36 over gfw_pose_essential: the rotation part of an essential
+// matrix fitted to each pair's undistorted bearings, ALL frame pairs in one device call — for pairs whose camera also moved.  Neither OpenCV's LMedS nor ARRSAC is
+// reproduced (include/gfwarp.h says what runs instead).  `pairs`, `params`, `seed` as for estimate_poses_almeida; the rounds' eight points come from
+// gfw_pose_draws_k.  A pair without points, or for which no rotation is found (found = 0), has has_rotation = false; `front`: the inliers in front of both cameras.
+struct PoseEssentialResult : PoseResult { int front = 0; double essential[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; };
+inline std::vector<PoseEssentialResult> estimate_poses_essential(gfw_ctx *ctx, const KernelParams &params, const gfw_pose_essential_cfg &cfg, const std::vector<FlowPair> &pairs,
+                                                                 double scaled_fps, double every_nth_frame = 1.0, uint64_t seed = 0) {
+    std::vector<PoseEssentialResult> out(pairs.size());
+    std::vector<size_t> live;
+    std::vector<int32_t> first{0};
+    std::vector<float> a, b;
+    for (size_t i = 0; i < pairs.size(); ++i) {
+        const FlowPair &p = pairs[i];
+        if (!p.has_points) continue;
+        if (p.points.size() != p.next_points.size()) throw GyroflowCoreError(GyroflowCoreError::Unknown, "estimate_poses_essential: a pair's two point sets have one length");
+        for (const auto &pt : p.points) { a.push_back(pt.first); a.push_back(pt.second); }
+        for (const auto &pt : p.next_points) { b.push_back(pt.first); b.push_back(pt.second); }
+        first.push_back((int32_t)(a.size() / 2));
+        live.push_back(i);
+    }
+    if (live.empty()) return out;
+    if (!ctx) throw GyroflowCoreError(GyroflowCoreError::Unknown, "estimate_poses_essential: no backend context for the pose estimation");
+    const int n = (int)live.size();
+    std::vector<int32_t> octets((size_t)n * (size_t)std::max(cfg.num_iters, 0) * 8 + 1), best((size_t)n * 4);
+    std::vector<float> quats((size_t)n * 4);
+    std::vector<double> rotations((size_t)n * 9), essential((size_t)n * 9);
+    int rc = gfw_pose_draws_k(seed, first.data(), n, cfg.num_iters, 8, octets.data());
+    if (rc == GFW_OK) rc = gfw_pose_essential(ctx, &params, &cfg, first.data(), a.data(), b.data(), n, octets.data(), quats.data(), rotations.data(), essential.data(),
+                                              best.data(), nullptr, nullptr, 0);
+    if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+    for (int k = 0; k < n; ++k) {
+        PoseEssentialResult &r = out[live[(size_t)k]];
+        r.has_rotation = best[(size_t)k * 4 + 3] != 0;
+        std::copy(rotations.begin() + k * 9, rotations.begin() + k * 9 + 9, r.rotation);
+        std::copy(essential.begin() + k * 9, essential.begin() + k * 9 + 9, r.essential);
+        std::copy(quats.begin() + k * 4, quats.begin() + k * 4 + 4, r.quat);
+        const auto rv = scaled_axis(r.rotation);
+        for (int i = 0; i < 3; ++i) r.euler[i] = rv[(size_t)i] * (scaled_fps / every_nth_frame);      // :146
+        r.inliers = best[(size_t)k * 4]; r.round = best[(size_t)k * 4 + 1]; r.front = best[(size_t)k * 4 + 2];
+    }
+    return out;
+}
 // ---- synchronization/optical_flow/opencv_pyrlk.rs:63-119 over gfw_flow_pyrlk: `OFOpenCVPyrLK::optical_flow_to` for ALL frame pairs in one device call.  `frames`:
 // n u8 gray planes back to back (host memory), `pairs` (first frame, second frame); `features`: one list per frame, or empty for the grid points of
 // opencv_dis.rs:62-119 (computed on the device).  One FlowPair per pair, in feature order; has_points only with at least 10 kept points (:107) — what
