@@ -21,11 +21,12 @@
 // accepted corner (itself included) and reduces the 64-bit maximum of the others (a lane's own first, sixteen loads in flight at a time, then one 64-bit LDS atomicMax a lane); the round's best is
 // accepted if its e > t = max(e, 0) * quality, else the pick ends.  At most max_corners rounds of ceil(candidates / 256) steps a lane.
 //
-// NO INDEX OUTSIDE A FRAME CAN BE FORMED: a pixel is fetched only for coordinates in [-1, n] and sides are n >= 3, so one reflection (-1 -> 1, n -> n - 2) lands in
+// NO INDEX OUTSIDE A FRAME CAN BE FORMED: a pixel is fetched only for coordinates in [-1, n] and sides are n >= 3, so one reflection (gfw_image_reflect, gfw_image.h: -1 -> 1, n -> n - 2) lands in
 // [0, n - 1]; the row padding (stride > w) is never read.  Plain C++ under -ffp-contract=off; all stores are ordinary vector stores; control flow around the barriers
 // is workgroup-uniform, around the ballots wave-uniform.
 #include <hip/hip_runtime.h>
 #include "gfw_corners.h"
+#include "gfw_image.h"
 
 #define GFW_CORNERS_PW (GFW_CORNERS_TILE_W + 6)      // pixels: the tile and a halo of 3
 #define GFW_CORNERS_PH (GFW_CORNERS_TILE_H + 6)
@@ -38,10 +39,6 @@
 
 struct GfwCornersD { int16_t x, y; };                // (Dx, Dy), |D| <= 1020
 
-__device__ __forceinline__ int gfw_corners_reflect(int i, int n) {                   // reflect-101: -1 -> 1, n -> n - 2
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
 __device__ __forceinline__ unsigned gfw_corners_bits(float v) { return __builtin_bit_cast(unsigned, v); }
 __device__ __forceinline__ float gfw_corners_float(unsigned v) { return __builtin_bit_cast(float, v); }
 
@@ -64,7 +61,7 @@ __global__ __launch_bounds__(256) void gfw_corners_eig_kernel(const GfwCornersAr
     for (int u = 0; u < GFW_CORNERS_LANE_PIXELS; ++u) {
         const int i = t + 256 * u, r = i / GFW_CORNERS_PW, c = i - r * GFW_CORNERS_PW;
         const int gx = min(max(tx0 - 3 + c, -1), w), gy = min(max(ty0 - 3 + r, -1), h);      // clamped, not tested: a load without a branch, and what lies beyond is never asked
-        px[u] = img[(size_t)gfw_corners_reflect(gy, h) * (size_t)A.stride + (size_t)gfw_corners_reflect(gx, w)];
+        px[u] = img[(size_t)gfw_image_reflect(gy, h) * (size_t)A.stride + (size_t)gfw_image_reflect(gx, w)];
     }
     #pragma unroll
     for (int u = 0; u < GFW_CORNERS_LANE_PIXELS; ++u) {
@@ -93,10 +90,10 @@ __global__ __launch_bounds__(256) void gfw_corners_eig_kernel(const GfwCornersAr
         if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
             int cx[3], sxx = 0, sxy = 0, syy = 0;
             #pragma unroll
-            for (int k = 0; k < 3; ++k) cx[k] = gfw_corners_reflect(gx + k - 1, w) - (tx0 - 2);
+            for (int k = 0; k < 3; ++k) cx[k] = gfw_image_reflect(gx + k - 1, w) - (tx0 - 2);
             #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                const GfwCornersD *row = s_d[gfw_corners_reflect(gy + j - 1, h) - (ty0 - 2)];
+                const GfwCornersD *row = s_d[gfw_image_reflect(gy + j - 1, h) - (ty0 - 2)];
                 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     const GfwCornersD D = row[cx[k]];
@@ -126,7 +123,7 @@ __global__ __launch_bounds__(256) void gfw_corners_eig_kernel(const GfwCornersAr
                           (e >= r0[0]) & (e >= r0[1]) & (e >= r0[2]) & (e >= r1[0]) & (e >= r1[2]) & (e >= r2[0]) & (e >= r2[1]) & (e >= r2[2]);
         key[m] = ((unsigned long long)gfw_corners_bits(e) << 32) | (unsigned long long)(((unsigned)gy << 13) | (unsigned)gx);
         const unsigned long long mask = __ballot(cand);
-        rank[m] = cand ? total + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u)) : -1;
+        rank[m] = cand ? total + gfw_image_ballot_rank(mask) : -1;
         total += (int)__popcll(mask);
     }
     if (best) atomicMax(&s_max, best);
@@ -197,19 +194,9 @@ __global__ __launch_bounds__(256) void gfw_corners_pick_kernel(const GfwCornersA
     if (t == 0) A.counts[frame] = count;
 }
 
-// feat_first from the frames' counts: one workgroup, lane t owns a run of consecutive frames
+// feat_first from the frames' counts: one workgroup (gfw_image_scan)
 __global__ __launch_bounds__(256) void gfw_corners_scan_kernel(const GfwCornersArgs A) {
-    __shared__ int s_sum[256];
-    const int t = (int)(threadIdx.y * 64u + threadIdx.x);
-    const int run = (A.n_frames + 255) / 256, lo = min(t * run, A.n_frames), hi = min(lo + run, A.n_frames);
-    int sum = 0;
-    for (int f = lo; f < hi; ++f) sum += A.counts[f];
-    s_sum[t] = sum;
-    __syncthreads();
-    int before = 0;
-    for (int j = 0; j < t; ++j) before += s_sum[j];
-    for (int f = lo; f < hi; ++f) { A.feat_first[f] = before; before += A.counts[f]; }
-    if (t == 255) A.feat_first[A.n_frames] = before;                                  // lane 255's run is the last (possibly empty) one
+    gfw_image_scan(A.n_frames, A.feat_first, [&A](int f) { return A.counts[f]; });
 }
 
 // The corners of frame blockIdx.x in pick order behind those of the frames before it

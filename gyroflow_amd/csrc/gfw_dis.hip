@@ -4,44 +4,24 @@
 // NOT part of it.  OpenCV's raster-order propagation depends on its thread count and is not reproduced: three synchronous passes, each reading its neighbours from the
 // pass before, so no result depends on the order in which workgroups run.
 //
-// Every sum over a patch's 64 pixels is an INTEGER: gradients are the integer central difference, bilinear samples of the second frame are fixed point (weights of 14
-// bits that sum to 16384, 5 fraction bits kept: 0 .. 8160), the difference d against 32 A has |d| <= 8160, a lane's d d <= 2^26 fits an int32 and a patch's sums fit
-// an int64 with room (64 Sdd <= 2^38); the mean normalisation is formed in integers too (64 Sdd - Sd Sd), and ONE conversion to f32 follows.  The order of an exact
-// sum is free, so the wave reduces with 64-bit LDS atomics and the result equals the statement's to the bit.
+// Every sum over a patch's 64 pixels is an INTEGER: gradients are the integer central difference, bilinear samples of the second frame are fixed point (gfw_image.h's
+// gfw_image_sample: weights of 14 bits that sum to 16384, 5 fraction bits kept: 0 .. 8160), the difference d against 32 A has |d| <= 8160, a lane's d d <= 2^26
+// fits an int32 and a patch's sums fit an int64 with room (64 Sdd <= 2^38); the mean normalisation is formed in integers too (64 Sdd - Sd Sd), and ONE conversion
+// to f32 follows.  The order of an exact sum is free, so the wave reduces with 64-bit LDS atomics and the result equals the statement's to the bit.
 //
 // The inverse search is ONE wave per (patch, pair), a lane per patch pixel: a barrier is a wave barrier.  The template's (A, Ix, Iy) stay in registers over every
 // evaluation of the pass; every lane computes the same f32 update from the same sums, so the trip counts are wave-uniform by construction.
 //
 // NO INDEX OUTSIDE A LEVEL CAN BE FORMED.  A level has sides w, h >= 8 (the host builds no smaller one: min(w, h) >= 8 * 2^coarsest), so nx = (w - 8) / 4 + 1 >= 1 and
-// a patch pixel is x = 4 i + (lane & 7) <= 4 (nx - 1) + 7 <= w - 1.  The gradient reads min(x + 1, w - 1) and max(x - 1, 0).  A sample reads columns
+// a patch pixel is x = 4 i + (lane & 7) <= 4 (nx - 1) + 7 <= w - 1.  The gradient reads min(x + 1, w - 1) and max(x - 1, 0).  A sample reads columns (gfw_image.h)
 // clamp(x + ix, 0, w - 1) and clamp(x + ix + 1, 0, w - 1), ix the integer part of the displacement, itself clamped to +-16384 as a FLOAT before the cast (no cast
 // outside the int range is executed; a displacement is finite because det > 2^24 divides finite sums): |x + ix + 1| < 2^15 and the clamp lands in the level.  The dense
 // field is read at coordinates clamped to [0, n - 1] before the cast, with the neighbour min(i0 + 1, n - 1).  The pyramid reads 2x + 1 <= 2 (w / 2 - 1) + 1 <= w - 1.
 // Rows alike.  Plain C++ under -ffp-contract=off; all stores are ordinary vector stores; control flow around the barriers is workgroup-uniform.
 #include <hip/hip_runtime.h>
 #include "gfw_dis.h"
+#include "gfw_image.h"
 
-// The four 14-bit weights of a position's fraction (a, b): every operation one f32 operation, rintf rounds half to even
-struct GfwDisWeights { int w00, w01, w10, w11; };
-__device__ __forceinline__ GfwDisWeights gfw_dis_weights(float a, float b) {
-    const float na = 1.0f - a, nb = 1.0f - b;
-    GfwDisWeights W;
-    W.w00 = (int)rintf((na * nb) * 16384.0f);
-    W.w01 = (int)rintf((a * nb) * 16384.0f);
-    W.w10 = (int)rintf((na * b) * 16384.0f);
-    W.w11 = 16384 - W.w00 - W.w01 - W.w10;
-    return W;
-}
-__device__ __forceinline__ int gfw_dis_clamp(int i, int n) { return min(max(i, 0), n - 1); }
-// The level `img` at the pixel (x, y) displaced by (ux, uy), edge replicated, 5 fraction bits
-__device__ __forceinline__ int gfw_dis_sample(const uint8_t *img, int w, int h, int stride, int x, int y, float ux, float uy) {
-    const float fx = floorf(ux), fy = floorf(uy);
-    const GfwDisWeights W = gfw_dis_weights(ux - fx, uy - fy);
-    const int ix = (int)fminf(fmaxf(fx, -16384.0f), 16384.0f), iy = (int)fminf(fmaxf(fy, -16384.0f), 16384.0f);
-    const int c0 = gfw_dis_clamp(x + ix, w), c1 = gfw_dis_clamp(x + ix + 1, w);
-    const uint8_t *r0 = img + (size_t)gfw_dis_clamp(y + iy, h) * (size_t)stride, *r1 = img + (size_t)gfw_dis_clamp(y + iy + 1, h) * (size_t)stride;
-    return (W.w00 * (int)r0[c0] + W.w01 * (int)r0[c1] + W.w10 * (int)r1[c0] + W.w11 * (int)r1[c1] + 256) >> 9;
-}
 // The field U [h][w][2] at (cx, cy), coordinates clamped to the level
 __device__ __forceinline__ void gfw_dis_bilinear(const float *U, int w, int h, float cx, float cy, float &vx, float &vy) {
     cx = fminf(fmaxf(cx, 0.0f), (float)(w - 1)); cy = fminf(fmaxf(cy, 0.0f), (float)(h - 1));
@@ -79,7 +59,7 @@ __device__ __forceinline__ void gfw_dis_reduce(unsigned long long (*s_acc)[5], i
 // What a wave holds of its patch, and the evaluation of a value u against the second frame: 64 times the mean-normalised SSD and the right-hand side
 struct GfwDisPatch { const uint8_t *b; int w, h, stride, x, y, a32, ix, iy; long long sx, sy; };
 __device__ __forceinline__ void gfw_dis_evaluate(const GfwDisPatch &P, unsigned long long (*s_acc)[5], int &ring, int lane, float ux, float uy, float &ssd, float &bx, float &by) {
-    const int d = gfw_dis_sample(P.b, P.w, P.h, P.stride, P.x, P.y, ux, uy) - P.a32;
+    const int d = gfw_image_sample(P.b, P.w, P.h, P.stride, P.x, P.y, ux, uy) - P.a32;
     const int part[4] = {d, d * d, P.ix * d, P.iy * d};
     long long S[4];
     gfw_dis_reduce<4>(s_acc, ring, lane, part, S);
@@ -175,7 +155,7 @@ __global__ __launch_bounds__(256) void gfw_dis_dense_kernel(const GfwDisArgs A, 
     for (int j = jlo; j <= jhi; ++j) {
         for (int i = ilo; i <= ihi; ++i) {
             const float ux = u[((size_t)j * nx + i) * 2], uy = u[((size_t)j * nx + i) * 2 + 1];
-            const int d = gfw_dis_sample(lb, w, h, ls, xc, yc, ux, uy) - a32;
+            const int d = gfw_image_sample(lb, w, h, ls, xc, yc, ux, uy) - a32;
             const float wt = 32.0f / (float)max(32, d < 0 ? -d : d);
             sw = sw + wt; sx = sx + (wt * ux); sy = sy + (wt * uy);
         }
@@ -184,19 +164,9 @@ __global__ __launch_bounds__(256) void gfw_dis_dense_kernel(const GfwDisArgs A, 
     o[0] = sx / sw; o[1] = sy / sw;
 }
 
-// out_pair_first from the grid counts of the pairs' first frames: one workgroup, lane t owns a run of consecutive pairs
+// out_pair_first from the grid counts of the pairs' first frames: one workgroup (gfw_image_scan)
 __global__ __launch_bounds__(256) void gfw_dis_scan_kernel(const GfwDisArgs A) {
-    __shared__ int s_sum[256];
-    const int t = (int)(threadIdx.y * 64u + threadIdx.x);
-    const int run = (A.n_pairs + 255) / 256, lo = min(t * run, A.n_pairs), hi = min(lo + run, A.n_pairs);
-    int sum = 0;
-    for (int p = lo; p < hi; ++p) sum += A.grid_counts[A.pair_frames[p * 2]];
-    s_sum[t] = sum;
-    __syncthreads();
-    int before = 0;
-    for (int j = 0; j < t; ++j) before += s_sum[j];
-    for (int p = lo; p < hi; ++p) { A.out_pair_first[p] = before; before += A.grid_counts[A.pair_frames[p * 2]]; }
-    if (t == 255) A.out_pair_first[A.n_pairs] = before;                               // lane 255's run is the last (possibly empty) one
+    gfw_image_scan(A.n_pairs, A.out_pair_first, [&A](int p) { return A.grid_counts[A.pair_frames[p * 2]]; });
 }
 
 // The kept nodes of pair blockIdx.x's first frame through the finest field: every one is returned, in grid order

@@ -3,7 +3,7 @@
 // 30 iterations or eps 0.01, flags 0 and minEigThreshold 1e-4, and its filter of the result (:88-100).  OpenCV's source is not part of the reference tree: the
 // contract is tests/_flowstmt.py, the published pyramidal Lucas-Kanade scheme stated operation by operation.
 //
-// Every window sum is an INTEGER: pixels, Scharr derivatives and bilinear samples are fixed point (weights of 14 bits that sum to 16384), the products of a window
+// Every window sum is an INTEGER: pixels, Scharr derivatives and bilinear samples are fixed point (gfw_image.h's weights of 14 bits that sum to 16384), the products of a window
 // are summed exactly (a lane's seven fit an int32 — 7 * 8160 * 4080 < 2^31 —, the 441 of a window need an int64: 441 * 4080^2 > 2^32), and one conversion to f32
 // follows each reduction.  The order of an exact sum is free, so the wave reduces with 64-bit LDS atomics and the result equals the statement's to the bit.
 //
@@ -15,30 +15,16 @@
 // NO INDEX OUTSIDE A LEVEL CAN BE FORMED.  A level has sides n >= 24 (GFW_FLOW_SIDE_MIN: the host builds no smaller one).  The iteration reads B at columns
 // iv .. iv + 21 (21 window pixels and the bilinear neighbour) and is entered only with -21 <= iv <= n - 1 (tested on the float BEFORE the cast, which is only made
 // for |g| < 2^24), so its indices lie in [-21, n + 20].  The template reads A at iu - 1 .. iu + 22 (the Scharr taps of both bilinear neighbours) with
-// iu = floor(p * 2^-l - 10) for a feature 0 <= p < w, so -10 <= iu <= n - 10 and its indices lie in [-11, n + 12].  gfw_flow_reflect maps i < 0 to -i <= 22 <= n - 1
+// iu = floor(p * 2^-l - 10) for a feature 0 <= p < w, so -10 <= iu <= n - 10 and its indices lie in [-11, n + 12].  gfw_image_reflect (gfw_image.h) maps i < 0 to -i <= 22 <= n - 1
 // and i >= n to 2n - 2 - i >= 2n - 2 - (n + 21) = n - 23 >= 0: one reflection lands inside [0, n - 1] for every index in [-22, n + 21] when n >= 23, and the cut at
 // 24 leaves one to spare.  The pyramid reads 2x - 2 .. 2x + 2 with x <= (n + 1) / 2 - 1: indices in [-2, n + 1], inside by the same map.  Rows alike.
 // Plain C++ under -ffp-contract=off; all stores are ordinary vector stores; control flow around the barriers is workgroup-uniform, around the ballots wave-uniform.
 #include <hip/hip_runtime.h>
 #include "gfw_flow.h"
+#include "gfw_image.h"
 
 #define GFW_FLOW_EPSILON 1.1920928955078125e-7f      // FLT_EPSILON
 
-__device__ __forceinline__ int gfw_flow_reflect(int i, int n) {                      // reflect-101: -1 -> 1, n -> n - 2
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
-// The four 14-bit weights of a position's fraction (a, b): every operation one f32 operation, rintf rounds half to even
-struct GfwFlowWeights { int w00, w01, w10, w11; };
-__device__ __forceinline__ GfwFlowWeights gfw_flow_weights(float a, float b) {
-    const float na = 1.0f - a, nb = 1.0f - b;
-    GfwFlowWeights W;
-    W.w00 = (int)rintf((na * nb) * 16384.0f);
-    W.w01 = (int)rintf((a * nb) * 16384.0f);
-    W.w10 = (int)rintf((na * b) * 16384.0f);
-    W.w11 = 16384 - W.w00 - W.w01 - W.w10;
-    return W;
-}
 __device__ __forceinline__ bool gfw_flow_inside(float x, float y, float w, float h) { return x >= 0.0f && x < w && y >= 0.0f && y < h; }      // false for a NaN
 
 // Level `level` from the level below it, all frames: out(x, y) = (sum k_i k_j in(r(2x + i), r(2y + j)) + 128) >> 8, k = 1 4 6 4 1.  A lane per pixel.
@@ -49,11 +35,11 @@ __global__ __launch_bounds__(256) void gfw_flow_pyramid_kernel(const GfwFlowLeve
     const uint8_t *in = src.base + (size_t)blockIdx.y * (size_t)src.frame_bytes;
     int xs[5];
     #pragma unroll
-    for (int i = 0; i < 5; ++i) xs[i] = gfw_flow_reflect(2 * x + i - 2, src.w);
+    for (int i = 0; i < 5; ++i) xs[i] = gfw_image_reflect(2 * x + i - 2, src.w);
     int acc = 0;
     #pragma unroll
     for (int j = 0; j < 5; ++j) {
-        const uint8_t *row = in + (size_t)gfw_flow_reflect(2 * y + j - 2, src.h) * (size_t)src.stride;
+        const uint8_t *row = in + (size_t)gfw_image_reflect(2 * y + j - 2, src.h) * (size_t)src.stride;
         const int r = (int)row[xs[0]] + 4 * (int)row[xs[1]] + 6 * (int)row[xs[2]] + 4 * (int)row[xs[3]] + (int)row[xs[4]];
         acc += (j == 0 || j == 4 ? 1 : (j == 2 ? 6 : 4)) * r;
     }
@@ -90,7 +76,7 @@ __global__ __launch_bounds__(64) void gfw_flow_grid_kernel(const GfwFlowArgs A) 
         }
         const unsigned long long mask = __ballot(keep);
         if (keep) {
-            const int at = packed + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+            const int at = packed + gfw_image_ballot_rank(mask);
             out[(size_t)at * 2] = (float)i; out[(size_t)at * 2 + 1] = (float)j;
         }
         packed += (int)__popcll(mask);
@@ -154,7 +140,7 @@ __global__ __launch_bounds__(64) void gfw_flow_track_kernel(const GfwFlowArgs A)
         // the template: I with 5 fraction bits, Ix and Iy in the Scharr derivative's own units, at floor(u) with u's weights
         const float fux = floorf(ux), fuy = floorf(uy);
         const int iux = (int)fux, iuy = (int)fuy;                                    // -10 <= iu < 8192
-        const GfwFlowWeights W = gfw_flow_weights(ux - fux, uy - fuy);
+        const GfwImageWeights W = gfw_image_weights(ux - fux, uy - fuy);
         int I[GFW_FLOW_LANE_PIXELS], Ix[GFW_FLOW_LANE_PIXELS], Iy[GFW_FLOW_LANE_PIXELS];
         int part[3] = {0, 0, 0};
         #pragma unroll
@@ -166,9 +152,9 @@ __global__ __launch_bounds__(64) void gfw_flow_track_kernel(const GfwFlowArgs A)
                 int v[4][4];
                 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const uint8_t *row = la + (size_t)gfw_flow_reflect(iuy + wy - 1 + r, lh) * (size_t)ls;
+                    const uint8_t *row = la + (size_t)gfw_image_reflect(iuy + wy - 1 + r, lh) * (size_t)ls;
                     #pragma unroll
-                    for (int c = 0; c < 4; ++c) v[r][c] = (int)row[gfw_flow_reflect(iux + wx - 1 + c, lw)];
+                    for (int c = 0; c < 4; ++c) v[r][c] = (int)row[gfw_image_reflect(iux + wx - 1 + c, lw)];
                 }
                 int dx[2][2], dy[2][2];                                              // the derivatives at (x + c, y + r)
                 #pragma unroll
@@ -206,15 +192,15 @@ __global__ __launch_bounds__(64) void gfw_flow_track_kernel(const GfwFlowArgs A)
             const float fgx = floorf(gx), fgy = floorf(gy);
             if (fgx < -21.0f || fgx >= (float)lw || fgy < -21.0f || fgy >= (float)lh) { if (l == 0) status = 0; break; }
             const int ivx = (int)fgx, ivy = (int)fgy;
-            const GfwFlowWeights V = gfw_flow_weights(gx - fgx, gy - fgy);
+            const GfwImageWeights V = gfw_image_weights(gx - fgx, gy - fgy);
             int pb[2] = {0, 0};
             #pragma unroll
             for (int m = 0; m < GFW_FLOW_LANE_PIXELS; ++m) {
                 const int wk = lane + 64 * m;
                 if (wk < GFW_FLOW_WIN_PIXELS) {
                     const int wy = wk / GFW_FLOW_WIN, wx = wk - wy * GFW_FLOW_WIN;
-                    const uint8_t *r0 = lb + (size_t)gfw_flow_reflect(ivy + wy, lh) * (size_t)ls, *r1 = lb + (size_t)gfw_flow_reflect(ivy + wy + 1, lh) * (size_t)ls;
-                    const int c0 = gfw_flow_reflect(ivx + wx, lw), c1 = gfw_flow_reflect(ivx + wx + 1, lw);
+                    const uint8_t *r0 = lb + (size_t)gfw_image_reflect(ivy + wy, lh) * (size_t)ls, *r1 = lb + (size_t)gfw_image_reflect(ivy + wy + 1, lh) * (size_t)ls;
+                    const int c0 = gfw_image_reflect(ivx + wx, lw), c1 = gfw_image_reflect(ivx + wx + 1, lw);
                     const int J = (V.w00 * (int)r0[c0] + V.w01 * (int)r0[c1] + V.w10 * (int)r1[c0] + V.w11 * (int)r1[c1] + 256) >> 9;
                     const int d = J - I[m];
                     pb[0] += d * Ix[m]; pb[1] += d * Iy[m];
@@ -239,19 +225,9 @@ __global__ __launch_bounds__(64) void gfw_flow_track_kernel(const GfwFlowArgs A)
     }
 }
 
-// out_pair_first from the pairs' kept counts: one workgroup, lane t owns a run of consecutive pairs
+// out_pair_first from the pairs' kept counts: one workgroup (gfw_image_scan)
 __global__ __launch_bounds__(256) void gfw_flow_scan_kernel(const GfwFlowArgs A) {
-    __shared__ int s_sum[256];
-    const int t = (int)(threadIdx.y * 64u + threadIdx.x);
-    const int run = (A.n_pairs + 255) / 256, lo = min(t * run, A.n_pairs), hi = min(lo + run, A.n_pairs);
-    int sum = 0;
-    for (int p = lo; p < hi; ++p) sum += A.kept[p];
-    s_sum[t] = sum;
-    __syncthreads();
-    int before = 0;
-    for (int j = 0; j < t; ++j) before += s_sum[j];
-    for (int p = lo; p < hi; ++p) { A.out_pair_first[p] = before; before += A.kept[p]; }
-    if (t == 255) A.out_pair_first[A.n_pairs] = before;                               // lane 255's run is the last (possibly empty) one
+    gfw_image_scan(A.n_pairs, A.out_pair_first, [&A](int p) { return A.kept[p]; });
 }
 
 // The kept points of pair blockIdx.x in feature order, ranked by ballot
@@ -272,7 +248,7 @@ __global__ __launch_bounds__(64) void gfw_flow_compact_kernel(const GfwFlowArgs 
         }
         const unsigned long long mask = __ballot(keep);
         if (keep) {
-            const size_t o = (size_t)(at + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u))) * 2;
+            const size_t o = (size_t)(at + gfw_image_ballot_rank(mask)) * 2;
             A.points_a[o] = feat[(size_t)k * 2]; A.points_a[o + 1] = feat[(size_t)k * 2 + 1];
             A.points_b[o] = nx; A.points_b[o + 1] = ny;
         }

@@ -4,8 +4,8 @@
 // `/` and sqrtf are correctly rounded, denormals are kept), sums run left to right, the four links of a pixel always in the order right, left, down, up.  A link that
 // does not exist has the weight 0 and the pixel itself as its neighbour, so a border pixel runs the very operations of an inner one.
 //
-// The fixed-point sampler (14-bit weights, 5 fraction bits, edge replicated) is the one of gfw_dis.hip, STATED AGAIN here: gfw_dis.hip is not edited by this unit
-// (its kernels' figures are pinned), so the function could not move into a shared header.
+// The fixed-point sampler (14-bit weights, 5 fraction bits, edge replicated) is gfw_image_sample of gfw_image.h, the one the DIS flow itself samples with; the
+// clamp c below is that header's gfw_image_clamp.
 //
 // A lane per pixel and pair (a lane per pixel of ONE colour in the half-sweep); the pair rides on blockIdx.y.  Within a half-sweep a pixel reads du, dv of its
 // four neighbours, which have the other colour and are not written by this launch, and its own: the result does not depend on the order in which lanes run.
@@ -17,37 +17,27 @@
 // are <= 8192 and pairs <= 65535, a level of the refinement is at most 4096 x 4096: indices are formed in size_t.  No LDS, no scratch, ordinary vector stores.
 #include <hip/hip_runtime.h>
 #include "gfw_varref.h"
-
-__device__ __forceinline__ int gfw_varref_c(int i, int n) { return min(max(i, 0), n - 1); }
-// The level's second image at the pixel (x, y) displaced by (ux, uy): gfw_dis.hip's gfw_dis_sample
-__device__ __forceinline__ int gfw_varref_sample(const uint8_t *img, int w, int h, int stride, int x, int y, float ux, float uy) {
-    const float fx = floorf(ux), fy = floorf(uy), a = ux - fx, b = uy - fy, na = 1.0f - a, nb = 1.0f - b;
-    const int w00 = (int)rintf((na * nb) * 16384.0f), w01 = (int)rintf((a * nb) * 16384.0f), w10 = (int)rintf((na * b) * 16384.0f), w11 = 16384 - w00 - w01 - w10;
-    const int ix = (int)fminf(fmaxf(fx, -16384.0f), 16384.0f), iy = (int)fminf(fmaxf(fy, -16384.0f), 16384.0f);
-    const int c0 = gfw_varref_c(x + ix, w), c1 = gfw_varref_c(x + ix + 1, w);
-    const uint8_t *r0 = img + (size_t)gfw_varref_c(y + iy, h) * (size_t)stride, *r1 = img + (size_t)gfw_varref_c(y + iy + 1, h) * (size_t)stride;
-    return (w00 * (int)r0[c0] + w01 * (int)r0[c1] + w10 * (int)r1[c0] + w11 * (int)r1[c1] + 256) >> 9;
-}
+#include "gfw_image.h"
 
 // What the prepare kernel sees of a pair's level: avg = (I0 + I1w) 0.5 and Iz = I1w - I0 at a pixel INSIDE the level, I1w the second image warped by the field
 struct GfwVarrefImages { const uint8_t *a, *b; const float *U; int w, h, stride; };
 __device__ __forceinline__ void gfw_varref_warped(const GfwVarrefImages &G, int x, int y, float &avg, float &iz) {
     const float *u = G.U + ((size_t)y * (size_t)G.w + (size_t)x) * 2;
     const float i0 = (float)G.a[(size_t)y * (size_t)G.stride + (size_t)x];
-    const float i1 = (float)gfw_varref_sample(G.b, G.w, G.h, G.stride, x, y, u[0], u[1]) * 0.03125f;
+    const float i1 = (float)gfw_image_sample(G.b, G.w, G.h, G.stride, x, y, u[0], u[1]) * 0.03125f;
     avg = (i0 + i1) * 0.5f; iz = i1 - i0;
 }
 // dx and dy of avg and Iz at a pixel inside the level: (a(c(x + 1)) - a(c(x - 1))) 0.5
 __device__ __forceinline__ void gfw_varref_dx(const GfwVarrefImages &G, int x, int y, float &ix, float &izx) {
     float a1, z1, a0, z0;
-    gfw_varref_warped(G, gfw_varref_c(x + 1, G.w), y, a1, z1);
-    gfw_varref_warped(G, gfw_varref_c(x - 1, G.w), y, a0, z0);
+    gfw_varref_warped(G, gfw_image_clamp(x + 1, G.w), y, a1, z1);
+    gfw_varref_warped(G, gfw_image_clamp(x - 1, G.w), y, a0, z0);
     ix = (a1 - a0) * 0.5f; izx = (z1 - z0) * 0.5f;
 }
 __device__ __forceinline__ void gfw_varref_dy(const GfwVarrefImages &G, int x, int y, float &iy, float &izy) {
     float a1, z1, a0, z0;
-    gfw_varref_warped(G, x, gfw_varref_c(y + 1, G.h), a1, z1);
-    gfw_varref_warped(G, x, gfw_varref_c(y - 1, G.h), a0, z0);
+    gfw_varref_warped(G, x, gfw_image_clamp(y + 1, G.h), a1, z1);
+    gfw_varref_warped(G, x, gfw_image_clamp(y - 1, G.h), a0, z0);
     iy = (a1 - a0) * 0.5f; izy = (z1 - z0) * 0.5f;
 }
 
@@ -64,7 +54,7 @@ __global__ __launch_bounds__(256) void gfw_varref_prepare_kernel(const GfwVarref
     gfw_varref_warped(G, x, y, avg, iz);
     gfw_varref_dx(G, x, y, ix, ixz);
     gfw_varref_dy(G, x, y, iy, iyz);
-    const int xp = gfw_varref_c(x + 1, w), xm = gfw_varref_c(x - 1, w), yp = gfw_varref_c(y + 1, h), ym = gfw_varref_c(y - 1, h);
+    const int xp = gfw_image_clamp(x + 1, w), xm = gfw_image_clamp(x - 1, w), yp = gfw_image_clamp(y + 1, h), ym = gfw_image_clamp(y - 1, h);
     gfw_varref_dx(G, xp, y, p, unused); gfw_varref_dx(G, xm, y, m, unused);
     const float ixx = (p - m) * 0.5f;
     gfw_varref_dx(G, x, yp, p, unused); gfw_varref_dx(G, x, ym, m, unused);
@@ -123,8 +113,8 @@ __global__ __launch_bounds__(256) void gfw_varref_coeff_kernel(const GfwVarrefAr
     const float wr = x + 1 < w ? (s + gfw_varref_s(F, x + 1, y)) * 0.5f : 0.0f, wl = x > 0 ? (gfw_varref_s(F, x - 1, y) + s) * 0.5f : 0.0f;
     const float wd = y + 1 < h ? (s + gfw_varref_s(F, x, y + 1)) * 0.5f : 0.0f, wu = y > 0 ? (gfw_varref_s(F, x, y - 1) + s) * 0.5f : 0.0f;
     const float ws = ((wr + wl) + wd) + wu;
-    const float *ur = F.U + ((size_t)y * w + gfw_varref_c(x + 1, w)) * 2, *ul = F.U + ((size_t)y * w + gfw_varref_c(x - 1, w)) * 2;
-    const float *ud = F.U + ((size_t)gfw_varref_c(y + 1, h) * w + x) * 2, *uu = F.U + ((size_t)gfw_varref_c(y - 1, h) * w + x) * 2;
+    const float *ur = F.U + ((size_t)y * w + gfw_image_clamp(x + 1, w)) * 2, *ul = F.U + ((size_t)y * w + gfw_image_clamp(x - 1, w)) * 2;
+    const float *ud = F.U + ((size_t)gfw_image_clamp(y + 1, h) * w + x) * 2, *uu = F.U + ((size_t)gfw_image_clamp(y - 1, h) * w + x) * 2;
     const float u = F.U[(size_t)idx * 2], v = F.U[(size_t)idx * 2 + 1];
     A.plane[GFW_VR_A11][at] = a11 + ws; A.plane[GFW_VR_A12][at] = a12; A.plane[GFW_VR_A22][at] = a22 + ws;
     A.plane[GFW_VR_B1][at] = b1 + ((((wr * (ur[0] - u)) + (wl * (ul[0] - u))) + (wd * (ud[0] - u))) + (wu * (uu[0] - u)));
@@ -140,8 +130,8 @@ __global__ __launch_bounds__(256) void gfw_varref_sor_kernel(const GfwVarrefArgs
     const int y = idx / hw, x = 2 * (idx % hw) + ((y + colour) & 1);
     if (x >= w) return;
     const size_t first = (size_t)pair * (size_t)w * (size_t)h, at = first + (size_t)y * w + x;
-    const size_t r = first + (size_t)y * w + gfw_varref_c(x + 1, w), l = first + (size_t)y * w + gfw_varref_c(x - 1, w);
-    const size_t d = first + (size_t)gfw_varref_c(y + 1, h) * w + x, t = first + (size_t)gfw_varref_c(y - 1, h) * w + x;
+    const size_t r = first + (size_t)y * w + gfw_image_clamp(x + 1, w), l = first + (size_t)y * w + gfw_image_clamp(x - 1, w);
+    const size_t d = first + (size_t)gfw_image_clamp(y + 1, h) * w + x, t = first + (size_t)gfw_image_clamp(y - 1, h) * w + x;
     float *DU = A.plane[GFW_VR_DU], *DV = A.plane[GFW_VR_DV];
     const float wr = A.plane[GFW_VR_WR][at], wl = x > 0 ? A.plane[GFW_VR_WR][l] : 0.0f, wd = A.plane[GFW_VR_WD][at], wu = y > 0 ? A.plane[GFW_VR_WD][t] : 0.0f;
     const float su = (((wr * DU[r]) + (wl * DU[l])) + (wd * DU[d])) + (wu * DU[t]);

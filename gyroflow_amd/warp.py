@@ -108,6 +108,16 @@ def _mesh_arg(mesh, dtype=np.float32):
     return m.ctypes.data, m.size, m
 
 
+def _frames_arg(frames, shape):
+    """u8 gray planes as numpy [n][height][stride], or a device pointer (int) with `shape` = (n, height, stride) -> (pointer or None, on-device flag,
+    (n, height, stride), the array to keep alive)"""
+    if isinstance(frames, (int, np.integer)):
+        return int(frames), 1, tuple(shape), None
+    keep = np.ascontiguousarray(frames, dtype=np.uint8)
+    assert keep.ndim == 3, "frames: [n][height][stride]"
+    return (keep.ctypes.data if keep.size else None), 0, keep.shape, keep
+
+
 def last_backend():
     return _last_backend
 
@@ -551,14 +561,7 @@ class Backend:
         visual search take) — with ``iters`` also iters int32 [raw][4], in the grid mode also grid_points f32 [n][nodes][2] and grid_counts int32 [n] — or, with
         ``out_ptrs`` = (next, status, iters or None, grid_points or None, grid_counts or None, pair_first, points_a, points_b) device pointers (points_a / points_b
         with room for [raw][2]), the number of raw slots: in order on the stream."""
-        if isinstance(frames, (int, np.integer)):
-            n, height, stride = shape
-            fp, on_device, _keep = int(frames), 1, None
-        else:
-            _keep = np.ascontiguousarray(frames, dtype=np.uint8)
-            assert _keep.ndim == 3, "frames: [n][height][stride]"
-            n, height, stride = _keep.shape
-            fp, on_device = (_keep.ctypes.data if _keep.size else None), 0
+        fp, on_device, (n, height, stride), _keep = _frames_arg(frames, shape)
         mode = (1 if features is None else 0) if point_mode is None else int(point_mode)
         cfg = abi.FlowPyrLKCfg(width=int(width), height=int(height), stride=int(stride), point_mode=mode)
         pf = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
@@ -598,14 +601,7 @@ class Backend:
         visual search take) — with ``flow`` also flow f32 [n_pairs][height >> finest_scale][width >> finest_scale][2], the finest level's dense field — or, with
         ``out_ptrs`` = (grid_points or None, grid_counts or None, flow or None, pair_first, points_a, points_b) device pointers (points_a / points_b with room for
         [n_pairs * nodes][2]), the number of those slots: in order on the stream."""
-        if isinstance(frames, (int, np.integer)):
-            n, height, stride = shape
-            fp, on_device, _keep = int(frames), 1, None
-        else:
-            _keep = np.ascontiguousarray(frames, dtype=np.uint8)
-            assert _keep.ndim == 3, "frames: [n][height][stride]"
-            n, height, stride = _keep.shape
-            fp, on_device = (_keep.ctypes.data if _keep.size else None), 0
+        fp, on_device, (n, height, stride), _keep = _frames_arg(frames, shape)
         cfg = abi.FlowDisCfg(width=int(width), height=int(height), stride=int(stride), finest_scale=int(finest_scale))
         pf = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
         p = lambda a: a.ctypes.data if a is not None and a.size else None
@@ -641,14 +637,7 @@ class Backend:
         corners f32 [n][max_corners][2] (kept first, in pick order, then zeros), counts int32 [n] — with ``scores`` also scores f32 [n][max_corners], with ``packed``
         also feat_first int32 [n + 1] and features f32 [kept][2], what flow_pyrlk takes as its features — or, with ``out_ptrs`` = (corners, scores or None, counts,
         feat_first or None, features or None) device pointers (features with room for [n * max_corners][2]), None: in order on the stream."""
-        if isinstance(frames, (int, np.integer)):
-            n, height, stride = shape
-            fp, on_device, _keep = int(frames), 1, None
-        else:
-            _keep = np.ascontiguousarray(frames, dtype=np.uint8)
-            assert _keep.ndim == 3, "frames: [n][height][stride]"
-            n, height, stride = _keep.shape
-            fp, on_device = (_keep.ctypes.data if _keep.size else None), 0
+        fp, on_device, (n, height, stride), _keep = _frames_arg(frames, shape)
         cfg = abi.CornersCfg(width=int(width), height=int(height), stride=int(stride), max_corners=int(max_corners), quality=float(quality), min_distance=float(min_distance),
                              max_workspace_mb=int(max_workspace_mb))
         args = (self.ctx, C.byref(cfg), fp, on_device, int(n))

@@ -56,10 +56,12 @@ def guarded(data, at_end):
     return arr
 
 
-def kernel_source(top="gfw_frame.hip", n_asm=13):
-    """`top` + the project headers it includes as one text (gen_jit_source.expand, without its typedef prelude: the host has <stdint.h>), asm -> emu_*()."""
+def kernel_source(top="gfw_frame.hip", n_asm=13, seen=None):
+    """`top` + the project headers it includes as one text (gen_jit_source.expand, without its typedef prelude: the host has <stdint.h>), asm -> emu_*().
+    `seen`: the `#pragma once` headers already expanded into the translation unit this text joins (a set, added to): units that share a header pass one set through
+    their calls, so that the header lands in the text once."""
     out = []
-    G.expand(os.path.join(G.CSRC, top), set(), out)
+    G.expand(os.path.join(G.CSRC, top), set() if seen is None else seen, out)
     src = "".join(out)
 
     def fix(m):
@@ -85,14 +87,15 @@ def _host_headers(text, seen):
     return out
 
 
-def build(defs, header, top="gfw_frame.hip", n_asm=13, driver="emu_driver.inc", extra_flags=("-DGFW_JIT=1", "-DGFW_BAKE=1"), opt="-O1"):
+def build(defs, header, top="gfw_frame.hip", n_asm=13, driver="emu_driver.inc", extra_flags=("-DGFW_JIT=1", "-DGFW_BAKE=1"), opt="-O1", seen=None):
     """-> path of the host library for these template arguments (+ bake header) (cached under build/emu/ by content: the kernel source, the files under
-    tests/emu/, and the host-only headers of the product that the drivers include — the entry points' own packers)."""
+    tests/emu/, and the host-only headers of the product that the drivers include — the entry points' own packers).  `seen`: kernel_source's, where `header`
+    holds other units' sources."""
     if not CXX.endswith("clang++"):
         import pytest
         pytest.skip("the host interpreter is built with the ROCm clang++ (half-precision and vector extensions of the kernel headers); not found")
     os.makedirs(OUT, exist_ok=True)
-    text = ('#include "emu_prelude.h"\n' + header + "\n" + kernel_source(top, n_asm) + '\n#include "%s"\n' % driver)
+    text = ('#include "emu_prelude.h"\n' + header + "\n" + kernel_source(top, n_asm, seen) + '\n#include "%s"\n' % driver)
     flags = ["-std=c++17", opt, "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wno-everything", "-I" + EMU] + list(extra_flags) + \
             ["-D%s=%s" % kv for kv in sorted(defs.items())]
     emu = "".join(open(os.path.join(EMU, f)).read() for f in sorted(os.listdir(EMU)))

@@ -15,7 +15,8 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        L = C.CDLL(_emu.build({}, _emu.kernel_source("gfw_flow.hip", 0), top="gfw_dis.hip", n_asm=0, driver="emu_dis_driver.inc", extra_flags=()))
+        seen = set()                                      # gfw_image.h is included by both units: once in the text
+        L = C.CDLL(_emu.build({}, _emu.kernel_source("gfw_flow.hip", 0, seen), top="gfw_dis.hip", n_asm=0, driver="emu_dis_driver.inc", extra_flags=(), seen=seen))
         vp, i32 = C.c_void_p, C.c_int
         L.gfw_emu_dis.argtypes = [i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, C.c_char_p, C.c_size_t]
         _lib = L

@@ -16,8 +16,9 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        header = _emu.kernel_source("gfw_flow.hip", 0) + "\n" + _emu.kernel_source("gfw_dis.hip", 0)
-        L = C.CDLL(_emu.build({}, header, top="gfw_varref.hip", n_asm=0, driver="emu_varref_driver.inc", extra_flags=()))
+        seen = set()                                      # gfw_image.h is included by all three units: once in the text
+        header = _emu.kernel_source("gfw_flow.hip", 0, seen) + "\n" + _emu.kernel_source("gfw_dis.hip", 0, seen)
+        L = C.CDLL(_emu.build({}, header, top="gfw_varref.hip", n_asm=0, driver="emu_varref_driver.inc", extra_flags=(), seen=seen))
         vp, i32 = C.c_void_p, C.c_int
         L.gfw_emu_varref.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, C.c_char_p, C.c_size_t]
         L.gfw_emu_dis.argtypes = [i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, C.c_char_p, C.c_size_t]

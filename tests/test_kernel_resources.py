@@ -4,22 +4,17 @@ The fused kernel's speed depends on how many workgroups a CU admits (profiles/r0
 compiler change that pushes the hot instantiations past a register step, or into scratch, must fail here and not show up as an
 unexplained slowdown on the GPU box."""
 import os
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import kernel_resources as KR          # noqa: E402
-
-LIB = os.path.join(ROOT, "gyroflow_amd", "libgfwarp.so")
+from _kres import KR, LIB, load
 
 
 @pytest.fixture(scope="module")
 def kernels():
     if not os.path.exists(LIB):
         pytest.skip("libgfwarp.so not built")
-    ks = {k[".name"]: k for k in KR.report(LIB)}
+    ks = load()
     assert len(ks) > 100, "code objects of libgfwarp.so not found"
     return ks
 

@@ -3,16 +3,11 @@ clip's (DH == 2: the fetch per line of the lane's two) and the per-frame flavour
 0-byte private segment, at most 64 VGPRs (eight waves per SIMD; the ahead-of-time budget of tests/test_kernel_resources.py is 80) and the scalar registers of eight
 workgroups per CU — as the same builds do with the switch off."""
 import ctypes as C
-import os
-import sys
 
 import pytest
 
 from gyroflow_amd import abi, synthetic as S
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import kernel_resources as KR  # noqa: E402
+from _kres import KR
 
 
 def compile_(lib, defs, header, out):

@@ -11,10 +11,7 @@ import sys
 import pytest
 
 from gyroflow_amd import abi, synthetic as S
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import kernel_resources as KR  # noqa: E402
+from _kres import KR, ROOT
 
 SCAN = os.path.join(ROOT, "tools", "scan_trans_hazard.py")
 W, H = 3840, 2160

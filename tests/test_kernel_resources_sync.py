@@ -3,30 +3,16 @@
 A (candidate, pair) of the cost stage is ONE wave: how many of them a CU holds at once is what hides the f64 slerp's latency, so the wave's registers are pinned at
 what the build gives, none of the three kernels may spill, and the cost kernel's LDS is the call's largest pair (asked for at launch, up to 16 KB) plus a fixed
 part that stays small."""
-import os
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import kernel_resources as KR          # noqa: E402
-
-LIB = os.path.join(ROOT, "gyroflow_amd", "libgfwarp.so")
+from _kres import KR, load, one
 
 
 @pytest.fixture(scope="module")
 def kernels():
-    assert os.path.exists(LIB), "libgfwarp.so not built"
-    ks = {k[".name"]: k for k in KR.report(LIB) if "gfw_sync_" in k[".name"]}
+    ks = {n: k for n, k in load().items() if "gfw_sync_" in n}
     assert len(ks) == 4, sorted(ks)                  # the lens stage for the fisheye and the generic model, the cost stage, the reduce stage
     return ks
-
-
-def one(kernels, tag):
-    hits = [k for n, k in kernels.items() if tag in n]
-    assert len(hits) == 1, (tag, len(hits))
-    return hits[0]
 
 
 def test_no_scratch(kernels):
