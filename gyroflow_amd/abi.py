@@ -134,6 +134,19 @@ class PoseEssentialCfg(C.Structure):
         super().__init__(*a, **kw)
 
 
+class SyncRsCfg(C.Structure):
+    """``gfw_sync_rs_cfg``: what every range of an rs-sync offset search shares (the defaults: the solver's as tests/_rssyncstmt.py states it)."""
+    _fields_ = [("video_width", C.c_int32), ("video_height", C.c_int32), ("flow_width", C.c_int32), ("flow_height", C.c_int32),
+                ("rounds", C.c_int32), ("refine", C.c_int32), ("hypotheses", C.c_int32), ("refits", C.c_int32), ("jacobi_sweeps", C.c_int32),
+                ("reserved", C.c_int32 * 3), ("frame_readout_time_ms", C.c_double), ("step_s", C.c_double), ("loss_scale", C.c_double),
+                ("camera_matrix", C.c_double * 9)]
+
+    def __init__(self, *a, **kw):
+        for k, v in (("rounds", 4), ("refine", 1), ("hypotheses", 16), ("refits", 3), ("jacobi_sweeps", 5), ("step_s", 3.0 / 1000.0), ("loss_scale", 1000.0)):
+            kw.setdefault(k, v)
+        super().__init__(*a, **kw)
+
+
 class FlowPyrLKCfg(C.Structure):
     """``gfw_flow_pyrlk_cfg``: what every frame of a pyramidal Lucas-Kanade optical-flow call shares."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("point_mode", C.c_int32), ("reserved", C.c_int32)]
@@ -173,6 +186,9 @@ SYNC_FINE_CANDIDATES = 200       # the second stage's candidates
 SYNC_PAIR_POINTS_MAX = 4096
 SYNC_GYRO_RANGES_MAX, SYNC_GYRO_EST_MAX, SYNC_GYRO_SAMPLES_MAX, SYNC_GYRO_CANDIDATES_MAX = 65535, 65536, 1 << 22, 2000000      # gfw_sync_gyro_*: per call / per range
 SYNC_GYRO_RING_SLOTS = 2         # staging slots of gfw_sync_gyro_*: calls an asynchronous context takes before one waits for an earlier copy
+SYNC_RS_PAIR_POINTS_MAX, SYNC_RS_PAIRS_MAX, SYNC_RS_RANGES_MAX, SYNC_RS_TRACK_MAX, SYNC_RS_CANDIDATES_MAX, SYNC_RS_ROUNDS_MAX = 4096, 65535, 65535, 1 << 24, 1 << 20, 8      # gfw_sync_rs_*
+SYNC_RS_LATER = 17               # candidates of every round of gfw_sync_rs_search behind the first
+SYNC_RS_RING_SLOTS = 2           # staging slots of gfw_sync_rs_*
 SYNC_OPTIM_FFT_MIN, SYNC_OPTIM_FFT_MAX, SYNC_OPTIM_SAMPLES_MAX, SYNC_OPTIM_TARGET_MAX, SYNC_OPTIM_TRIM_MAX = 16, 8192, 1 << 24, 65535, 1024      # gfw_sync_optim_*
 SYNC_OPTIM_RING_SLOTS = 2        # staging slots of gfw_sync_optim_*
 FILTER_NOT_APPLIED = 1           # gfw_lowpass_gyro: the reference's from_params would fail; the data is untouched
@@ -267,6 +283,9 @@ def bind(lib):
     lib.gfw_pose_almeida.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(PoseAlmeidaCfg), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_pose_almeida.restype = i32
     lib.gfw_pose_draws.argtypes = [C.c_uint64, vp, i32, i32, i32, vp, vp, vp]; lib.gfw_pose_draws.restype = i32
     lib.gfw_pose_essential.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(PoseEssentialCfg), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_pose_essential.restype = i32
+    lib.gfw_sync_rs_costs.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(SyncRsCfg), vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32]; lib.gfw_sync_rs_costs.restype = i32
+    lib.gfw_sync_rs_search.argtypes = [vp, C.POINTER(KernelParams), C.POINTER(SyncRsCfg), vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, C.c_double, C.c_double, vp, vp, vp, i32]
+    lib.gfw_sync_rs_search.restype = i32
     lib.gfw_pose_draws_k.argtypes = [C.c_uint64, vp, i32, i32, i32, vp]; lib.gfw_pose_draws_k.restype = i32
     lib.gfw_flow_pyrlk.argtypes = [vp, C.POINTER(FlowPyrLKCfg), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_flow_pyrlk.restype = i32
     lib.gfw_flow_dis.argtypes = [vp, C.POINTER(FlowDisCfg), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32]; lib.gfw_flow_dis.restype = i32
@@ -301,7 +320,7 @@ EXPORTS = ["gfw_abi_version", "gfw_list_devices", "gfw_set_device", "gfw_get_inf
            "gfw_build_matrices_batch_stab", "gfw_zoom_fovs_stab", "gfw_sync_visual_costs", "gfw_sync_visual_search",
            "gfw_lowpass_gyro", "gfw_sync_gyro_costs", "gfw_sync_gyro_search",
            "gfw_optim_tables", "gfw_optim_resample", "gfw_sync_optim_rank", "gfw_sync_optim_points",
-           "gfw_pose_almeida", "gfw_pose_draws", "gfw_pose_essential", "gfw_pose_draws_k", "gfw_flow_pyrlk", "gfw_corners_shi_tomasi", "gfw_flow_dis", "gfw_flow_dis_refined"]
+           "gfw_pose_almeida", "gfw_pose_draws", "gfw_pose_essential", "gfw_pose_draws_k", "gfw_sync_rs_costs", "gfw_sync_rs_search", "gfw_flow_pyrlk", "gfw_corners_shi_tomasi", "gfw_flow_dis", "gfw_flow_dis_refined"]
 
 
 def load_library(path=None):

@@ -28,6 +28,7 @@
 #include "gfw_sync_optim.h"
 #include "gfw_pose.h"
 #include "gfw_pose_essential.h"
+#include "gfw_sync_rs.h"
 #include "gfw_flow.h"
 #include "gfw_corners.h"
 #include "gfw_dis.h"
@@ -39,6 +40,7 @@
 #include "gfw_sync_optim_host.h"
 #include "gfw_pose_host.h"
 #include "gfw_pose_essential_host.h"
+#include "gfw_sync_rs_host.h"
 #include "gfw_flow_host.h"
 #include "gfw_corners_host.h"
 #include "gfw_dis_host.h"
@@ -134,6 +136,9 @@ struct gfw_ctx {
     // gfw_pose_almeida and gfw_pose_essential: pair firsts, points and draws staged the same way (work space: the visual search's)
     static constexpr int kPoseSlots = 2;
     StagingRing<kPoseSlots> pose_ring;
+    // gfw_sync_rs_*: ranges, pairs, points, the quaternion track and candidates staged the same way (work space: the visual search's)
+    static constexpr int kRsSlots = 2;
+    StagingRing<kRsSlots> rs_ring;
     // gfw_flow_pyrlk: pairs, features and host frames staged the same way (work space: the visual search's)
     static constexpr int kFlowSlots = 2;
     StagingRing<kFlowSlots> flow_ring;
@@ -1029,6 +1034,7 @@ int gfw_undistort_clip_lens(gfw_ctx *c, int n_frames, int nplanes, const gfw_buf
 #include "gfw_api_sync_optim.inc"
 #include "gfw_api_pose.inc"
 #include "gfw_api_pose_essential.inc"
+#include "gfw_api_sync_rs.inc"
 #include "gfw_api_flow.inc"
 #include "gfw_api_corners.inc"
 #include "gfw_api_dis.inc"

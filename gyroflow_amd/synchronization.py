@@ -10,7 +10,7 @@ range is ONE device call, ``Backend.sync_visual_search`` (gfw_sync_visual_search
 The 90 %-of-range acceptance rule (:137) and the range's middle timestamp are applied here.
 
 Not covered: clips with per-frame time offsets, stabiliser data or lens meshes, keyframed lens data or video rotation inside a range,
-suppress_rotation; rs_sync itself.  (The optical flow that produces the matched points: ``optical_flow_pyrlk`` below.)
+suppress_rotation.  (rs_sync: ``find_offsets_rssync`` below.  The optical flow that produces the matched points: ``optical_flow_pyrlk`` below.)
 
     offsets = synchronization.find_offsets_essential(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params, backend)
     initial_offset, search_size = synchronization.initial_offset_fast(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges, sync_params, backend)
@@ -50,6 +50,17 @@ is not covered.
 
 ``OFOpenCVPyrLK::detect_features`` (optical_flow/opencv_pyrlk.rs:25-42): the Shi-Tomasi corners of ALL frames in one device call,
 ``Backend.corners_shi_tomasi`` (gfw_corners_shi_tomasi) — the ``features`` of ``optical_flow_pyrlk``.
+
+    offsets = synchronization.find_offsets_rssync(compute_params, ranges, matched_points, sync_params, backend, track)
+    name, cost = synchronization.guess_orientation({name: track}, compute_params, ranges, matched_points, sync_params, backend)
+    offsets = synchronization.find_offsets(offset_method, compute_params, ranges, sync_params, backend, ...)
+
+``rs_sync::find_offsets`` (find_offset/rs_sync.rs, offset method 2, the reference's default): ALL ranges in one device call, ``Backend.sync_rs_search``
+(gfw_sync_rs_search) — rolling-shutter aware per point, and tolerant of a camera that moved.  The adapter is mirrored here: ``calc_initial_fast`` through
+``initial_offset_fast``, ``collect_points``' range cut, ranges under 2 pairs skipped, the readout rules (:74-81), the sign and unit conventions, the
+90 %-of-radius rule (:178) and the middle timestamp.  The solver, the ``rs-sync`` crate, is not in the reference tree and is NOT reproduced: what runs is the
+search tests/_rssyncstmt.py states.  ``guess_orientation`` is ``guess_orient`` (:190-222) over tracks the caller has already transformed (``apply_transforms``
+for the 48 orientations is not covered).  ``find_offsets`` dispatches on the offset method as synchronization/mod.rs:383-388 does.
 
     optim = synchronization.OptimSync.new(raw_imu)
     points_ms, rank, ratio = optim.run(target_sync_points, trim_ranges_s, backend)
@@ -197,6 +208,100 @@ def initial_offset_fast(estimated_gyro, raw_imu, duration_ms, scaled_fps, ranges
         if offsets:
             return median_offset(o for _, o, _ in offsets), 3000.0
     return sync_params.initial_offset, sync_params.search_size
+
+
+def rs_readout_time_ms(compute_params):
+    """rs_sync.rs:74-80: the frame readout time the solver gets, ms (0 -> half a frame; a global shutter -> 0.01)"""
+    cp = compute_params
+    t = float(getattr(cp, "frame_readout_time", 0.0))
+    if t == 0.0:
+        t = 1000.0 / cp.scaled_fps / 2.0
+    lens = cp.lens
+    if (lens.get("global_shutter") if isinstance(lens, dict) else getattr(lens, "global_shutter", False)):
+        t = 0.01
+    return t
+
+
+def rs_inputs(compute_params, flow_size, **solver):
+    """What gfw_sync_rs_* take for these parameters: (KernelParams, abi.SyncRsCfg); ``solver``: SyncRsCfg fields other than the defaults."""
+    kp, almeida = pose_inputs(compute_params, flow_size)
+    cfg = abi.SyncRsCfg(video_width=almeida.video_width, video_height=almeida.video_height, flow_width=almeida.flow_width, flow_height=almeida.flow_height,
+                        frame_readout_time_ms=rs_readout_time_ms(compute_params), **solver)
+    for i in range(9):
+        cfg.camera_matrix[i] = almeida.camera_matrix[i]
+    return kp, cfg
+
+
+def rs_collect_points(ranges, matched_points):
+    """``collect_points`` (rs_sync.rs:224-241) and the walk of :107-149 -> [(sync point (from_ts, to_ts), [(ts_a, ts_b, points_a, points_b)])] for the ranges
+    of at least 2 pairs.  ``matched_points``: {ts_us: (next_ts_us, points [n][2], next points [n][2])} as ``find_offsets_visual`` takes it."""
+    out = []
+    keys = sorted(matched_points)
+    for from_ts, to_ts in ranges:
+        pairs = [(ts,) + tuple(matched_points[ts]) for ts in keys if from_ts <= ts < to_ts] if to_ts > from_ts else []
+        if len(pairs) < 2:                                                                               # :108
+            continue
+        assert all(len(a) == len(b) for _, _, a, b in pairs)                                             # :128
+        out.append(((pairs[0][0], pairs[-1][1]), pairs))
+    return out
+
+
+def find_offsets_rssync(compute_params, ranges, matched_points, sync_params, backend, track, calc_initial_fast=False, estimated_gyro=None, raw_imu=(),
+                        duration_ms=0.0, flow_size=None, **solver):
+    """``find_offsets`` (rs_sync.rs:17-49, :153-188) -> [(timestamp, offset, cost)]: one ``Backend.sync_rs_search`` call for all ranges that reach the search.
+    ``track``: (ts_us int64 [n], wxyz f64 [n][4]), the gyro's quaternions (:159).  With ``calc_initial_fast`` the search starts from ``initial_offset_fast``
+    of ``estimated_gyro`` / ``raw_imu`` / ``duration_ms``."""
+    cp = compute_params
+    initial_offset, search_size = sync_params.initial_offset, sync_params.search_size
+    if calc_initial_fast:
+        initial_offset, search_size = initial_offset_fast(estimated_gyro, raw_imu, duration_ms, cp.scaled_fps, ranges, sync_params, backend)
+    live = rs_collect_points(ranges, matched_points)
+    if not live:
+        return []
+    kp, cfg = rs_inputs(cp, flow_size or (cp.width, cp.height), **solver)
+    presync_radius, initial_delay = search_size, -initial_offset                                         # :165-166
+    results = backend.sync_rs_search(kp, cfg, [pairs for _, pairs in live], track[0], track[1], initial_delay / 1000.0, presync_radius / 1000.0)
+    frame_readout_time = cfg.frame_readout_time_ms / 1000.0                                              # :81
+    out = []
+    for ((from_ts, to_ts), _), r in zip(live, results):
+        if not r.found:
+            continue
+        offset = r.value * 1000.0
+        if abs(offset - initial_delay) < presync_radius * 0.9:                                           # :178
+            out.append((float(from_ts + to_ts) / 2.0 / 1000.0, -offset - (frame_readout_time * 1000.0 / 2.0), r.cost))
+    return out
+
+
+def guess_orientation(tracks, compute_params, ranges, matched_points, sync_params, backend, flow_size=None, **solver):
+    """``guess_orient`` (rs_sync.rs:190-222) over ``tracks``: {name: (ts_us, wxyz)} in the caller's order, each already transformed to its orientation —
+    per track one round-0 search of every sync point (``pre_sync``), the picks' costs summed; `if a.1 < b.1 { a } else { b }`: of equal sums the LATER name
+    wins.  -> (name, total cost), or None without tracks."""
+    cp = compute_params
+    live = rs_collect_points(ranges, matched_points)
+    solver = dict(solver, rounds=1, refine=0)
+    kp, cfg = rs_inputs(cp, flow_size or (cp.width, cp.height), **solver)
+    best = None
+    for name, (ts_us, wxyz) in tracks.items():
+        total = 0.0
+        if live:
+            for r in backend.sync_rs_search(kp, cfg, [pairs for _, pairs in live], ts_us, wxyz, -sync_params.initial_offset / 1000.0, sync_params.search_size / 1000.0):
+                total += r.coarse_cost if r.found else 0.0                                               # unwrap_or((0.0, 0.0))
+        best = (name, total) if best is None or not (best[1] < total) else best
+    return best
+
+
+def find_offsets(offset_method, compute_params, ranges, sync_params, backend, matched_points=None, track=None, estimated_gyro=None, raw_imu=(), duration_ms=0.0, **kw):
+    """``PoseEstimator::find_offsets`` (synchronization/mod.rs:382-389): 0 -> ``find_offsets_essential``, 1 -> ``find_offsets_visual``, 2 ->
+    ``find_offsets_rssync``; an unknown method finds nothing."""
+    method = int(offset_method)
+    if method == 0:
+        return find_offsets_essential(estimated_gyro, raw_imu, duration_ms, compute_params.scaled_fps, ranges, sync_params, backend)
+    if method == 1:
+        return find_offsets_visual(compute_params, ranges, matched_points, sync_params, backend)
+    if method == 2:
+        return find_offsets_rssync(compute_params, ranges, matched_points, sync_params, backend, track, estimated_gyro=estimated_gyro, raw_imu=raw_imu,
+                                   duration_ms=duration_ms, **kw)
+    return []
 
 
 def scaled_axis(rot):

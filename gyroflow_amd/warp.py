@@ -542,6 +542,63 @@ class Backend:
         return (quats, rot, ess, best, ri, rf) if rounds else (quats, rot, ess, best)
 
     @staticmethod
+    def _sync_rs_ranges(ranges):
+        """[[(ts_a_us, ts_b_us, points_a [n][2], points_b [n][2])]] -> (range_first, pair_ts, pair_first, points_a, points_b) as gfw_sync_rs_* take them"""
+        rf = np.zeros(len(ranges) + 1, dtype=np.int32)
+        if ranges:
+            rf[1:] = np.cumsum([len(r) for r in ranges])
+        ts, first, pa, pb = Backend._sync_pairs([p for r in ranges for p in r])
+        return rf, ts, first, pa, pb
+
+    def sync_rs_costs(self, params, cfg, ranges, track_ts_us, track_wxyz, candidates, out_ptr=None):
+        """The rs-sync range costs (find_offset/rs_sync.rs; the solver as tests/_rssyncstmt.py states it) of caller-given candidate delays for every range in one
+        device call (gfw_sync_rs_costs).
+
+        ``params``: the KernelParams `undistort_points` builds; ``cfg``: abi.SyncRsCfg; ``ranges``: one list of (ts_a_us, ts_b_us, points_a [n][2], points_b
+        [n][2]) optical-flow pairs per range; ``track_ts_us`` int64 [n] strictly ascending, ``track_wxyz`` f64 [n][4]: the quaternion track; ``candidates``: one
+        float64 array of delays (seconds) per range.  Returns one float64 cost array per range — or, with ``out_ptr`` (a device pointer to as many doubles as
+        there are candidates, range after range), None: in order on the stream."""
+        rf, ts, first, pa, pb = self._sync_rs_ranges(ranges)
+        tt, tq = np.ascontiguousarray(track_ts_us, dtype=np.int64).reshape(-1), np.ascontiguousarray(track_wxyz, dtype=np.float64).reshape(-1, 4)
+        assert len(tt) == len(tq), "one quaternion per track timestamp"
+        cands = [np.asarray(c, dtype=np.float64).reshape(-1) for c in candidates]
+        assert len(cands) == len(ranges)
+        cf = np.zeros(len(ranges) + 1, dtype=np.int32)
+        if cands:
+            cf[1:] = np.cumsum([len(c) for c in cands])
+        cand = np.ascontiguousarray(np.concatenate(cands)) if cands else np.zeros(0)
+        args = (self.ctx, C.byref(params), C.byref(cfg), rf.ctypes.data, len(ranges), ts.ctypes.data, first.ctypes.data, pa.ctypes.data, pb.ctypes.data, len(ts),
+                tt.ctypes.data, tq.ctypes.data, len(tt), cf.ctypes.data, cand.ctypes.data, len(cand))
+        if out_ptr is not None:
+            self._check(self.lib.gfw_sync_rs_costs(*args, out_ptr, 1))
+            return None
+        costs = np.zeros(max(len(cand), 1), dtype=np.float64)
+        self._check(self.lib.gfw_sync_rs_costs(*args, costs.ctypes.data, 0))
+        return [costs[cf[r]:cf[r + 1]].copy() for r in range(len(ranges))]
+
+    def sync_rs_search(self, params, cfg, ranges, track_ts_us, track_wxyz, initial_delay_s=0.0, radius_s=3.0, rounds=False, out_ptrs=None):
+        """``full_sync`` of rs_sync.rs:164-175 for every range in one device call (gfw_sync_rs_search); arguments as for sync_rs_costs, delays in seconds.
+        Returns [abi.SyncResult] (coarse_value / coarse_cost: the round-0 pick; value / cost: the final delay and its pick's cost) — with ``rounds`` also every
+        round's candidates and range costs, f64 [n_ranges][sync_rs_candidates(..)] each — or, with ``out_ptrs`` = (results, round_candidates or None,
+        round_costs or None) device pointers, None: in order on the stream."""
+        rf, ts, first, pa, pb = self._sync_rs_ranges(ranges)
+        tt, tq = np.ascontiguousarray(track_ts_us, dtype=np.int64).reshape(-1), np.ascontiguousarray(track_wxyz, dtype=np.float64).reshape(-1, 4)
+        assert len(tt) == len(tq), "one quaternion per track timestamp"
+        n = len(ranges)
+        args = (self.ctx, C.byref(params), C.byref(cfg), rf.ctypes.data, n, ts.ctypes.data, first.ctypes.data, pa.ctypes.data, pb.ctypes.data, len(ts),
+                tt.ctypes.data, tq.ctypes.data, len(tt), float(initial_delay_s), float(radius_s))
+        if out_ptrs is not None:
+            self._check(self.lib.gfw_sync_rs_search(*args, *out_ptrs, 1))
+            return None
+        res = (abi.SyncResult * max(n, 1))()
+        total = sync_rs_candidates(radius_s, cfg.step_s, cfg.rounds) if rounds else 0
+        cand, cost = np.zeros((n, total)), np.zeros((n, total))
+        q = lambda a: a.ctypes.data if a.size else None
+        self._check(self.lib.gfw_sync_rs_search(*args, C.cast(res, C.c_void_p), q(cand) if rounds else None, q(cost) if rounds else None, 0))
+        out = [res[i] for i in range(n)]
+        return (out, cand, cost) if rounds else out
+
+    @staticmethod
     def _flow_features(features):
         """one [n][2] array per frame -> (feat_first int32 [n_frames + 1], features f32 [total][2]) as gfw_flow_pyrlk takes them (kept alive by the caller)"""
         lists = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, 2) for f in features]
@@ -707,6 +764,11 @@ def sync_gyro_coarse_count(search_size_ms):
     """candidates of the gyro-match search's first stage: `search_size as usize * 2` (essential_matrix.rs:55) — the cast comes before the multiplication"""
     v = float(search_size_ms)
     return 0 if v != v or v <= 0.0 else int(min(v, 2.0 ** 62)) * 2
+
+
+def sync_rs_candidates(radius_s, step_s, rounds):
+    """candidates of a range over all rounds of gfw_sync_rs_search: 2 floor(radius / step) + 1, then 17 a round"""
+    return 2 * int(np.floor(float(radius_s) / float(step_s))) + 1 + (int(rounds) - 1) * abi.SYNC_RS_LATER
 
 
 def optim_window_count(n_samples, sample_rate):

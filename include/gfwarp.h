@@ -615,7 +615,7 @@ int   gfw_zoom_smooth(const double *fov_minimal, int n, double adaptive_zoom_win
  * HAS_IBIS_DATA, HAS_MESH_DATA or HAS_FPD_DATA, a non-zero reserved slot, no tracks.
  * NOT covered: clips with per_frame_time_offsets, camera_stab_data or mesh_correction (in the reference the frame index, and so
  * the mesh, follows `timestamp - offs`); lens data or a video rotation keyframed inside a range; suppress_rotation; AKAZE
- * (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below; its corner detection: gfw_corners_shi_tomasi below), rs_sync.  (essential_matrix: gfw_sync_gyro_search below; optimsync: gfw_sync_optim_points below; pose estimation by the
+ * (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below; its corner detection: gfw_corners_shi_tomasi below).  (essential_matrix: gfw_sync_gyro_search below; rs_sync: gfw_sync_rs_search below; optimsync: gfw_sync_optim_points below; pose estimation by the
  * Almeida method: gfw_pose_almeida below; by an essential matrix, pose methods 0 and 2: gfw_pose_essential below.) */
 typedef struct gfw_sync_search {
     int32_t width, height;            /* params.width / height: the bounds test (`w as f32`) and the readout divisor */
@@ -667,7 +667,7 @@ int   gfw_sync_visual_search(gfw_ctx *ctx, const gfw_kernel_params *params, cons
  * GFW_ERR_INVALID_ARGUMENT, the range named in gfw_last_error(), outputs untouched: null arguments for non-zero counts, negative
  * counts, a negative or descending first array, a slice outside its array, a non-finite initial_offset or search_size, a negative
  * search_size, counts over the limits above.  Non-finite sample values are not rejected; the pick among NaN costs is unspecified.
- * NOT covered: AKAZE (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below; its corner detection: gfw_corners_shi_tomasi below; the DIS dense flow: gfw_flow_dis below), rs_sync itself, pose estimation by a homography (method 3; the Almeida method: gfw_pose_almeida below; methods 0 and 2, an essential matrix: gfw_pose_essential below; the series of
+ * NOT covered: AKAZE (pyramidal Lucas-Kanade optical flow: gfw_flow_pyrlk below; its corner detection: gfw_corners_shi_tomasi below; the DIS dense flow: gfw_flow_dis below), the rs-sync crate's own solver (what runs for rs_sync: gfw_sync_rs_search below), pose estimation by a homography (method 3; the Almeida method: gfw_pose_almeida below; methods 0 and 2, an essential matrix: gfw_pose_essential below; the series of
  * estimated samples is made of their rotations by gyroflow::estimated_gyro / gyroflow_amd.synchronization.estimated_gyro).
  *
  * gfw_lowpass_gyro: Lowpass::filter_gyro_forward_backward (filtering.rs:46-74) of xyz [n][3] f64 in place, on the host (no context):
@@ -830,6 +830,76 @@ int   gfw_pose_essential(gfw_ctx *ctx, const gfw_kernel_params *params, const gf
                          const int32_t *octets, float *quats, double *rotations, double *essential, int32_t *best,
                          int32_t *round_inliers, double *round_fits, int out_on_device);
 int   gfw_pose_draws_k(uint64_t seed, const int32_t *pair_first, int n_pairs, int num_iters, int k, int32_t *tuples);
+
+/* ---- synchronization: the rs-sync offset search of all ranges of a clip in one device call ----
+ * find_offset/rs_sync.rs: offset method 2, the reference's default (synchronization/mod.rs:383) — the one search that is rolling-shutter
+ * aware per point and tolerates a camera that moved.  The adapter is mirrored: what goes in (:115-146, per-point unit bearings and
+ * per-point timestamps), what comes out (a delay in seconds and a cost) and, in the mirrors, the acceptance rule (:178).  Its solver,
+ * the `rs-sync` crate, is NOT part of the reference tree and is NOT REPRODUCED — neither its cost, nor its round schedule, nor its
+ * final gradient refinement.  What runs is stated operation by operation in tests/_rssyncstmt.py; the device equals that statement
+ * to the bit, and the statement is held to finding planted delays.  Nothing reference-produced is compared.  All arithmetic behind
+ * the lens inverse is f64 (+ - * / sqrt); every sum has one fixed order.
+ *   prepare    `undistort_points_for_optical_flow` of both frames' points as gfw_pose_essential's prepare stage ((-1e6, -1e6) where
+ *              the lens has no inverse); the f32 (x, y) give the f64 unit bearing of (x, y, 1); the point's time is
+ *              pair_ts / 1e6 + (frame_readout_time_ms / 1000) * (y_raw / flow_height), y_raw the flow pixel's own y (:132-133)
+ *   track      track_ts_us [n_track] strictly ascending, track_wxyz [n_track][4] f64 (w, x, y, z): an INPUT of the call, as
+ *              rs_sync.rs:159 passes `gyro.quaternions` and guess_orient passes other tracks — not the context's tracks.  At time t:
+ *              t clamped to the track's ends, bisection, normalised linear interpolation with the shorter-arc flip, one sqrt (not
+ *              slerp: no acos / sin).  World bearing: R(q(t)) diag(1, -1, -1) p, the rotation by pi about X of set_quats (:248-251)
+ *   pair cost  at delay d: m_i = ra_i x rb_i with both bearings in the world at t_i + d (a static scene: every m_i perpendicular to
+ *              the camera's translation).  Direction hypothesis 0: the eigenvector of the smallest eigenvalue of sum m_i m_i^T
+ *              (cyclic Jacobi, jacobi_sweeps sweeps, the first of equal eigenvalues); hypotheses h = 1 .. hypotheses: m_i x m_j
+ *              normalised, i = 7h mod n, j = (13h + 5) mod n, skipped where its squared length is not > 0.  Score
+ *              sum rho(loss_scale * m_i.t), rho(x) = x^2 / (1 + x^2); the FIRST minimal hypothesis wins; `refits` refits with
+ *              w_i = 1 / (1 + x_i^2)^2; the cost is the score at the last t.  A pair of 0 points costs 0; of 1 point: hypothesis 0 only.
+ *              Sums over a pair's points: lane l of 64 folds points l, l + 64, .. from 0.0, then v = v + v[l ^ off], off = 32 .. 1
+ *   range      range r owns pairs range_first[r] .. range_first[r + 1] - 1 (range_first[0] = 0, range_first[n_ranges] = n_pairs);
+ *              pair p owns points pair_first[p] .. of points_a / points_b [..][2] f32 and pair_ts_us [n_pairs][2] (both frames' times).
+ *              A range's cost is the sum of its pairs' costs in pair order
+ * gfw_sync_rs_costs: the range costs of caller-given candidate delays (seconds): range r owns candidates cand_first[r] ..
+ * cand_first[r + 1] - 1 (cand_first[0] = 0) and the same entries of costs — the building block of pre_sync and the orientation guess.
+ * gfw_sync_rs_search: `full_sync(initial_delay, from, to, step, radius, rounds)` (:164-175) for every range without a host round
+ * trip, 1 + 2 * rounds launches: round 0 has 2h + 1 candidates initial_delay_s + (i - h) * step_s, h = floor(radius_s / step_s); every
+ * later round 17 candidates pick + (i - 8) * (step / 8), the step divided by 8 again; of equal costs the FIRST candidate wins; with
+ * `refine`, behind the last round the vertex of the parabola through the pick and its two neighbours where both exist and the second
+ * difference is positive.
+ *   results    [n_ranges] gfw_sync_result: found = 0 for a range without pairs (everything else 0); n_coarse = 2h + 1; the round-0
+ *              pick and its cost; value / cost: the final delay (seconds) and the last pick's cost
+ *   round_candidates / round_costs   NULL or [n_ranges][2h + 1 + 17 (rounds - 1)] f64: every round's candidates and range costs
+ *   limits     at most 4096 points in a pair, 65535 pairs, 65535 ranges, 2^24 track samples, 2^20 candidates a range and round,
+ *              rounds 1 .. 8, hypotheses 0 .. 64, refits 0 .. 16, jacobi_sweeps 1 .. 32, 2 GiB staged in all
+ * The sign and unit conventions (initial_delay = -initial_offset, offset = -delay * 1000 - readout / 2), the readout rules (:74-81),
+ * the range cut and the 90 % rule are the caller's (gyroflow::find_offsets_rssync, gyroflow_amd.synchronization).  Everything travels
+ * in one pinned staging copy; both calls run in order on the context's stream; outputs are host or device memory (out_on_device);
+ * with device outputs an asynchronous context returns without waiting.  n_ranges = 0 succeeds and writes nothing.  Rejected with
+ * GFW_ERR_INVALID_ARGUMENT, the range or pair named in gfw_last_error(), outputs untouched: null arguments for non-zero counts,
+ * negative counts, a first array that does not start at 0, descends or does not end at its count, more than 4096 points a pair,
+ * counts over the limits, a track under 2 samples or not strictly ascending, a non-finite or non-positive step, a negative or
+ * non-finite radius, a non-finite initial delay, rounds outside 1 .. 8, params->flags with HAS_IBIS_DATA, HAS_MESH_DATA or
+ * HAS_FPD_DATA, f / c that are not the f32 cast of camera_matrix, sizes under 1, a non-zero reserved slot.  Non-finite point or
+ * quaternion values are not rejected; the pick among NaN costs is unspecified.
+ * NOT covered: the crate's own numerics; AKAZE; `apply_transforms` for the 48 orientations of guess_orient (the caller transforms the
+ * tracks); per_frame_time_offsets; lens data keyframed inside a call. */
+typedef struct gfw_sync_rs_cfg {
+    int32_t video_width, video_height;     /* compute_params.width / height */
+    int32_t flow_width, flow_height;       /* FrameResult::frame_size */
+    int32_t rounds, refine;                /* 4, 1 */
+    int32_t hypotheses, refits;            /* 16, 3 */
+    int32_t jacobi_sweeps;                 /* 5: every 3 x 3 matrix of the test plants is at its floor after 4 */
+    int32_t reserved[3];                   /* 0 */
+    double  frame_readout_time_ms;         /* after the rules of rs_sync.rs:74-80 */
+    double  step_s;                        /* 3.0 / 1000.0 */
+    double  loss_scale;                    /* 1000: about 1 px at f = 1000 px */
+    double  camera_matrix[9];              /* get_lens_data_at_timestamp(..).0, row-major */
+} gfw_sync_rs_cfg;
+int   gfw_sync_rs_costs(gfw_ctx *ctx, const gfw_kernel_params *params, const gfw_sync_rs_cfg *cfg, const int32_t *range_first, int n_ranges,
+                        const int64_t *pair_ts_us, const int32_t *pair_first, const float *points_a, const float *points_b, int n_pairs,
+                        const int64_t *track_ts_us, const double *track_wxyz, int n_track,
+                        const int32_t *cand_first, const double *candidates, int n_candidates, double *costs, int out_on_device);
+int   gfw_sync_rs_search(gfw_ctx *ctx, const gfw_kernel_params *params, const gfw_sync_rs_cfg *cfg, const int32_t *range_first, int n_ranges,
+                         const int64_t *pair_ts_us, const int32_t *pair_first, const float *points_a, const float *points_b, int n_pairs,
+                         const int64_t *track_ts_us, const double *track_wxyz, int n_track, double initial_delay_s, double radius_s,
+                         gfw_sync_result *results, double *round_candidates, double *round_costs, int out_on_device);
 
 /* ---- synchronization: pyramidal Lucas-Kanade optical flow of a clip's frame pairs in one device call ----
  * optical_flow/opencv_pyrlk.rs:63-119 (`OFOpenCVPyrLK::optical_flow_to`, the reference's method 1): the given features of each pair's

@@ -18,6 +18,7 @@
 //   gyroflow::calculate_fovs               src/core/zooming/mod.rs:35-70    (the adaptive-zoom fov series: one device call + host smoothing)
 //   gyroflow::find_offsets_visual          src/core/synchronization/find_offset/visual_features.rs:10-147
 //   gyroflow::find_offsets_essential       src/core/synchronization/find_offset/essential_matrix.rs:13-91   (+ initial_offset_fast: rs_sync.rs:26-45)
+//   gyroflow::find_offsets_rssync          src/core/synchronization/find_offset/rs_sync.rs                  (the adapter; the rs-sync crate's solver is not reproduced)
 //   gyroflow::OptimSync                    src/core/synchronization/optimsync.rs   (where in a clip to sync: new on the host, run in one device call)
 //
 // `FrameTransform::at_timestamp` itself (quaternions -> per-row matrices) is input here: the caller provides
@@ -466,6 +467,62 @@ inline SyncParams initial_offset_fast(gfw_ctx *ctx, const std::map<int64_t, Time
     sync_params.initial_offset = median_offset(v);
     sync_params.search_size = 3000.0;
     return sync_params;
+}
+
+// ---- synchronization/find_offset/rs_sync.rs `find_offsets` over gfw_sync_rs_search: the rs-sync offset of every range (offset method 2, the reference's default), ALL
+// ranges in one device call.  The adapter is mirrored here — collect_points' range cut (:224-241), ranges under 2 pairs skipped (:108), the sign and unit
+// conventions (:164-166, :176-179), the 90 %-of-radius rule (:178) and the middle timestamp (:180); the solver, the rs-sync crate, is not in the reference tree and is
+// NOT reproduced (include/gfwarp.h says what runs instead).  `cfg.frame_readout_time_ms`: rs_readout_time_ms of the clip's; `matched` as for find_offsets_visual,
+// ascending by timestamp; `track_*`: the gyro's quaternions (:159), timestamps strictly ascending, (w, x, y, z).  With calc_initial_fast the caller passes what
+// initial_offset_fast returns as `sync_params`.  -> (timestamp, offset, cost) per range that is searched and accepted.
+inline double rs_readout_time_ms(double frame_readout_time_ms, double scaled_fps, bool global_shutter) {      // :74-80
+    double t = frame_readout_time_ms;
+    if (t == 0.0) t = 1000.0 / scaled_fps / 2.0;
+    if (global_shutter) t = 0.01;
+    return t;
+}
+inline std::vector<std::tuple<double, double, double>> find_offsets_rssync(gfw_ctx *ctx, const KernelParams &params, const gfw_sync_rs_cfg &cfg,
+                                                                           const std::vector<std::pair<int64_t, int64_t>> &ranges, const std::vector<MatchedPoints> &matched,
+                                                                           const SyncParams &sync_params, const std::vector<int64_t> &track_timestamps_us,
+                                                                           const std::vector<double> &track_wxyz) {
+    std::vector<std::tuple<double, double, double>> offsets;
+    if (track_wxyz.size() != track_timestamps_us.size() * 4) throw GyroflowCoreError(GyroflowCoreError::Unknown, "find_offsets_rssync: one (w, x, y, z) per track timestamp");
+    std::vector<std::pair<int64_t, int64_t>> sync_points;
+    std::vector<int32_t> range_first{0}, first{0};
+    std::vector<int64_t> ts;
+    std::vector<float> a, b;
+    for (const auto &range : ranges) {
+        std::vector<const MatchedPoints *> in;
+        if (range.second > range.first)
+            for (const MatchedPoints &m : matched) if (m.timestamp_us >= range.first && m.timestamp_us < range.second) in.push_back(&m);
+        if (in.size() < 2) continue;                                                                // :108
+        for (const MatchedPoints *m : in) {
+            if (m->points.size() != m->next_points.size()) throw GyroflowCoreError(GyroflowCoreError::Unknown, "find_offsets_rssync: a pair's two point sets have one length");      // :128
+            ts.push_back(m->timestamp_us); ts.push_back(m->next_timestamp_us);
+            for (const auto &pt : m->points) { a.push_back(pt.first); a.push_back(pt.second); }
+            for (const auto &pt : m->next_points) { b.push_back(pt.first); b.push_back(pt.second); }
+            first.push_back((int32_t)(a.size() / 2));
+        }
+        range_first.push_back((int32_t)(ts.size() / 2));
+        sync_points.emplace_back(in.front()->timestamp_us, in.back()->next_timestamp_us);           // :116-119
+    }
+    if (sync_points.empty()) return offsets;
+    if (!ctx) throw GyroflowCoreError(GyroflowCoreError::Unknown, "find_offsets_rssync: no backend context for the rs-sync search");
+    const double presync_radius = sync_params.search_size, initial_delay = -sync_params.initial_offset;      // :165-166
+    std::vector<gfw_sync_result> results(sync_points.size());
+    std::memset(results.data(), 0, sizeof(gfw_sync_result) * results.size());
+    const int rc = gfw_sync_rs_search(ctx, &params, &cfg, range_first.data(), (int)sync_points.size(), ts.data(), first.data(), a.data(), b.data(), (int)(ts.size() / 2),
+                                      track_timestamps_us.data(), track_wxyz.data(), (int)track_timestamps_us.size(), initial_delay / 1000.0, presync_radius / 1000.0,
+                                      results.data(), nullptr, nullptr, 0);
+    if (rc != GFW_OK) throw GyroflowCoreError(GyroflowCoreError::from_code(rc), gfw_last_error());
+    const double frame_readout_time = cfg.frame_readout_time_ms / 1000.0;                           // :81
+    for (size_t k = 0; k < sync_points.size(); ++k) {
+        if (!results[k].found) continue;
+        const double offset = results[k].value * 1000.0, d = offset - initial_delay;
+        if ((d < 0.0 ? -d : d) < presync_radius * 0.9)                                              // :178
+            offsets.emplace_back((double)(sync_points[k].first + sync_points[k].second) / 2.0 / 1000.0, -offset - (frame_readout_time * 1000.0 / 2.0), results[k].cost);
+    }
+    return offsets;
 }
 
 // ---- synchronization/estimate_pose/almeida.rs over gfw_pose_almeida: `PoseEstimator::process_detected_frames` (synchronization/mod.rs:110-167) with the Almeida
