@@ -1,4 +1,4 @@
-// gfw_api_pose.inc — part of gfw_api.hip (textually included): gfw_pose_almeida and gfw_pose_draws.  What they check and stage is gfw_pose_host.h's.
+// gfw_api_pose.inc — part of gfw_api.hip (textually included): gfw_pose_almeida and gfw_pose_draws.  What they check and stage is gfw_pose_host.h's; the pair set's check and staging and the lens gate, shared with the other point-pair calls, gfw_pairs_host.h's.
 
 // Almeida pose estimation of every frame pair of a call (estimate_pose/almeida.rs:23-238; gfw_pose.hip).  See include/gfwarp.h for the argument contract.
 extern "C" int gfw_pose_almeida(gfw_ctx *c, const gfw_kernel_params *p, const gfw_pose_almeida_cfg *cfg, const int32_t *pair_first, const float *points_a,
@@ -6,18 +6,10 @@ extern "C" int gfw_pose_almeida(gfw_ctx *c, const gfw_kernel_params *p, const gf
                                 float *quats, double *rotations, int32_t *best, int32_t *round_inliers, float *round_fits, int out_on_device) {
     if (!c || !p || !cfg) { set_error("bad pose arguments (null context / params / configuration)"); return GFW_ERR_INVALID_ARGUMENT; }
     if (cfg->reserved) { set_error("bad pose configuration: the reserved slot must be 0"); return GFW_ERR_INVALID_ARGUMENT; }
-    if (cfg->video_width < 1 || cfg->video_height < 1 || cfg->flow_width < 1 || cfg->flow_height < 1 || !(cfg->inlier_angle_deg >= 0.0f)) {
-        set_error("bad pose configuration: video %d x %d, optical flow %d x %d, inlier angle %g", cfg->video_width, cfg->video_height, cfg->flow_width, cfg->flow_height, (double)cfg->inlier_angle_deg);
-        return GFW_ERR_INVALID_ARGUMENT; }
-    if (p->flags & (256 | 512 | 1024)) {                                     // HAS_IBIS_DATA | HAS_MESH_DATA | HAS_FPD_DATA
-        set_error("pose estimation does not cover per-frame IBIS/OIS shifts, lens meshes or focal-plane distortion data (flags 0x%x)", p->flags);
-        return GFW_ERR_INVALID_ARGUMENT; }
-    const double *K = cfg->camera_matrix;
-    if (p->f[0] != (float)K[0] || p->f[1] != (float)K[4] || p->c[0] != (float)K[2] || p->c[1] != (float)K[5]) {
-        set_error("the kernel parameters' f (%g, %g) / c (%g, %g) are not the f32 cast of camera_matrix (%g, %g) / (%g, %g)", (double)p->f[0], (double)p->f[1], (double)p->c[0], (double)p->c[1], K[0], K[4], K[2], K[5]);
-        return GFW_ERR_INVALID_ARGUMENT; }
-    const GfwPoseInputs I = {pair_first, points_a, points_b, n_pairs, triples, sample_first, samples, cfg->num_iters, cfg->num_samples};
     char why[256];
+    if (!gfw_pairs_lens_check(*p, cfg->camera_matrix, {cfg->video_width, cfg->video_height, cfg->flow_width, cfg->flow_height}, "pose", "pose estimation", cfg->inlier_angle_deg >= 0.0f,
+                              why, sizeof(why), "inlier angle %g", (double)cfg->inlier_angle_deg)) { set_error("%s", why); return GFW_ERR_INVALID_ARGUMENT; }
+    const GfwPoseInputs I = {pair_first, points_a, points_b, n_pairs, triples, sample_first, samples, cfg->num_iters, cfg->num_samples};
     if (!gfw_pose_check(I, why, sizeof(why))) { set_error("%s", why); return GFW_ERR_INVALID_ARGUMENT; }
     if (n_pairs == 0) return GFW_OK;
     if (!quats || !rotations || !best) { set_error("bad pose arguments (a null quats / rotations / best array)"); return GFW_ERR_INVALID_ARGUMENT; }
@@ -30,7 +22,7 @@ extern "C" int gfw_pose_almeida(gfw_ctx *c, const gfw_kernel_params *p, const gf
     StagedBlock B;
     HIP_TRY(c->pose_ring.acquire(S.total, c->stream, &B.slot), GFW_ERR_HIP);
     gfw_pose_fill(S, I, B.h(), B.d(), A);
-    gfw_pose_constants(cfg->video_width, cfg->video_height, cfg->flow_width, cfg->flow_height, cfg->inlier_angle_deg, K, A);
+    gfw_pose_constants(cfg->video_width, cfg->video_height, cfg->flow_width, cfg->flow_height, cfg->inlier_angle_deg, cfg->camera_matrix, A);
     HIP_TRY(B.upload(S.total, c->stream), GFW_ERR_HIP);
     const size_t rounds = (size_t)n_pairs * (size_t)cfg->num_iters, total = (size_t)A.total;
     CallOutputs O(c->d_out, out_on_device);

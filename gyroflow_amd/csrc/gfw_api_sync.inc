@@ -1,5 +1,5 @@
-// gfw_api_sync.inc — part of gfw_api.hip (textually included): the sync searches' entry points — gfw_sync_visual_*, gfw_lowpass_gyro, gfw_sync_gyro_*.  What they stage
-// is gfw_sync_host.h's and gfw_sync_gyro_host.h's.
+// gfw_api_sync.inc — part of gfw_api.hip (textually included): the sync searches' entry points — gfw_sync_visual_*, gfw_lowpass_gyro, gfw_sync_gyro_*.  What the visual
+// search checks and what they stage is gfw_sync_host.h's and gfw_sync_gyro_host.h's.
 
 // The visual-features sync search (find_offset/visual_features.rs:10-147; gfw_sync.hip).  See include/gfwarp.h for the argument contract.  One body serves both entries:
 // `search_mode` < 0 = gfw_sync_visual_costs (the caller's candidates), 0 / 1 = gfw_sync_visual_search (the coarse candidates are made here, the fine ones on the device).
@@ -7,40 +7,12 @@ struct SyncOut { double *costs; float *mapped; gfw_sync_result *result; double *
 static int sync_visual_impl(gfw_ctx *c, const gfw_kernel_params *p, const gfw_sync_search *search, const int64_t *pair_ts_us, const int32_t *pair_first,
                             const float *points_a, const float *points_b, int n_pairs, const double *candidates, int n_candidates, int search_mode,
                             double initial_offset_ms, double search_size_ms, double frame_readout_time_ms, double scaled_fps, const SyncOut &out, int out_on_device) {
-    if (!c || !p || !search || n_pairs < 0 || n_candidates < 0) { set_error("bad sync arguments (null context / params / search, or a negative count)"); return GFW_ERR_INVALID_ARGUMENT; }
-    if (search->reserved[0] || search->reserved[1]) { set_error("bad sync search: reserved slots must be 0"); return GFW_ERR_INVALID_ARGUMENT; }
-    if (search->width < 1 || search->height < 1 || search->horizontal_readout < 0 || search->horizontal_readout > 1 || search->use_sync_offsets < 0 || search->use_sync_offsets > 1) {
-        set_error("bad sync search: %d x %d, horizontal_readout %d, use_sync_offsets %d", search->width, search->height, search->horizontal_readout, search->use_sync_offsets);
-        return GFW_ERR_INVALID_ARGUMENT; }
-    if ((unsigned long long)search->width * (unsigned long long)search->width + (unsigned long long)search->height * (unsigned long long)search->height >= (1ull << 32)) {
-        set_error("bad sync search: %d x %d — width^2 + height^2 must stay below 2^32 (a squared distance is folded as 32 bits)", search->width, search->height);
-        return GFW_ERR_INVALID_ARGUMENT; }
-    if (p->flags & (256 | 512 | 1024)) {                                     // HAS_IBIS_DATA | HAS_MESH_DATA | HAS_FPD_DATA
-        set_error("the sync search does not cover per-frame IBIS/OIS shifts, lens meshes or focal-plane distortion data (flags 0x%x)", p->flags);
-        return GFW_ERR_INVALID_ARGUMENT; }
-    if (n_pairs > GFW_SYNC_PAIRS_MAX) { set_error("%d pairs: at most %d in a call", n_pairs, GFW_SYNC_PAIRS_MAX); return GFW_ERR_INVALID_ARGUMENT; }
-    if (n_pairs && (!pair_ts_us || !pair_first)) { set_error("bad sync arguments (pairs without pair_ts_us / pair_first)"); return GFW_ERR_INVALID_ARGUMENT; }
-    int total = 0, max_pair = 0;
-    if (n_pairs) {
-        if (pair_first[0] < 0) { set_error("pair 0: pair_first %d is negative", pair_first[0]); return GFW_ERR_INVALID_ARGUMENT; }
-        for (int i = 0; i < n_pairs; ++i) {
-            if (pair_first[i + 1] < pair_first[i]) { set_error("pair %d: pair_first descends (%d after %d)", i, pair_first[i + 1], pair_first[i]); return GFW_ERR_INVALID_ARGUMENT; }
-            const int n = pair_first[i + 1] - pair_first[i];
-            if (n > GFW_SYNC_PAIR_MAX) { set_error("pair %d: %d points, at most %d", i, n, GFW_SYNC_PAIR_MAX); return GFW_ERR_INVALID_ARGUMENT; }
-            if (n > max_pair) max_pair = n;
-        }
-        total = pair_first[n_pairs];
-        if (total && (!points_a || !points_b)) { set_error("bad sync arguments (%d points without points_a / points_b)", total); return GFW_ERR_INVALID_ARGUMENT; }
-    }
-    int n_coarse = n_candidates;
-    if (search_mode < 0) {
-        if (n_candidates && (!candidates || !out.costs)) { set_error("bad sync arguments (candidates without their array / costs)"); return GFW_ERR_INVALID_ARGUMENT; }
-    } else {
-        if (search_mode > 1 || !out.result) { set_error("bad sync arguments (mode %d, or a null result)", search_mode); return GFW_ERR_INVALID_ARGUMENT; }
-        const double steps = gfw_sync_coarse_steps(search_mode, search_size_ms, scaled_fps);
-        if (steps > 1000000.0) { set_error("a search of %g candidates (search_size_ms %g, scaled_fps %g)", steps * (search_mode ? 2.0 : 1.0), search_size_ms, scaled_fps); return GFW_ERR_INVALID_ARGUMENT; }
-        n_coarse = (int)steps * (search_mode ? 2 : 1);
-    }
+    if (!c || !p) { set_error("bad sync arguments (null context / params / search, or a negative count)"); return GFW_ERR_INVALID_ARGUMENT; }
+    const GfwPairSet P = {pair_ts_us, pair_first, points_a, points_b, n_pairs};
+    int total = 0, max_pair = 0, n_coarse = 0;
+    char why[256];
+    if (!gfw_sync_check(search, p->flags, P, candidates, n_candidates, search_mode, search_size_ms, scaled_fps, search_mode < 0 ? (const void *)out.costs : (const void *)out.result, total, max_pair, n_coarse, why, sizeof(why))) {
+        set_error("%s", why); return GFW_ERR_INVALID_ARGUMENT; }
     if (c->tracks.org_n < 1 && c->tracks.sm_n < 1) { set_error("no quaternion tracks set (gfw_set_quaternion_tracks)"); return GFW_ERR_INVALID_ARGUMENT; }
     if (search_mode < 0 && n_candidates == 0) return GFW_OK;
     API_TRY(enter_device(c));

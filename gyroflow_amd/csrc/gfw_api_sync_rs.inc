@@ -1,4 +1,4 @@
-// gfw_api_sync_rs.inc — part of gfw_api.hip (textually included): gfw_sync_rs_costs and gfw_sync_rs_search.  What they check and stage is gfw_sync_rs_host.h's.
+// gfw_api_sync_rs.inc — part of gfw_api.hip (textually included): gfw_sync_rs_costs and gfw_sync_rs_search.  What they check and stage is gfw_sync_rs_host.h's; the pair set's check and staging and the lens gate, shared with the other point-pair calls, gfw_pairs_host.h's.
 
 // The rs-sync offset search (find_offset/rs_sync.rs, offset method 2; gfw_sync_rs.hip).  See include/gfwarp.h for the argument contract.  One body serves both
 // entries: `S.search` false = gfw_sync_rs_costs (the caller's candidates: prepare, cost, sum), true = gfw_sync_rs_search (prepare, then cost and pick per round).
@@ -6,19 +6,11 @@ static int sync_rs_impl(gfw_ctx *c, const gfw_kernel_params *p, const gfw_sync_r
                         gfw_sync_result *results, double *round_candidates, double *round_costs, int out_on_device) {
     if (!c || !p || !cfg) { set_error("bad rs-sync arguments (null context / params / configuration)"); return GFW_ERR_INVALID_ARGUMENT; }
     if (cfg->reserved[0] || cfg->reserved[1] || cfg->reserved[2]) { set_error("bad rs-sync configuration: the reserved slots must be 0"); return GFW_ERR_INVALID_ARGUMENT; }
-    if (cfg->video_width < 1 || cfg->video_height < 1 || cfg->flow_width < 1 || cfg->flow_height < 1 || !std::isfinite(cfg->frame_readout_time_ms)) {
-        set_error("bad rs-sync configuration: video %d x %d, optical flow %d x %d, frame_readout_time_ms %g", cfg->video_width, cfg->video_height, cfg->flow_width, cfg->flow_height, cfg->frame_readout_time_ms);
-        return GFW_ERR_INVALID_ARGUMENT; }
-    if (p->flags & (256 | 512 | 1024)) {                                     // HAS_IBIS_DATA | HAS_MESH_DATA | HAS_FPD_DATA
-        set_error("the rs-sync search does not cover per-frame IBIS/OIS shifts, lens meshes or focal-plane distortion data (flags 0x%x)", p->flags);
-        return GFW_ERR_INVALID_ARGUMENT; }
-    const double *K = cfg->camera_matrix;
-    if (p->f[0] != (float)K[0] || p->f[1] != (float)K[4] || p->c[0] != (float)K[2] || p->c[1] != (float)K[5]) {
-        set_error("the kernel parameters' f (%g, %g) / c (%g, %g) are not the f32 cast of camera_matrix (%g, %g) / (%g, %g)", (double)p->f[0], (double)p->f[1], (double)p->c[0], (double)p->c[1], K[0], K[4], K[2], K[5]);
-        return GFW_ERR_INVALID_ARGUMENT; }
+    char why[256];
+    if (!gfw_pairs_lens_check(*p, cfg->camera_matrix, {cfg->video_width, cfg->video_height, cfg->flow_width, cfg->flow_height}, "rs-sync", "the rs-sync search", std::isfinite(cfg->frame_readout_time_ms),
+                              why, sizeof(why), "frame_readout_time_ms %g", cfg->frame_readout_time_ms)) { set_error("%s", why); return GFW_ERR_INVALID_ARGUMENT; }
     S.step_s = cfg->step_s; S.loss_scale = cfg->loss_scale; S.rounds = cfg->rounds; S.refine = cfg->refine;
     S.hypotheses = cfg->hypotheses; S.refits = cfg->refits; S.sweeps = cfg->jacobi_sweeps;
-    char why[256];
     if (!gfw_rs_check(I, S, why, sizeof(why))) { set_error("%s", why); return GFW_ERR_INVALID_ARGUMENT; }
     if (I.n_ranges == 0) return GFW_OK;
     if (S.search ? !results : (I.n_candidates && !costs)) { set_error("bad rs-sync arguments (a null %s array)", S.search ? "result" : "cost"); return GFW_ERR_INVALID_ARGUMENT; }
@@ -76,18 +68,14 @@ extern "C" int gfw_sync_rs_costs(gfw_ctx *c, const gfw_kernel_params *p, const g
                                  const int32_t *pair_first, const float *points_a, const float *points_b, int n_pairs, const int64_t *track_ts_us, const double *track_wxyz,
                                  int n_track, const int32_t *cand_first, const double *candidates, int n_candidates, double *costs, int out_on_device) {
     const GfwRsInputs I = {range_first, n_ranges, pair_ts_us, pair_first, points_a, points_b, n_pairs, track_ts_us, track_wxyz, n_track, cand_first, candidates, n_candidates};
-    GfwRsSettings S;
-    memset(&S, 0, sizeof(S));
-    S.search = false;
-    return sync_rs_impl(c, p, cfg, I, S, costs, nullptr, nullptr, nullptr, out_on_device);
+    return sync_rs_impl(c, p, cfg, I, GfwRsSettings{}, costs, nullptr, nullptr, nullptr, out_on_device);
 }
 extern "C" int gfw_sync_rs_search(gfw_ctx *c, const gfw_kernel_params *p, const gfw_sync_rs_cfg *cfg, const int32_t *range_first, int n_ranges, const int64_t *pair_ts_us,
                                   const int32_t *pair_first, const float *points_a, const float *points_b, int n_pairs, const int64_t *track_ts_us, const double *track_wxyz,
                                   int n_track, double initial_delay_s, double radius_s, gfw_sync_result *results, double *round_candidates, double *round_costs,
                                   int out_on_device) {
     const GfwRsInputs I = {range_first, n_ranges, pair_ts_us, pair_first, points_a, points_b, n_pairs, track_ts_us, track_wxyz, n_track, nullptr, nullptr, 0};
-    GfwRsSettings S;
-    memset(&S, 0, sizeof(S));
+    GfwRsSettings S = {};
     S.search = true; S.initial_delay_s = initial_delay_s; S.radius_s = radius_s;
     return sync_rs_impl(c, p, cfg, I, S, nullptr, results, round_candidates, round_costs, out_on_device);
 }

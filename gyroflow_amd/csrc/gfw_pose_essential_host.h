@@ -2,32 +2,23 @@
 // gfw_pose_host.h's, beside the generator they share).  Included behind gfw_pose_essential.h (GfwPoseEssArgs) by gfw_api.hip and by whatever else stages a call for
 // those kernels; no kernel's translation unit sees it and it calls nothing of HIP.
 #pragma once
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#include "gfw_layout.h"
+#include "gfw_pairs_host.h"
 
 // The caller's arrays of one call (include/gfwarp.h: gfw_pose_essential)
 struct GfwPoseEssInputs {
     const int32_t *pair_first; const float *points_a, *points_b; int n_pairs;
+    GfwPairSet pairs() const { return GfwPairSet{nullptr, pair_first, points_a, points_b, n_pairs}; }
     const int32_t *octets;
     int num_iters;
 };
 
 // -> true, or false with the reason (the pair named) in `err`
 inline bool gfw_pose_ess_check(const GfwPoseEssInputs &I, char *err, size_t cap) {
+    int total, max_pair;
     if (I.n_pairs < 0 || I.num_iters < 0) { snprintf(err, cap, "bad pose arguments (negative count: %d pairs, %d rounds)", I.n_pairs, I.num_iters); return false; }
-    if (I.n_pairs > GFW_PE_PAIRS_MAX) { snprintf(err, cap, "%d pairs: at most %d in a call", I.n_pairs, GFW_PE_PAIRS_MAX); return false; }
+    if (!gfw_pairs_check(I.pairs(), {"pose", GFW_PE_PAIRS_MAX, GFW_PE_PAIR_MAX, false, false}, total, max_pair, err, cap)) return false;
     if (I.num_iters > GFW_PE_ROUNDS_MAX) { snprintf(err, cap, "%d rounds: at most %d", I.num_iters, GFW_PE_ROUNDS_MAX); return false; }
     if (I.n_pairs == 0) return true;
-    if (!I.pair_first) { snprintf(err, cap, "bad pose arguments (pairs without pair_first)"); return false; }
-    if (I.pair_first[0] < 0) { snprintf(err, cap, "pair 0: pair_first %d is negative", I.pair_first[0]); return false; }
-    for (int p = 0; p < I.n_pairs; ++p) {
-        if (I.pair_first[p + 1] < I.pair_first[p]) { snprintf(err, cap, "pair %d: pair_first descends (%d after %d)", p, I.pair_first[p + 1], I.pair_first[p]); return false; }
-        const int n = I.pair_first[p + 1] - I.pair_first[p];
-        if (n > GFW_PE_PAIR_MAX) { snprintf(err, cap, "pair %d: %d points, at most %d", p, n, GFW_PE_PAIR_MAX); return false; }
-    }
-    if (I.pair_first[I.n_pairs] && (!I.points_a || !I.points_b)) { snprintf(err, cap, "bad pose arguments (%d points without points_a / points_b)", I.pair_first[I.n_pairs]); return false; }
     if (I.num_iters && !I.octets) { snprintf(err, cap, "bad pose arguments (rounds without octets)"); return false; }
     for (int p = 0; p < I.n_pairs; ++p) {
         const int n = I.pair_first[p + 1] - I.pair_first[p];
@@ -49,23 +40,16 @@ struct GfwPoseEssLayout { size_t o_first, o_pts, o_octets, total; };
 inline GfwPoseEssLayout gfw_pose_ess_layout(const GfwPoseEssInputs &I) {
     BlockLayout L;
     GfwPoseEssLayout S;
-    const size_t total = I.n_pairs ? (size_t)I.pair_first[I.n_pairs] : 0;
-    S.o_first = L.add(sizeof(int32_t) * ((size_t)I.n_pairs + 1));
-    S.o_pts = L.add(sizeof(float) * 2 * total * 2);
+    gfw_pairs_add(L, I.n_pairs, (size_t)gfw_pairs_total(I.pairs(), false), S.o_first, S.o_pts);
     S.o_octets = L.add(sizeof(int32_t) * 8 * (size_t)I.n_pairs * (size_t)I.num_iters);
     S.total = L.total;
     return S;
 }
 // Fills the block at (h, d) and the argument block's input pointers and counts
 inline void gfw_pose_ess_fill(const GfwPoseEssLayout &S, const GfwPoseEssInputs &I, char *h, const char *d, GfwPoseEssArgs &A) {
-    const int total = I.n_pairs ? I.pair_first[I.n_pairs] : 0;
-    const size_t pb = sizeof(float) * 2 * (size_t)total;
-    if (I.n_pairs) memcpy(h + S.o_first, I.pair_first, sizeof(int32_t) * ((size_t)I.n_pairs + 1));
-    else *(int32_t *)(h + S.o_first) = 0;
-    if (total) { memcpy(h + S.o_pts, I.points_a, pb); memcpy(h + S.o_pts + pb, I.points_b, pb); }
+    A.total = gfw_pairs_fill(S.o_first, S.o_pts, I.pairs(), false, h, d, A.pair_first, A.points);
     if (I.n_pairs && I.num_iters) memcpy(h + S.o_octets, I.octets, sizeof(int32_t) * 8 * (size_t)I.n_pairs * (size_t)I.num_iters);
-    A.pair_first = (const int32_t *)(d + S.o_first); A.points = (const float *)(d + S.o_pts); A.octets = (const int32_t *)(d + S.o_octets);
-    A.n_pairs = I.n_pairs; A.total = total; A.num_iters = I.num_iters;
+    A.octets = (const int32_t *)(d + S.o_octets); A.n_pairs = I.n_pairs; A.num_iters = I.num_iters;
 }
 // The call's constants
 inline void gfw_pose_ess_constants(int video_w, int video_h, int flow_w, int flow_h, double inlier_threshold, int min_front, GfwPoseEssArgs &A) {

@@ -1,14 +1,12 @@
 // gfw_pose_host.h — host only: what gfw_pose_almeida checks and stages for the kernels of gfw_pose.hip, and the draws of gfw_pose_draws.  Included behind gfw_pose.h
 // (GfwPoseArgs, gfw_pose_math.h) by gfw_api.hip and by whatever else stages a call for those kernels; no kernel's translation unit sees it and it calls nothing of HIP.
 #pragma once
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#include "gfw_layout.h"
+#include "gfw_pairs_host.h"
 
 // The caller's arrays of one call (include/gfwarp.h: gfw_pose_almeida)
 struct GfwPoseInputs {
     const int32_t *pair_first; const float *points_a, *points_b; int n_pairs;
+    GfwPairSet pairs() const { return GfwPairSet{nullptr, pair_first, points_a, points_b, n_pairs}; }
     const int32_t *triples, *sample_first, *samples;
     int num_iters, num_samples;
 };
@@ -16,19 +14,13 @@ inline int gfw_pose_list_len(int n, int num_samples) { return n < num_samples ? 
 
 // -> true, or false with the reason (the pair named) in `err`
 inline bool gfw_pose_check(const GfwPoseInputs &I, char *err, size_t cap) {
+    int total, max_pair;
     if (I.n_pairs < 0 || I.num_iters < 0 || I.num_samples < 0) { snprintf(err, cap, "bad pose arguments (negative count: %d pairs, %d rounds, %d samples)", I.n_pairs, I.num_iters, I.num_samples); return false; }
-    if (I.n_pairs > GFW_POSE_PAIRS_MAX) { snprintf(err, cap, "%d pairs: at most %d in a call", I.n_pairs, GFW_POSE_PAIRS_MAX); return false; }
+    if (!gfw_pairs_check(I.pairs(), {"pose", GFW_POSE_PAIRS_MAX, GFW_POSE_PAIR_MAX, false, false}, total, max_pair, err, cap)) return false;
     if (I.num_iters > GFW_POSE_ROUNDS_MAX) { snprintf(err, cap, "%d rounds: at most %d", I.num_iters, GFW_POSE_ROUNDS_MAX); return false; }
     if (I.n_pairs == 0) return true;
-    if (!I.pair_first) { snprintf(err, cap, "bad pose arguments (pairs without pair_first)"); return false; }
-    if (I.pair_first[0] < 0) { snprintf(err, cap, "pair 0: pair_first %d is negative", I.pair_first[0]); return false; }
-    for (int p = 0; p < I.n_pairs; ++p) {
-        if (I.pair_first[p + 1] < I.pair_first[p]) { snprintf(err, cap, "pair %d: pair_first descends (%d after %d)", p, I.pair_first[p + 1], I.pair_first[p]); return false; }
-        const int n = I.pair_first[p + 1] - I.pair_first[p];
-        if (n > GFW_POSE_PAIR_MAX) { snprintf(err, cap, "pair %d: %d points, at most %d", p, n, GFW_POSE_PAIR_MAX); return false; }
-        if (!I.samples && n > I.num_samples) { snprintf(err, cap, "pair %d: %d points but num_samples %d, and no sample lists", p, n, I.num_samples); return false; }
-    }
-    if (I.pair_first[I.n_pairs] && (!I.points_a || !I.points_b)) { snprintf(err, cap, "bad pose arguments (%d points without points_a / points_b)", I.pair_first[I.n_pairs]); return false; }
+    if (!I.samples && max_pair > I.num_samples) for (int p = 0; p < I.n_pairs; ++p)
+        if (I.pair_first[p + 1] - I.pair_first[p] > I.num_samples) { snprintf(err, cap, "pair %d: %d points but num_samples %d, and no sample lists", p, I.pair_first[p + 1] - I.pair_first[p], I.num_samples); return false; }
     if (I.num_iters && !I.triples) { snprintf(err, cap, "bad pose arguments (rounds without triples)"); return false; }
     if (I.samples && !I.sample_first) { snprintf(err, cap, "bad pose arguments (samples without sample_first)"); return false; }
     if (I.samples && I.sample_first[0] < 0) { snprintf(err, cap, "pair 0: sample_first %d is negative", I.sample_first[0]); return false; }
@@ -58,9 +50,7 @@ struct GfwPoseLayout { size_t o_first, o_pts, o_triples, o_sfirst, o_samples, to
 inline GfwPoseLayout gfw_pose_layout(const GfwPoseInputs &I) {
     BlockLayout L;
     GfwPoseLayout S;
-    const size_t total = I.n_pairs ? (size_t)I.pair_first[I.n_pairs] : 0;
-    S.o_first = L.add(sizeof(int32_t) * ((size_t)I.n_pairs + 1));
-    S.o_pts = L.add(sizeof(float) * 2 * total * 2);
+    gfw_pairs_add(L, I.n_pairs, (size_t)gfw_pairs_total(I.pairs(), false), S.o_first, S.o_pts);
     S.o_triples = L.add(sizeof(int32_t) * 3 * (size_t)I.n_pairs * (size_t)I.num_iters);
     S.o_sfirst = L.add(I.samples ? sizeof(int32_t) * ((size_t)I.n_pairs + 1) : 0);
     S.o_samples = L.add(I.samples && I.n_pairs ? sizeof(int32_t) * (size_t)(I.sample_first[I.n_pairs] - I.sample_first[0]) : 0);
@@ -69,11 +59,7 @@ inline GfwPoseLayout gfw_pose_layout(const GfwPoseInputs &I) {
 }
 // Fills the block at (h, d) and the argument block's input pointers and counts
 inline void gfw_pose_fill(const GfwPoseLayout &S, const GfwPoseInputs &I, char *h, const char *d, GfwPoseArgs &A) {
-    const int total = I.n_pairs ? I.pair_first[I.n_pairs] : 0;
-    const size_t pb = sizeof(float) * 2 * (size_t)total;
-    if (I.n_pairs) memcpy(h + S.o_first, I.pair_first, sizeof(int32_t) * ((size_t)I.n_pairs + 1));
-    else *(int32_t *)(h + S.o_first) = 0;
-    if (total) { memcpy(h + S.o_pts, I.points_a, pb); memcpy(h + S.o_pts + pb, I.points_b, pb); }
+    A.total = gfw_pairs_fill(S.o_first, S.o_pts, I.pairs(), false, h, d, A.pair_first, A.points);
     if (I.n_pairs && I.num_iters) memcpy(h + S.o_triples, I.triples, sizeof(int32_t) * 3 * (size_t)I.n_pairs * (size_t)I.num_iters);
     A.sample_first = nullptr; A.samples = nullptr;
     if (I.samples && I.n_pairs) {
@@ -82,8 +68,7 @@ inline void gfw_pose_fill(const GfwPoseLayout &S, const GfwPoseInputs &I, char *
         if (sf[I.n_pairs]) memcpy(h + S.o_samples, I.samples + I.sample_first[0], sizeof(int32_t) * (size_t)sf[I.n_pairs]);
         A.sample_first = (const int32_t *)(d + S.o_sfirst); A.samples = (const int32_t *)(d + S.o_samples);
     }
-    A.pair_first = (const int32_t *)(d + S.o_first); A.points = (const float *)(d + S.o_pts); A.triples = (const int32_t *)(d + S.o_triples);
-    A.n_pairs = I.n_pairs; A.total = total; A.num_iters = I.num_iters; A.num_samples = I.num_samples;
+    A.triples = (const int32_t *)(d + S.o_triples); A.n_pairs = I.n_pairs; A.num_iters = I.num_iters; A.num_samples = I.num_samples;
 }
 // The call's constants: sizes, K in both precisions, the three derivative matrices, the inlier gate `inlier_angle.to_radians()` = angle * (PI / 180) in f32
 inline void gfw_pose_constants(int video_w, int video_h, int flow_w, int flow_h, float inlier_angle_deg, const double *K, GfwPoseArgs &A) {

@@ -2,15 +2,13 @@
 // (GfwRsArgs) by gfw_api.hip and by whatever else stages a call for those kernels; no kernel's translation unit sees it and it calls nothing of HIP.
 #pragma once
 #include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#include "gfw_layout.h"
+#include "gfw_pairs_host.h"
 
 // The caller's arrays of one call (include/gfwarp.h: gfw_sync_rs_search)
 struct GfwRsInputs {
     const int32_t *range_first; int n_ranges;
     const int64_t *pair_ts_us; const int32_t *pair_first; const float *points_a, *points_b; int n_pairs;
+    GfwPairSet pairs() const { return GfwPairSet{pair_ts_us, pair_first, points_a, points_b, n_pairs}; }
     const int64_t *track_ts_us; const double *track_wxyz; int n_track;
     const int32_t *cand_first; const double *candidates; int n_candidates;      // gfw_sync_rs_costs only (cand_first null: a search)
 };
@@ -25,10 +23,11 @@ inline int gfw_rs_round0_count(double radius_s, double step_s) {
 
 // -> true, or false with the reason (the range or pair named) in `err`
 inline bool gfw_rs_check(const GfwRsInputs &I, const GfwRsSettings &S, char *err, size_t cap) {
+    int points, max_pair;
     if (I.n_ranges < 0 || I.n_pairs < 0 || I.n_track < 0 || I.n_candidates < 0) {
         snprintf(err, cap, "bad rs-sync arguments (negative count: %d ranges, %d pairs, %d track samples, %d candidates)", I.n_ranges, I.n_pairs, I.n_track, I.n_candidates); return false; }
     if (I.n_ranges > GFW_RS_RANGES_MAX) { snprintf(err, cap, "%d ranges: at most %d in a call", I.n_ranges, GFW_RS_RANGES_MAX); return false; }
-    if (I.n_pairs > GFW_RS_PAIRS_MAX) { snprintf(err, cap, "%d pairs: at most %d in a call", I.n_pairs, GFW_RS_PAIRS_MAX); return false; }
+    if (I.n_pairs > GFW_RS_PAIRS_MAX) { snprintf(err, cap, "%d pairs: at most %d in a call", I.n_pairs, GFW_RS_PAIRS_MAX); return false; }      // here: also refused without ranges
     if (S.hypotheses < 0 || S.hypotheses > GFW_RS_HYPOTHESES_MAX || S.refits < 0 || S.refits > GFW_RS_REFITS_MAX || S.sweeps < 1 || S.sweeps > GFW_RS_SWEEPS_MAX || !(S.loss_scale > 0.0) || !isfinite(S.loss_scale)) {
         snprintf(err, cap, "bad rs-sync configuration: %d hypotheses (0 .. %d), %d refits (0 .. %d), %d Jacobi sweeps (1 .. %d), loss_scale %g", S.hypotheses, GFW_RS_HYPOTHESES_MAX, S.refits, GFW_RS_REFITS_MAX, S.sweeps, GFW_RS_SWEEPS_MAX, S.loss_scale);
         return false; }
@@ -45,16 +44,7 @@ inline bool gfw_rs_check(const GfwRsInputs &I, const GfwRsSettings &S, char *err
     for (int r = 0; r < I.n_ranges; ++r)
         if (I.range_first[r + 1] < I.range_first[r]) { snprintf(err, cap, "range %d: range_first descends (%d after %d)", r, I.range_first[r + 1], I.range_first[r]); return false; }
     if (I.range_first[I.n_ranges] != I.n_pairs) { snprintf(err, cap, "range %d: range_first ends at %d, the call has %d pairs", I.n_ranges - 1, I.range_first[I.n_ranges], I.n_pairs); return false; }
-    if (I.n_pairs) {
-        if (!I.pair_first || !I.pair_ts_us) { snprintf(err, cap, "bad rs-sync arguments (pairs without pair_first / pair_ts_us)"); return false; }
-        if (I.pair_first[0] < 0) { snprintf(err, cap, "pair 0: pair_first %d is negative", I.pair_first[0]); return false; }
-        for (int p = 0; p < I.n_pairs; ++p) {
-            if (I.pair_first[p + 1] < I.pair_first[p]) { snprintf(err, cap, "pair %d: pair_first descends (%d after %d)", p, I.pair_first[p + 1], I.pair_first[p]); return false; }
-            const int n = I.pair_first[p + 1] - I.pair_first[p];
-            if (n > GFW_RS_PAIR_MAX) { snprintf(err, cap, "pair %d: %d points, at most %d", p, n, GFW_RS_PAIR_MAX); return false; }
-        }
-        if (I.pair_first[I.n_pairs] > I.pair_first[0] && (!I.points_a || !I.points_b)) { snprintf(err, cap, "bad rs-sync arguments (%d points without points_a / points_b)", I.pair_first[I.n_pairs] - I.pair_first[0]); return false; }
-    }
+    if (!gfw_pairs_check(I.pairs(), {"rs-sync", GFW_RS_PAIRS_MAX, GFW_RS_PAIR_MAX, true, true}, points, max_pair, err, cap)) return false;      // the points count from pair_first[0]
     if (I.n_track < 2) { snprintf(err, cap, "a track of %d samples: at least 2", I.n_track); return false; }
     if (I.n_track > GFW_RS_TRACK_MAX) { snprintf(err, cap, "a track of %d samples: at most %d", I.n_track, GFW_RS_TRACK_MAX); return false; }
     if (!I.track_ts_us || !I.track_wxyz) { snprintf(err, cap, "bad rs-sync arguments (a null track array)"); return false; }
@@ -80,10 +70,10 @@ inline GfwRsLayout gfw_rs_layout(const GfwRsInputs &I) {
     BlockLayout L;
     GfwRsLayout S;
     memset(&S, 0, sizeof(S));
-    S.points = I.n_pairs ? (size_t)(I.pair_first[I.n_pairs] - I.pair_first[0]) : 0;
+    S.points = (size_t)gfw_pairs_total(I.pairs(), true);
     S.o_rfirst = L.add(sizeof(int32_t) * ((size_t)I.n_ranges + 1));
     S.o_prange = L.add(sizeof(int32_t) * (size_t)I.n_pairs);
-    S.o_pfirst = L.add(sizeof(int32_t) * ((size_t)I.n_pairs + 1));
+    S.o_pfirst = L.add(sizeof(int32_t) * ((size_t)I.n_pairs + 1));      // the pair timestamps lie between the shared parts: added here, not by gfw_pairs_add
     S.o_pts_us = L.add(sizeof(int64_t) * 2 * (size_t)I.n_pairs);
     S.o_pts = L.add(sizeof(float) * 2 * S.points * 2);
     S.o_tt = L.add(sizeof(double) * (size_t)I.n_track);
@@ -105,15 +95,11 @@ inline GfwRsLayout gfw_rs_layout(const GfwRsInputs &I) {
 // Fills the block at (h, d) and the argument block's input pointers and counts
 inline void gfw_rs_fill(const GfwRsLayout &S, const GfwRsInputs &I, char *h, const char *d, GfwRsArgs &A) {
     memcpy(h + S.o_rfirst, I.range_first, sizeof(int32_t) * ((size_t)I.n_ranges + 1));
-    int32_t *prange = (int32_t *)(h + S.o_prange), *pfirst = (int32_t *)(h + S.o_pfirst);
+    int32_t *prange = (int32_t *)(h + S.o_prange);
     for (int r = 0; r < I.n_ranges; ++r)
         for (int p = I.range_first[r]; p < I.range_first[r + 1]; ++p) prange[p] = r;
-    const int32_t base = I.n_pairs ? I.pair_first[0] : 0;
-    pfirst[0] = 0;
-    for (int p = 0; p < I.n_pairs; ++p) pfirst[p + 1] = I.pair_first[p + 1] - base;
+    A.total = gfw_pairs_fill(S.o_pfirst, S.o_pts, I.pairs(), true, h, d, A.pair_first, A.points);
     if (I.n_pairs) memcpy(h + S.o_pts_us, I.pair_ts_us, sizeof(int64_t) * 2 * (size_t)I.n_pairs);
-    const size_t pb = sizeof(float) * 2 * S.points;
-    if (S.points) { memcpy(h + S.o_pts, I.points_a + (size_t)base * 2, pb); memcpy(h + S.o_pts + pb, I.points_b + (size_t)base * 2, pb); }
     double *tt = (double *)(h + S.o_tt);
     for (int i = 0; i < I.n_track; ++i) tt[i] = (double)I.track_ts_us[i] / 1000000.0;
     memcpy(h + S.o_tq, I.track_wxyz, sizeof(double) * 4 * (size_t)I.n_track);
@@ -125,10 +111,9 @@ inline void gfw_rs_fill(const GfwRsLayout &S, const GfwRsInputs &I, char *h, con
             for (int p = I.range_first[r]; p < I.range_first[r + 1]; ++p) { pc[p] = at; at += I.cand_first[r + 1] - I.cand_first[r]; }
         A.cand_first = (const int32_t *)(d + S.o_cfirst); A.cand = (const double *)(d + S.o_cand); A.pc_first = (const int64_t *)(d + S.o_pcfirst);
     }
-    A.range_first = (const int32_t *)(d + S.o_rfirst); A.pair_range = (const int32_t *)(d + S.o_prange); A.pair_first = (const int32_t *)(d + S.o_pfirst);
-    A.pair_ts = (const int64_t *)(d + S.o_pts_us); A.points = (const float *)(d + S.o_pts);
+    A.range_first = (const int32_t *)(d + S.o_rfirst); A.pair_range = (const int32_t *)(d + S.o_prange); A.pair_ts = (const int64_t *)(d + S.o_pts_us);
     A.track_t = (const double *)(d + S.o_tt); A.track_q = (const double *)(d + S.o_tq);
-    A.n_ranges = I.n_ranges; A.n_pairs = I.n_pairs; A.total = (int32_t)S.points; A.n_track = I.n_track; A.lds_points = S.max_pair;
+    A.n_ranges = I.n_ranges; A.n_pairs = I.n_pairs; A.n_track = I.n_track; A.lds_points = S.max_pair;
 }
 // The call's constants
 inline void gfw_rs_constants(int video_w, int video_h, int flow_w, int flow_h, double frame_readout_time_ms, const GfwRsSettings &S, GfwRsArgs &A) {

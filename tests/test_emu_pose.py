@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import _emu_pose as EP
+import _pairbase as PB
 import _posecase as PC
 
 
@@ -58,3 +59,10 @@ def test_the_entry_points_check_names_the_pair():
     s[1][63, 39] = 65
     with pytest.raises(EP.Refused, match="pair 1: sample 65 of round 63"):
         run(c, samples=s)
+
+
+def test_a_pair_set_that_starts_behind_unused_points_gives_the_same_bits():
+    """pair_first[0] = 3: the firsts are staged as given and the points from the arrays' start (tests/_pairbase.py)"""
+    c = PB.almeida()
+    quats, _, best, ri, _ = PB.assert_base_does_not_matter(lambda: run(c), "pose_almeida")
+    assert best[1, 0] >= 3 and quats[1, 0] != 1.0 and ri.shape == (2, 4)                   # the fit, the count and the pick ran

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import _emu_pose_essential as EP
+import _pairbase as PB
 import _posesscase as EC
 
 
@@ -58,3 +59,10 @@ def test_the_entry_points_check_names_the_pair():
     o[1, 63, 0] = -1
     with pytest.raises(EP.Refused, match="pair 1: round 63"):
         run(c, octets=o)
+
+
+def test_a_pair_set_that_starts_behind_unused_points_gives_the_same_bits():
+    """pair_first[0] = 3: the firsts are staged as given and the points from the arrays' start (tests/_pairbase.py)"""
+    c = PB.essential()
+    _, _, ess, _, ri, rf = PB.assert_base_does_not_matter(lambda: run(c), "pose_essential")
+    assert ri.shape == (2, 4) and rf.any() and ri.any()                                    # the fits and the counts ran

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import _emu_rs_sync as ER
+import _pairbase as PB
 import _rssynccase as RC
 import _rssyncstmt as RS
 
@@ -59,3 +60,14 @@ def test_the_entry_points_check_names_the_range_or_pair():
     cfg = RC.cfg_of(cam, c.cfg); cfg.rounds = 9
     with pytest.raises(ER.Refused, match="9 rounds, 1 .. 8"):
         ER.sync_rs_search(cam.kp, cam.clip.model, cam.clip.digital, cfg, c.ranges, c.track[0], c.track[1], c.initial_s, c.radius_s)
+
+
+def test_a_pair_set_that_starts_behind_unused_points_gives_the_same_bits():
+    """pair_first[0] = 3: the firsts are staged from 0 and the points from the third on (tests/_pairbase.py)"""
+    c = PB.rs_sync()
+    cam = c.cam
+    args = (cam.kp, cam.clip.model, cam.clip.digital, RC.cfg_of(cam, c.cfg), c.ranges, c.track[0], c.track[1])
+    costs = PB.assert_base_does_not_matter(lambda: ER.sync_rs_costs(*args, c.candidates), "sync_rs_costs")
+    assert len(costs[0]) == 3 and len(set(costs[0].tolist())) == 3 and all(v > 0.0 for v in costs[0])
+    rows, cand, cost = PB.assert_base_does_not_matter(lambda: tuple(ER.sync_rs_search(*args, c.initial_s, c.radius_s)), "sync_rs_search")
+    assert cand.shape == (1, 3) and rows[0][1] == 3 and len(set(cost[0].tolist())) == 3

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import _emu_sync as E
+import _pairbase as PB
 import _synccase as SC
 import _syncstmt as SS
 import _zoomstmt as Z
@@ -195,3 +196,10 @@ def test_no_pairs_and_no_candidates():
     res, coarse, fine_costs = E.sync_visual_search(*emu_args(rng), 0, rng.clip.tracks, 0.0, 0.5, 0.0)                            # `0.5 as usize` = 0: five launches, nothing found
     assert res.found == 0 and len(coarse) == 0 and np.all(fine_costs == 0.0)
     assert list(E.sync_visual_costs(rng.kp, rng.clip.model, rng.clip.digital, SC.sync_search(rng.clip), [], [(0.0, 0.0), (1.0, 3.0)], rng.clip.tracks)) == [0.0, 0.0]
+
+
+def test_a_pair_set_that_starts_behind_unused_points_gives_the_same_bits():
+    """pair_first[0] = 3: the firsts are staged as given and the points from the arrays' start (tests/_pairbase.py)"""
+    rng, cands = PB.visual()
+    costs = PB.assert_base_does_not_matter(lambda: E.sync_visual_costs(*emu_args(rng), cands, rng.clip.tracks), "sync_visual_costs")
+    assert len(costs) == 3 and len(set(costs.tolist())) == 3 and costs[1] == min(costs)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from gyroflow_amd import abi, synchronization as SY, synthetic as S, warp
+import _pairbase as PB
 import _posecase as PC
 import _posestmt as PS
 
@@ -190,3 +191,12 @@ def test_the_python_mirror_end_to_end_equals_the_statement():
     gyro = SY.estimated_gyro({1000000 + 33367 * i: (r and r["euler"]) for i, r in enumerate(got)}, 59.94)
     assert len(gyro) == 4 and all(t > 1000.0 and len(g) == 3 for t, g in gyro.values())
     be.close()
+
+
+def test_a_pair_set_that_starts_behind_unused_points_gives_the_same_bits():
+    """pair_first[0] = 3: the firsts are staged as given and the points from the arrays' start (tests/_pairbase.py)"""
+    c = PB.almeida()
+    be = backend_for(c.cam)
+    quats, _, best, ri, _ = PB.assert_base_does_not_matter(lambda: run(be, c, rounds=True), "pose_almeida")
+    be.close()
+    assert best[1, 0] >= 3 and quats[1, 0] != 1.0 and ri.shape == (2, 4)                   # the fit, the count and the pick ran

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from gyroflow_amd import abi, synchronization as SY, synthetic as S, warp
+import _pairbase as PB
 import _posesscase as EC
 import _posessstmt as ES
 
@@ -229,3 +230,12 @@ def test_the_python_mirror_end_to_end_equals_the_statement():
     with pytest.raises(NotImplementedError):
         SY.estimate_poses(3, cp, pairs, be)
     be.close()
+
+
+def test_a_pair_set_that_starts_behind_unused_points_gives_the_same_bits():
+    """pair_first[0] = 3: the firsts are staged as given and the points from the arrays' start (tests/_pairbase.py)"""
+    c = PB.essential()
+    be = backend_for(c.cam)
+    _, _, _, _, ri, rf = PB.assert_base_does_not_matter(lambda: run(be, c, rounds=True), "pose_essential")
+    be.close()
+    assert ri.shape == (2, 4) and rf.any() and ri.any()                                    # the fits and the counts ran

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from gyroflow_amd import abi, synchronization as SY, synthetic as S, warp
+import _pairbase as PB
 import _rssynccase as RC
 import _rssyncstmt as RS
 
@@ -285,3 +286,19 @@ def test_the_python_mirror_runs_end_to_end_from_the_fast_initial_offset_to_accep
     assert SY.guess_orientation({"a": c.track, "b": c.track}, cp, ranges[:1], matched, sp, be, flow_size=cam.flow)[0] == "b"
     assert SY.guess_orientation({}, cp, ranges[:1], matched, sp, be, flow_size=cam.flow) is None
     be.close()
+
+
+def test_a_pair_set_that_starts_behind_unused_points_gives_the_same_bits():
+    """pair_first[0] = 3: the firsts are staged from 0 and the points from the third on (tests/_pairbase.py)"""
+    c = PB.rs_sync()
+    be = backend_for(c.cam)
+    args = (c.cam.kp, RC.cfg_of(c.cam, c.cfg), c.ranges, c.track[0], c.track[1])
+    costs = PB.assert_base_does_not_matter(lambda: be.sync_rs_costs(*args, c.candidates), "sync_rs_costs")
+    assert len(costs[0]) == 3 and len(set(costs[0].tolist())) == 3 and all(v > 0.0 for v in costs[0])
+
+    def searched():
+        res, cand, cost = be.sync_rs_search(*args, c.initial_s, c.radius_s, rounds=True)
+        return np.array(RC.rows_of(res)), cand, cost
+    rows, cand, cost = PB.assert_base_does_not_matter(searched, "sync_rs_search")
+    be.close()
+    assert cand.shape == (1, 3) and rows[0][1] == 3 and len(set(cost[0].tolist())) == 3

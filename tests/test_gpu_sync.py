@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from gyroflow_amd import abi, synthetic as S, warp
+import _pairbase as PB
 import _synccase as SC
 import _syncstmt as SS
 
@@ -265,3 +266,12 @@ def test_arguments():
         assert costs() == 0 and np.all(out >= 0.0) and find() == 0 and res.found == 1 and res.n_coarse == 5
     finally:
         be.close()
+
+
+def test_a_pair_set_that_starts_behind_unused_points_gives_the_same_bits():
+    """pair_first[0] = 3: the firsts are staged as given and the points from the arrays' start (tests/_pairbase.py)"""
+    rng, cands = PB.visual()
+    be = backend_for(rng.clip)
+    costs = PB.assert_base_does_not_matter(lambda: be.sync_visual_costs(rng.kp, SC.sync_search(rng.clip), rng.pairs, cands), "sync_visual_costs")
+    be.close()
+    assert len(costs) == 3 and len(set(costs.tolist())) == 3 and costs[1] == min(costs)
