@@ -133,7 +133,8 @@ __global__ __launch_bounds__(64) void gfw_rs_cost_kernel(const GfwRsArgs A) {
 }
 
 // Pick stage: workgroup blockIdx.x is a range.  A lane adds the pairs of a contiguous run of candidates and keeps the run's first minimum, lane 0 folds the lanes'
-// picks in lane order: together the first minimum over the candidates in index order.
+// picks in lane order: together the first minimum over the candidates in index order.  A NaN sum is never picked while another sum of the round is not NaN: a run
+// takes only sums that are not NaN, a lane whose run held none is skipped like an empty one, and a round of nothing but NaN picks candidate 0 with its NaN cost.
 __global__ __launch_bounds__(GFW_RS_LANES) void gfw_rs_pick_kernel(const GfwRsArgs A) {
     __shared__ double s_cost[GFW_RS_LANES];
     __shared__ int s_idx[GFW_RS_LANES];
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(GFW_RS_LANES) void gfw_rs_pick_kernel(const GfwRsAr
         for (int p = p0; p < p1; ++p) sum = sum + A.pair_costs[(A.mode == 0 ? (size_t)A.pc_first[p] : (size_t)p * A.n_cand) + c];
         sums[c] = sum;
         if (A.mode == 1) cands[c] = gfw_rs_candidate(A, r, c);
-        if (idx < 0 || sum < best) { best = sum; idx = c; }
+        if (sum == sum && (idx < 0 || sum < best)) { best = sum; idx = c; }         // a NaN sum is never taken: idx stays -1 where the whole run is NaN
     }
     if (A.mode == 0) return;                                                         // workgroup-uniform
     s_cost[t] = best; s_idx[t] = idx;
@@ -173,6 +174,7 @@ __global__ __launch_bounds__(GFW_RS_LANES) void gfw_rs_pick_kernel(const GfwRsAr
             if (s_idx[j] < 0) continue;
             if (pick < 0 || s_cost[j] < low) { low = s_cost[j]; pick = s_idx[j]; }
         }
+        if (pick < 0) { pick = 0; low = sums[0]; }                                   // every sum of the round is NaN: candidate 0, its cost NaN (sums[0] is this lane's own store)
         const double centre = gfw_rs_candidate(A, r, pick);
         s_pick = pick; s_centre = centre;
         gfw_sync_result *res = A.results + r;

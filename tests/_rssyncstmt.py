@@ -21,7 +21,12 @@ compared with it.
              neighbours where both exist and the second difference is positive
 
 Arithmetic: float64, one rounding per written operator (+ - * / sqrt only), batched over candidates and points (elementwise operations round like scalar ones).
-The statement asserts its indices, positive square-root arguments and finite results while it runs."""
+The statement asserts its indices, positive square-root arguments and finite results while it runs.  With `nonfinite=True` (tests/_rstablecase.py) the last two are
+off and a NaN goes through as the device's arithmetic takes it: a zero quaternion gives 0 / 0 = NaN, a NaN cost is a NaN range sum.
+
+NaN rule of the pick: a candidate whose range sum is NaN is never picked while another candidate of that round has a sum that is not NaN — the pick is the first
+minimum, in candidate order, among the sums that are not NaN; where every sum of a round is NaN the pick is candidate 0 and its cost NaN (`found` stays 1).  The
+parabola is skipped where `den > 0.0` is false, so a NaN neighbour means no refinement."""
 import numpy as np
 
 import _posessstmt as ES
@@ -55,8 +60,15 @@ def prepare(cam, cfg, pair_ts_us, points_a, points_b):
     return tuple(out)
 
 
-def quat_at(T, Q, t, conj=False):
+def quat_at(T, Q, t, conj=False, nonfinite=False):
     """the track at the times t [..] -> (w, x, y, z) arrays"""
+    if nonfinite:
+        with np.errstate(all="ignore"):
+            return _quat_at(T, Q, t, conj, True)
+    return _quat_at(T, Q, t, conj, False)
+
+
+def _quat_at(T, Q, t, conj, nonfinite):
     n = len(T)
     assert n >= 2
     tc = np.where(t < T[0], T[0], np.where(t > T[n - 1], T[n - 1], t))
@@ -68,7 +80,7 @@ def quat_at(T, Q, t, conj=False):
     b = [np.where(dot < 0.0, -x, x) for x in b]
     q = [x + ((y - x) * f) for x, y in zip(a, b)]
     s = (((q[0] * q[0]) + (q[1] * q[1])) + (q[2] * q[2])) + (q[3] * q[3])
-    assert (s > 0.0).all()
+    assert nonfinite or (s > 0.0).all()
     nrm = np.sqrt(s)
     q = [x / nrm for x in q]
     if conj:
@@ -129,15 +141,22 @@ def score(cfg, m, t):
     return wave_sum(x2 / (1.0 + x2))
 
 
-def pair_costs(cfg, T, Q, prepared, delays, conj=False, directions=False):
+def pair_costs(cfg, T, Q, prepared, delays, conj=False, directions=False, nonfinite=False):
     """the cost of one pair at the delays [C] (seconds) -> [C] (with `directions` also the final t [C][3])"""
+    if nonfinite:
+        with np.errstate(all="ignore"):
+            return _pair_costs(cfg, T, Q, prepared, delays, conj, directions, True)
+    return _pair_costs(cfg, T, Q, prepared, delays, conj, directions, False)
+
+
+def _pair_costs(cfg, T, Q, prepared, delays, conj, directions, nonfinite):
     ba, ta, bb, tb = prepared
     d = np.asarray(delays, dtype=np.float64).reshape(-1)
     C, n = len(d), len(ta)
     if n == 0:
         return (np.zeros(C), np.zeros((C, 3))) if directions else np.zeros(C)
-    ra = to_world(quat_at(T, Q, ta[None, :] + d[:, None], conj), ba)
-    rb = to_world(quat_at(T, Q, tb[None, :] + d[:, None], conj), bb)
+    ra = to_world(quat_at(T, Q, ta[None, :] + d[:, None], conj, nonfinite), ba)
+    rb = to_world(quat_at(T, Q, tb[None, :] + d[:, None], conj, nonfinite), bb)
     m = ((ra[1] * rb[2]) - (ra[2] * rb[1]), (ra[2] * rb[0]) - (ra[0] * rb[2]), (ra[0] * rb[1]) - (ra[1] * rb[0]))
     t = smallest(moments(m), cfg.sweeps)
     best = score(cfg, m, t)
@@ -159,17 +178,17 @@ def pair_costs(cfg, T, Q, prepared, delays, conj=False, directions=False):
         w = 1.0 / ((1.0 + x2) * (1.0 + x2))
         t = smallest(moments(m, w), cfg.sweeps)
     cost = score(cfg, m, t)
-    assert np.isfinite(cost).all() and np.isfinite(t).all()
+    assert nonfinite or (np.isfinite(cost).all() and np.isfinite(t).all())
     return (cost, t) if directions else cost
 
 
-def range_costs(cfg, T, Q, prepared_pairs, delays, conj=False):
+def range_costs(cfg, T, Q, prepared_pairs, delays, conj=False, nonfinite=False):
     """-> (per pair [C][n_pairs], range sum [C])"""
     d = np.asarray(delays, dtype=np.float64).reshape(-1)
     per = np.zeros((len(d), len(prepared_pairs)))
     total = np.zeros(len(d))
     for p, pr in enumerate(prepared_pairs):
-        per[:, p] = pair_costs(cfg, T, Q, pr, d, conj)
+        per[:, p] = pair_costs(cfg, T, Q, pr, d, conj, nonfinite=nonfinite)
         total = total + per[:, p]
     return per, total
 
@@ -183,14 +202,15 @@ def candidates_total(cfg, radius_s):
 
 
 def first_min(costs):
-    k = 0
-    for i in range(1, len(costs)):
-        if costs[i] < costs[k]:
+    """the first minimum among the costs that are not NaN; 0 where every cost is NaN"""
+    k = -1
+    for i in range(len(costs)):
+        if costs[i] == costs[i] and (k < 0 or costs[i] < costs[k]):
             k = i
-    return k
+    return max(k, 0)
 
 
-def search_range(cfg, T, Q, prepared_pairs, initial_delay_s, radius_s, conj=False):
+def search_range(cfg, T, Q, prepared_pairs, initial_delay_s, radius_s, conj=False, nonfinite=False):
     """full_sync of one range -> dict(found, n_coarse, coarse_value, coarse_cost, value, cost, candidates [total], costs [total])"""
     n0 = round0_count(radius_s, cfg.step_s)
     h = (n0 - 1) // 2
@@ -202,7 +222,7 @@ def search_range(cfg, T, Q, prepared_pairs, initial_delay_s, radius_s, conj=Fals
     cand = float(initial_delay_s) + ((np.arange(n0) - h).astype(np.float64) * step)
     at = 0
     for rnd in range(cfg.rounds):
-        _, costs = range_costs(cfg, T, Q, prepared_pairs, cand, conj)
+        _, costs = range_costs(cfg, T, Q, prepared_pairs, cand, conj, nonfinite)
         k = first_min(costs)
         out["candidates"][at:at + len(cand)], out["costs"][at:at + len(cand)] = cand, costs
         at += len(cand)
@@ -214,7 +234,7 @@ def search_range(cfg, T, Q, prepared_pairs, initial_delay_s, radius_s, conj=Fals
                 den = (costs[k - 1] - (2.0 * costs[k])) + costs[k + 1]
                 if den > 0.0:
                     value = cand[k] + (step * ((0.5 * (costs[k - 1] - costs[k + 1])) / den))
-            assert np.isfinite(value)
+            assert nonfinite or np.isfinite(value)
             out.update(value=float(value), cost=float(costs[k]))
         else:
             step = step / 8.0
@@ -222,24 +242,24 @@ def search_range(cfg, T, Q, prepared_pairs, initial_delay_s, radius_s, conj=Fals
     return out
 
 
-def search(cam, cfg, track_ts_us, track_wxyz, ranges, initial_delay_s, radius_s, conj=False):
+def search(cam, cfg, track_ts_us, track_wxyz, ranges, initial_delay_s, radius_s, conj=False, nonfinite=False):
     """gfw_sync_rs_search's outputs.  ranges: [[(ts_a_us, ts_b_us, points_a, points_b)]] -> (results int/float rows [n][6], candidates [n][total], costs [n][total])"""
     T, Q = track_seconds(track_ts_us), np.asarray(track_wxyz, dtype=np.float64).reshape(-1, 4)
     total = candidates_total(cfg, radius_s)
     res, cands, costs = [], np.zeros((len(ranges), total)), np.zeros((len(ranges), total))
     for r, pairs in enumerate(ranges):
         prepared = [prepare(cam, cfg, (ta, tb), a, b) for ta, tb, a, b in pairs]
-        o = search_range(cfg, T, Q, prepared, initial_delay_s, radius_s, conj)
+        o = search_range(cfg, T, Q, prepared, initial_delay_s, radius_s, conj, nonfinite)
         res.append((o["found"], o["n_coarse"], o["coarse_value"], o["coarse_cost"], o["value"], o["cost"]))
         cands[r], costs[r] = o["candidates"], o["costs"]
     return res, cands, costs
 
 
-def costs_of(cam, cfg, track_ts_us, track_wxyz, ranges, candidates):
+def costs_of(cam, cfg, track_ts_us, track_wxyz, ranges, candidates, nonfinite=False):
     """gfw_sync_rs_costs' outputs: one array of range costs per range for its candidates (seconds)"""
     T, Q = track_seconds(track_ts_us), np.asarray(track_wxyz, dtype=np.float64).reshape(-1, 4)
     out = []
     for pairs, cand in zip(ranges, candidates):
         prepared = [prepare(cam, cfg, (ta, tb), a, b) for ta, tb, a, b in pairs]
-        out.append(range_costs(cfg, T, Q, prepared, cand)[1])
+        out.append(range_costs(cfg, T, Q, prepared, cand, nonfinite=nonfinite)[1])
     return out
